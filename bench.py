@@ -16,9 +16,16 @@ barrier + torch.cuda.synchronize() on both sides, max over ranks; rank 0 prints 
 `python bench.py --gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself
 (re-executes under torch.distributed.run on 127.0.0.1) and prints the one line of rank 0.
 
-The timed region is repeated (R times exactly K steps, each between barrier + synchronize) until it
-has run for >= 0.5 s; `value` comes from the MEDIAN repeat (K = 20 steps is ~2 ms: one repeat is
-noise), min / max are in config.timing.
+The timed region is exactly K steps.  `--min-time S` (default 0) repeats it, R times exactly K steps,
+each between barrier + synchronize, until it has run for >= S seconds; `value` then comes from the
+MEDIAN repeat, min / max are in config.timing.
+
+`--dump-outputs DIR` writes what the timed path computed in its last timed step, as a caller of that
+path holds it: DIR/preds.npy (the step's predictions) and DIR/<parameter name>.npy (every weight after
+that step's optimizer update), float32 (float64 stays float64).  Graph, features, seed batches and
+initial weights come from fixed seeds, so two builds run with the same arguments can be compared
+output for output.  A weight of more than 4 Mi elements (the Pokec shape's embedding table) is dumped
+as a fixed, seeded sample of its rows; the whole dump stays below 64 MB.
 
 Extra objects on the line (tier contract, section 4 of the task):
   roofline     the step's dominant launch, timed IN PLACE (engine_roofline): the command list of the queue-mode
@@ -102,6 +109,37 @@ def build_model(gs, adj, aggregator="mean", rng="philox", seed=123, fanout=FANOU
     model.train_sampler.seed = seed
     model.val_sampler.seed = seed
     return model
+
+
+DUMP_MAX_ELEMS = 1 << 22        # --dump-outputs: a larger weight is sampled by rows
+DUMP_MAX_BYTES = 64 << 20
+
+
+def snapshot_outputs(preds, model, engine=None):
+    """-> {name: host array} of what the timed path's caller holds after its last step (see --dump-outputs): the
+    step's predictions and the model's parameters.  Taken right after the timed region, before anything else
+    steps the engine."""
+    if hasattr(engine, "sync_rows"):
+        engine.sync_rows()                         # deferred table rows: settle every row first
+    torch.cuda.synchronize()
+    out = {}
+    for name, t in [("preds", preds)] + list(model.named_parameters()):
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            n_rows = int(t.shape[0])
+            k = max(1, DUMP_MAX_ELEMS // max(1, t.numel() // n_rows))
+            rows = np.sort(np.random.default_rng(0).choice(n_rows, size=min(k, n_rows), replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        out[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes" % total
+    return out
+
+
+def write_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def rows_per_seed(fanout):
@@ -421,8 +459,9 @@ def _lognormal_graph(gs, n_nodes, mu, sigma, max_deg, seed=0):
 
 
 def _timed_steps(step, n_warm, n_steps, finish=None, ddp=None):
-    """finish: work the steps deferred (an engine's sync_rows) -- inside the timed region.  With a process group: a
-    barrier + synchronize on both sides of the timed region, the MAX over the ranks."""
+    """-> (seconds per step, what the last timed step returned).  finish: work the steps deferred (an engine's
+    sync_rows) -- inside the timed region.  With a process group: a barrier + synchronize on both sides of the timed
+    region, the MAX over the ranks."""
     def sync():
         if ddp is not None:
             ddp.barrier()
@@ -434,7 +473,7 @@ def _timed_steps(step, n_warm, n_steps, finish=None, ddp=None):
     sync()
     t0 = time.perf_counter()
     for k in range(n_warm, n_warm + n_steps):
-        step(k)
+        last = step(k)
     if finish is not None:
         finish()
     sync()
@@ -443,7 +482,7 @@ def _timed_steps(step, n_warm, n_steps, finish=None, ddp=None):
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-    return dt / n_steps
+    return dt / n_steps, last
 
 
 def _placeholder_adj():
@@ -451,7 +490,7 @@ def _placeholder_adj():
     return sparse.csr_matrix((np.array([1, 1]), np.array([0, 0]), np.array([0, 0, 1, 2])), shape=(3, 1))
 
 
-def extra_papers(gs, dev, steps=60, warmup=5, n_nodes=111_059_956, B=BATCH, ddp=None):
+def extra_papers(gs, dev, steps=60, warmup=5, n_nodes=111_059_956, B=BATCH, ddp=None, keep=False):
     """BASELINE configs[4] on one GPU at its REAL size: 111 059 956 nodes, ~3.2e9 edges (int64 row offsets, 13 GB of
     int32 neighbour ids), 128-d bf16 features (28 GB), mean aggregator, three layers, fan-out 15/10/5 -- graph and
     table generated on the device (store.DeviceCSR.synthetic / FeatureStore.synthetic; ~43 GB of the 288 GB).
@@ -464,6 +503,7 @@ def extra_papers(gs, dev, steps=60, warmup=5, n_nodes=111_059_956, B=BATCH, ddp=
     gs.nn_modules.SparseUniformNeighborSampler.rng_default = "philox"
     specs = [{"n_train_samples": f, "n_val_samples": f, "output_dim": h,
               "activation": (lambda x: x) if i == 2 else F.relu} for i, (f, h) in enumerate(zip(fan, dims))]
+    torch.manual_seed(0)                        # the initial weights
     model = gs.GSSupervised(sampler_class=gs.sampler_lookup["sparse_uniform_neighbor_sampler"], adj=_placeholder_adj(),
                             train_adj=_placeholder_adj(), prep_class=gs.prep_lookup["identity"],
                             aggregator_class=gs.aggregator_lookup["mean"], input_dim=128, n_nodes=n_rows,
@@ -479,7 +519,8 @@ def extra_papers(gs, dev, steps=60, warmup=5, n_nodes=111_059_956, B=BATCH, ddp=
     tg = torch.from_numpy(rng.integers(0, N_CLASSES, size=(total, world * B, 1))[:, rank * B:(rank + 1) * B].copy()).to(dev)
     eng = gs.engine.FusedMeanTrainStep(model, store, gs.ProblemLosses.classification, ids[0], tg[0], ddp=ddp)
     eng.load_epoch(ids, tg)
-    dt = _timed_steps(lambda k: eng.step_queue(), warmup, steps, ddp=ddp)
+    dt, last = _timed_steps(lambda k: eng.step_queue(), warmup, steps, ddp=ddp)
+    outputs = snapshot_outputs(last, model, eng) if keep else None
     csr.check()
     rows = 1 + 15 + 150 + 750
     rec = {"config": "BASELINE configs[4] at its real size (N=%d, nnz=%d): mean, 3 layers, fan-out 15/10/5, 128-d bf16 "
@@ -493,10 +534,12 @@ def extra_papers(gs, dev, steps=60, warmup=5, n_nodes=111_059_956, B=BATCH, ddp=
     else:
         rec["exchange_us"] = exchange_in_list_us(eng, lambda k: eng.step_queue())
     rec["_engine"] = eng
+    if keep:
+        rec["_outputs"] = outputs
     return rec
 
 
-def extra_pokec(gs, dev, steps=40, warmup=5, B=BATCH, precision=None, engine="fused", ddp=None):
+def extra_pokec(gs, dev, steps=40, warmup=5, B=BATCH, precision=None, engine="fused", ddp=None, keep=False):
     """BASELINE configs[3] at its SHAPE on one GPU: Pokec-sized graph (1.63 M nodes, ~6e7 edges), no features,
     trainable 64-d node embeddings (node_embedding prep), attention aggregator (hidden 32), fan-out 20/15,
     regression_mae.  The step keeps the reference's DENSE embedding-gradient semantics (every row of the 418 MB
@@ -511,6 +554,7 @@ def extra_pokec(gs, dev, steps=40, warmup=5, B=BATCH, precision=None, engine="fu
     gs.nn_modules.SparseUniformNeighborSampler.rng_default = "philox"
     specs = [{"n_train_samples": f, "n_val_samples": f, "output_dim": h,
               "activation": (lambda x: x) if i == 1 else F.relu} for i, (f, h) in enumerate(zip(fan, dims))]
+    torch.manual_seed(0)                        # the initial weights and embeddings
     model = gs.GSSupervised(sampler_class=gs.sampler_lookup["sparse_uniform_neighbor_sampler"], adj=adj, train_adj=adj,
                             prep_class=gs.prep_lookup["node_embedding"],
                             aggregator_class=gs.aggregator_lookup["attention"], input_dim=None,
@@ -535,7 +579,9 @@ def extra_pokec(gs, dev, steps=40, warmup=5, B=BATCH, precision=None, engine="fu
     # deferred table rows (engine.sync_rows): the timed region ends with every row of the table settled, i.e. it
     # pays for one dense catch-up pass per `steps` steps (a training run pays one per epoch, before evaluation)
     deferred = bool(getattr(step_fn, "lazy_rows", False))
-    dt = _timed_steps(lambda k: step_fn(ids[k], tg[k]), warmup, steps, finish=step_fn.sync_rows if deferred else None, ddp=ddp)
+    dt, last = _timed_steps(lambda k: step_fn(ids[k], tg[k]), warmup, steps, finish=step_fn.sync_rows if deferred else None,
+                            ddp=ddp)
+    outputs = snapshot_outputs(last, model, step_fn) if keep else None
     if deferred:
         how += "; table rows updated when touched or read (gsage_rows_*: bit-identical to the dense update), " \
                "all rows settled inside the timed region"
@@ -554,6 +600,8 @@ def extra_pokec(gs, dev, steps=40, warmup=5, B=BATCH, precision=None, engine="fu
             rec["exchange_us"] = exchange_in_list_us(step_fn, lambda k: step_fn(ids[k % total], tg[k % total]))
         step_fn.sync_rows()
     rec["_engine"] = step_fn
+    if keep:
+        rec["_outputs"] = outputs
     return rec
 
 
@@ -786,13 +834,19 @@ def main():
                          "a device-resident batch queue")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--min-time", type=float, default=0.5,
-                    help="repeat the K-step timed region until it has run this many seconds in total")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="repeat the K-step timed region until it has run this many seconds in total (default 0: "
+                         "one timed region of exactly K steps)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the predictions and weights of the last timed step as DIR/<name>.npy (needs one timed "
+                         "region: --min-time 0)")
     ap.add_argument("--extra", type=str, default="max_pool,attention,papers,pokec,ddp_1rank,cli,b4096,fp32",
                     help="comma-separated additional configurations measured after the main line (N=1 only) and "
                          "reported under `extra`: an aggregator name (same graph), `papers` / `pokec` (BASELINE "
                          "configs[4] / configs[3] shapes on their own synthetic graphs); '' for none")
     args = ap.parse_args()
+    if args.dump_outputs and args.min_time > 0:
+        ap.error("--dump-outputs needs exactly one timed region of K steps (--min-time 0)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
 
@@ -816,9 +870,12 @@ def main():
     if args.config != "reddit":
         # BASELINE configs[3] / configs[4] as the main line (one command per configuration and GPU count)
         fn = extra_pokec if args.config == "pokec" else extra_papers
-        rec = fn(gs, dev, steps=args.steps, warmup=args.warmup, B=args.batch_size, ddp=ddp)
+        rec = fn(gs, dev, steps=args.steps, warmup=args.warmup, B=args.batch_size, ddp=ddp,
+                 keep=bool(args.dump_outputs) and rank == 0)
         rec.pop("_engine", None)
         if rank == 0:
+            if args.dump_outputs:
+                write_outputs(args.dump_outputs, rec.pop("_outputs"))
             line = {"metric": "seed-nodes/sec", "value": rec["value"], "unit": "seed-nodes/sec", "n_gpus": world,
                     "steps": args.steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_step"], "higher_is_better": True,
                     "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -858,8 +915,10 @@ def main():
             ddp.barrier()
         torch.cuda.synchronize()
 
-    def measure(aggregator, min_time):
-        """Build model + engine for `aggregator`, warm up, time R x exactly K steps.  Returns a dict."""
+    def measure(aggregator, min_time, keep=False):
+        """Build model + engine for `aggregator`, warm up, time R x exactly K steps (keep: snapshot what the last
+        timed step computed, see --dump-outputs).  Returns a dict."""
+        torch.manual_seed(0)                            # the initial weights
         model = build_model(gs, data["adj"], aggregator=aggregator, rng="philox", fanout=fanout,
                             hidden=hidden).to(dev)
         if ddp is not None:
@@ -901,12 +960,12 @@ def main():
             sync()
             t0 = time.perf_counter()
             for _ in range(args.steps):                 # EXACTLY K steps per timed repeat
-                run_step(k)
+                last = run_step(k)
                 k += 1
             sync()
             dt = time.perf_counter() - t0
             if hasattr(step_fn, "flush") and args.pipeline:
-                step_fn.flush()      # pipelined engine: drain the last compute stage (outside the clock)
+                last = step_fn.flush()      # pipelined engine: drain the last compute stage (outside the clock)
                 torch.cuda.synchronize()
             if ddp is not None:
                 t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -921,13 +980,17 @@ def main():
                 stop = bool(flag.item())
             if stop:
                 break
+        outputs = snapshot_outputs(last, model, step_fn) if keep else None
         model.train_sampler.csr(dev).check()
         xus = exchange_in_list_us(step_fn, run_step) if ddp is not None else None      # (collective steps: every rank)
         med = float(np.median(times))
         return {"model": model, "step_fn": step_fn, "engine": engine, "queued": queued, "use_graph": use_graph,
-                "elapsed": med, "times": times, "launches_per_step": float(np.median(launches)), "exchange_us": xus}
+                "elapsed": med, "times": times, "launches_per_step": float(np.median(launches)), "exchange_us": xus,
+                "outputs": outputs}
 
-    res = measure(args.aggregator, args.min_time)
+    res = measure(args.aggregator, args.min_time, keep=bool(args.dump_outputs) and rank == 0)
+    if res["outputs"] is not None:
+        write_outputs(args.dump_outputs, res.pop("outputs"))
     elapsed, step_fn, model = res["elapsed"], res["step_fn"], res["model"]
     elem = store.data.element_size()
 
