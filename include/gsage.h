@@ -930,6 +930,37 @@ int gsage_metric_f1(const float *logits, int64_t ld, const void *targets, int mu
                     int64_t ldy, int64_t B, int32_t C, int32_t *counts, double *out, void *stream);
 int gsage_metric_mae(const float *y_true, const float *y_pred, int64_t n, double *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Full-neighbourhood segment reduce (layer-wise inference, infer.py)
+ *
+ *     out[v, c] = reduce_{u in N(v)} table[u, c]   for every row v of a CSR adjacency, c < D
+ *     N(v) = col[rowptr[v] .. rowptr[v+1]); a row of degree 0 has the single neighbour 0 (the dummy).
+ *   mode GSAGE_SEG_MEAN:              (1/|N(v)|) sum
+ *   mode GSAGE_SEG_MAX:               max
+ *   mode GSAGE_SEG_SOFTMAX_WEIGHTED:  sum_u softmax_u(keys[u, :32] . keys[v, :32]) table[u, c]
+ *     (keys: fp32 [n_rows, ldk], ldk >= 32, 16-byte aligned rows; online softmax, fp32).
+ *   table: bf16 or fp32 (dtype), ld a multiple of 16 bytes with round_up(D, 16 bytes) <= ld; fp32 accumulation.
+ *   out: bf16 or fp32 (out_dtype) [n_rows, out_ld] -- may point into the middle of a wider row (the right half
+ *   of a concat); only columns < D are stored.  act: GSAGE_ACT_NONE or GSAGE_ACT_RELU (epilogue).
+ *   Plan (built by the caller once per adjacency):
+ *     order     int32 [n_short]         rows of degree <= slice_len (their order is the schedule: degree-descending)
+ *     slices    int64 [n_slices, 2]     (row, first edge) of the slice_len-edge slices of every longer row
+ *     long_rows int64 [n_long, 2]       (row, index of its first slice); the slices of a row are consecutive
+ *   partials: fp32 [n_slices, ldp], ldp >= gsage_segment_reduce_ldp(D), 16-byte aligned (unused if n_slices == 0).
+ *   Two launches (short rows + slices, then the per-row merge in slice order); no floating-point atomics: the same
+ *   inputs give the same bits.  err_flag (int32, may be NULL) is set to 1 when a neighbour id is outside
+ *   [0, n_rows); such an id reads row 0.
+ * ---------------------------------------------------------------------------------------- */
+enum { GSAGE_SEG_MEAN = 0, GSAGE_SEG_MAX = 1, GSAGE_SEG_SOFTMAX_WEIGHTED = 2 };
+/* HOST: the smallest row length of the partials buffer for width D (-1 when D <= 0) */
+int64_t gsage_segment_reduce_ldp(int64_t D);
+int gsage_segment_reduce(int mode, const void *table, int dtype, int64_t ld, int64_t D, const float *keys,
+                         int64_t ldk, const int64_t *rowptr, const int32_t *col, int64_t n_rows,
+                         const int32_t *order, int64_t n_short, const int64_t *slices, int64_t n_slices,
+                         const int64_t *long_rows, int64_t n_long, int32_t slice_len, float *partials,
+                         int64_t ldp, void *out, int out_dtype, int64_t out_ld, int act, int32_t *err_flag,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,11 +9,13 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
     nn_modules.py, models.py, problem.py, helpers.py, lr.py, train.py
                               same names and interfaces as the reference's files
     dist.py                   RCCL data-parallel gradient sync
+    infer.py                  layer-wise full-neighbourhood inference, node-embedding export
     engine/                   the whole train_step as recorded launches (captured autograd path; fused mean /
                               pool / attention engines on a shared base)
 """
-from . import _native, dist, engine, helpers, nn_modules, ops, optim, problem, store               # noqa: F401
+from . import _native, dist, engine, helpers, infer, nn_modules, ops, optim, problem, store        # noqa: F401
 from .helpers import set_seeds, to_numpy                            # noqa: F401
+from .infer import full_neighbour                                   # noqa: F401
 from .lr import LRSchedule                                          # noqa: F401
 from .models import GSSupervised                                    # noqa: F401
 from .nn_modules import aggregator_lookup, prep_lookup, sampler_lookup   # noqa: F401
@@ -21,4 +23,4 @@ from .problem import DeviceMetrics, NodeProblem, ProblemLosses, ProblemMetrics, 
 from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef                  # noqa: F401
 
 __all__ = ["GSSupervised", "NodeProblem", "aggregator_lookup", "prep_lookup", "sampler_lookup",
-           "set_seeds", "to_numpy", "LRSchedule", "FeatureStore", "DeviceCSR", "RowRef", "ops"]
+           "set_seeds", "to_numpy", "LRSchedule", "FeatureStore", "DeviceCSR", "RowRef", "ops", "full_neighbour"]

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libgsage_hip.so")
 F32, BF16 = 0, 1
 POOL_MAX, POOL_MEAN = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
+SEG_MEAN, SEG_MAX, SEG_SOFTMAX_WEIGHTED = 0, 1, 2
 ABI_VERSION = 6
 
 _vp = ctypes.c_void_p
@@ -162,6 +163,9 @@ SIGNATURES = {
     "gsage_head_l1_scratch": (_int, [_i64, _i64]),
     "gsage_metric_f1": (_int, [_vp, _i64, _vp, _int, _int, _i64, _i64, _i32, _vp, _vp, _vp]),
     "gsage_metric_mae": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "gsage_segment_reduce_ldp": (_i64, [_i64]),
+    "gsage_segment_reduce": (_int, [_int, _vp, _int, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
+                                    _vp, _i64, _i32, _vp, _i64, _vp, _int, _i64, _int, _vp, _vp]),
     "gsage_attn_bwd": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _int, _i64, _vp, _i64, _i32, _i64, _i64,
                               _vp, _i64, _vp, _i64, _vp]),
 }

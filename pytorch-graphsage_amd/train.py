@@ -22,6 +22,12 @@ when launched under torch.distributed.run (one process per GPU, RCCL grad all-re
                   train.py:64) -- the per-batch readback is the one thing left that costs a host sync per step.
   eager           the module path (GSSupervised.train_step), one launch per operator.
 Data-parallel runs keep batches of one fixed size (--batch-size / world per rank, counter-based sampler).
+
+Layer-wise full-neighbourhood inference (infer.py, opt-in; the default output is unchanged):
+  --full-neighbour-eval   val_metric / test_f1 come from infer.full_neighbour on the val / test folds (deterministic:
+                          every neighbour of every node, no sampling) instead of the sampled forward
+  --save-embeddings PATH  after training, F.normalize(H^L) of every row of the adjacency, in node-id order, as one
+                          .npy (rank 0)
 """
 from __future__ import division, print_function
 
@@ -88,6 +94,24 @@ def evaluate(model, problem, mode='val'):
         # scored on the device (problem.DeviceMetrics): the fold's predictions never travel to the host
         return batch_metric(problem.task, torch.cat(acts), torch.cat(preds))
     return problem.metric_fn(np.vstack([to_numpy(a) for a in acts]), np.vstack([to_numpy(p) for p in preds]))
+
+
+def full_neighbour_evaluate(model, problem, mode='val'):
+    """evaluate() by layer-wise full-neighbourhood inference (infer.full_neighbour) of the fold's nodes; every rank
+    computes the whole fold.  No random draw is consumed."""
+    assert mode in ['test', 'val']
+    nodes = problem.nodes[mode]
+    _, acts = problem._batch(nodes, problem.targets[nodes])
+    dev = problem.feats.device
+    preds = gs.full_neighbour(model, problem.feats, nodes=torch.from_numpy(nodes).to(dev))
+    return batch_metric(problem.task, acts.reshape(acts.shape[0], -1), preds)
+
+
+def save_embeddings(model, problem, path):
+    """F.normalize(H^L) of every row, node-id order, one .npy."""
+    _, emb = gs.full_neighbour(model, problem.feats, nodes=torch.zeros(1, dtype=torch.int64,
+                                                                       device=problem.feats.device), embeddings=True)
+    np.save(path, emb.cpu().numpy())
 
 
 class FusedEvaluator(object):
@@ -181,6 +205,8 @@ def parse_args(argv=None):
     parser.add_argument('--rng', type=str, default='compat', choices=['compat', 'philox'])
     parser.add_argument('--precision', type=str, default='bf16', choices=['bf16', 'fp32'])
     parser.add_argument('--engine', type=str, default='auto', choices=['auto', 'eager', 'fused'])
+    parser.add_argument('--full-neighbour-eval', action="store_true")
+    parser.add_argument('--save-embeddings', type=str, default=None)
 
     args = parser.parse_args(argv)
     args.cuda = not args.no_cuda
@@ -234,6 +260,13 @@ def main(argv=None, problem=None):
     if ddp is not None:
         gs.dist.attach(model, ddp, seed=args.seed)
     print(model, file=sys.stderr)
+    if args.full_neighbour_eval or args.save_embeddings:
+        try:
+            gs.infer.check_supported(model)
+        except ValueError as e:
+            raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings: %s' % e)
+    evaluate_fn = (lambda mode: full_neighbour_evaluate(model, problem, mode=mode)) if args.full_neighbour_eval else \
+        (lambda mode: evaluate(model, problem, mode=mode))
 
     set_seeds(args.seed ** 2)                          # train.py:133
     start_time = time()
@@ -260,7 +293,7 @@ def main(argv=None, problem=None):
                              "time": time() - start_time}))
                 sys.stdout.flush()
         model.eval()
-        val_metric = evaluate(model, problem, mode='val')
+        val_metric = evaluate_fn('val')
 
     gs.helpers.legacy_stream.release()                 # hand numpy's stream back to the host
     print('-- done --', file=sys.stderr)
@@ -269,7 +302,9 @@ def main(argv=None, problem=None):
                      "time": time() - start_time}))
         sys.stdout.flush()
         if args.show_test:
-            print(dumps({"test_f1": evaluate(model, problem, mode='test')}))
+            print(dumps({"test_f1": evaluate_fn('test')}))
+        if args.save_embeddings:
+            save_embeddings(model, problem, args.save_embeddings)
     if ddp is not None:
         ddp.close()
 
@@ -364,8 +399,12 @@ def train_fused(args, problem, model, ddp, start_time, cls):
     assert live is None or step.fused_head or step.fused_l1 or min(live) == B
     val_metric = train_metric = None
     epoch = 0
-    fold_eval = FusedEvaluator(cls, model, problem).prepare('val') if os.environ.get("GSAGE_FUSED_EVAL", "1") == "1" else \
-        (lambda mode='val': evaluate(model, problem, mode=mode))
+    if args.full_neighbour_eval:
+        fold_eval = lambda mode='val': full_neighbour_evaluate(model, problem, mode=mode)      # noqa: E731
+    elif os.environ.get("GSAGE_FUSED_EVAL", "1") == "1":
+        fold_eval = FusedEvaluator(cls, model, problem).prepare('val')
+    else:
+        fold_eval = lambda mode='val': evaluate(model, problem, mode=mode)                     # noqa: E731
     # The per-batch line (train.py:150-158) without a host sync per step: batch b is scored on the device right behind
     # its step into a small device ring (problem.MetricRing), and the ring is read back -- one copy -- every 32 batches
     # and at the end of every epoch: same lines, same order, same values, printed 32 at a time.
@@ -447,6 +486,8 @@ def train_fused(args, problem, model, ddp, start_time, cls):
         sys.stdout.flush()
         if args.show_test:
             print(dumps({"test_f1": test_metric}))
+        if args.save_embeddings:
+            save_embeddings(model, problem, args.save_embeddings)
     if ddp is not None:
         ddp.close()
     return step
