@@ -11,7 +11,7 @@ import torch
 from .. import _native as nat
 from .. import ops
 from ..nn_modules import AttentionAggregator, IdentityPrep, NodeEmbeddingPrep
-from .common import FusedTrainStep, _PrepDesc, _ReduceDesc, _r64
+from .common import FusedTrainStep, _PrepDesc, _Wgrad, _r64
 
 
 class FusedAttnTrainStep(FusedTrainStep):
@@ -126,40 +126,30 @@ class FusedAttnTrainStep(FusedTrainStep):
             return self.store.data, self.ldin[0], self._cur_ids
         return self.g0_set[s], self.ldin[0], None
 
-    def _wg_problems(self, l, s):
-        """(dC, A, lda, M, Ntot, K, parameter) of the four weight gradients of level l"""
-        inp, ld, rows = self._in(l, s)
-        h, Ha, D, layer = self.h[l], self.Ha, self.din[l], self.layers[l]
-        probs = [(self.dc[l][:, :h], inp, ld, self.rows[l], h, D, layer.fc_x.weight, rows),
-                 (self.dc[l][:, h:], self.aggc[l], ld, self.rows[l], h, D, layer.fc_neib.weight, None),
-                 (self.da[l], self.hid[l], self.HA_LD, self.rall[l], Ha, Ha, layer.att[2].weight, None),
-                 (self.dhid[l], inp, ld, self.rall[l], Ha, D, layer.att[0].weight, rows)]
-        if l == 0 and self.emb:      # the prep's affine: d out^T x embedding rows
-            probs.append(self._emb_wgrad_problem())
-        return probs
-
     def _init_reduce(self):
-        dev, f32 = self.dev, torch.float32
-        rdesc, self.slabs = [], []
-        # K5b workgroups per problem: the problems go out eight to a launch in the order of _stage_compute and one
-        # workgroup fits per CU, so each launch's problems are sized together to fill the chip once
-        # (ops.wgrad_balance)
-        order = [(l, i, p) for l in range(self.L - 1, -1, -1) for i, p in enumerate(self._wg_problems(l, 0))]
-        targets = ops.wgrad_balance([(p[3], p[4], p[5]) for _l, _i, p in order])
-        self.wg_target = {(l, i): t for (l, i, _p), t in zip(order, targets)}
-        for l in range(self.L):
-            bufs = []
-            for i, (dC, A, lda, M, ntot, K, prm, _rows) in enumerate(self._wg_problems(l, 0)):
-                rps, S, ldk = ops.wgrad_plan(M, ntot, K, self.wg_target[(l, i)])
-                buf = torch.zeros(S, ntot, ldk, dtype=f32, device=dev)
-                bufs.append(buf)
-                rdesc.append(_ReduceDesc(buf.data_ptr(), ntot * ldk, self.poff[self.pidx[id(prm)]], S, ntot, K, ldk))
-            self.slabs.append(bufs)
-        if self.emb:
-            rdesc.append(self._emb_reduce_desc())
-        self._install_reduce(rdesc)
-        if self.emb:
-            self._init_emb_optimizer()
+        """finalisation table: the slabs of levels 0 .. L-1 in their launch order (the prep's inside level 0)"""
+        srcs, prms = self._plan_wgrad(), []
+        for l, layer in enumerate(self.layers):
+            prms += [layer.fc_x.weight, layer.fc_neib.weight, layer.att[2].weight, layer.att[0].weight]
+            prms += [self.model.prep.fc.weight] if l == 0 and self.emb else []
+        self._install_reduce([srcs[id(p)] for p in prms])
+
+    def _wgrad_problems(self, s):
+        """levels L-1 .. 0: fc_x, fc_neib, att.2, att.0 [, the prep's at level 0]"""
+        probs = []
+        for l in range(self.L - 1, -1, -1):
+            inp, ld, rows = self._in(l, s)
+            h, Ha, D, layer = self.h[l], self.Ha, self.din[l], self.layers[l]
+            probs += [_Wgrad(self.dc[l][:, :h], inp, ld, 0, self.rows[l], h, D, h, rows, layer.fc_x.weight),
+                      _Wgrad(self.dc[l][:, h:], self.aggc[l], ld, 0, self.rows[l], h, D, h, None, layer.fc_neib.weight),
+                      _Wgrad(self.da[l], self.hid[l], self.HA_LD, 0, self.rall[l], Ha, Ha, Ha, None, layer.att[2].weight),
+                      _Wgrad(self.dhid[l], inp, ld, 0, self.rall[l], Ha, D, Ha, rows, layer.att[0].weight)]
+        return probs + ([self._emb_wgrad_problem()] if self.emb else [])
+
+    def _wgrad_targets(self, probs):
+        """the problems go out eight to a launch and one workgroup fits per CU, so each launch's problems are sized
+        together to fill the chip once"""
+        return ops.wgrad_balance([(p.M, p.Ntot, p.K) for p in probs])
 
     # ---- stages ----------------------------------------------------------------------------------------
     def _stage_gather(self, s, with_adam=False, ids=None, hops=None, skip_rows=0):
@@ -289,12 +279,5 @@ class FusedAttnTrainStep(FusedTrainStep):
                     below.data_ptr(), self.code, below.stride(0), self.datt[l].data_ptr(), ld, self.dx[l].data_ptr(), ld,
                     R, self.dagg[l].data_ptr(), ld, self.ws[l].data_ptr(), self.dc[l - 1].data_ptr(), self.code,
                     self.dc[l - 1].stride(0), RA, D, L - l + 1, self.off_host, self.fan_host, stream), "attn_merge_bwd")
-        probs = []
-        for l in range(L - 1, -1, -1):
-            for i, ((dC, A, lda, M, ntot, K, prm, rows), slab) in enumerate(zip(self._wg_problems(l, s), self.slabs[l])):
-                probs.append((dC, A, lda, 0, M, ntot, K, ntot, slab, self.wg_target[(l, i)], rows))
-        for i in range(0, len(probs), 8):
-            if i == 0:
-                self._wgrad_ticks()
-            ops.wgrad_multi(probs[i:i + 8])
+        self._stage_wgrad(s)
         self._stage_finalize(s)

@@ -7,8 +7,12 @@ the ONE gradient all-reduce, and the Adam-state hand-back to `GSSupervised.train
 
 The aggregator-specific parts (per-level operands, forward / backward launches, which rows are gathered
 ahead) live in mean.py / pool.py / attn.py: subclasses implement `why_not`, `_init_levels`, `_init_reduce`,
-`_stage_gather`, `_stage_compute` and `_backward_levels`.
+`_stage_gather`, `_stage_compute`, `_backward_levels`, and for the weight gradients `_wgrad_problems(s)` (the
+step's K5b problems of batch set s, `_Wgrad`s in launch order) and `_wgrad_targets(problems)` (workgroups to aim at,
+one per problem).  This module slices those problems once (`_plan_wgrad`) and issues them against that plan
+(`_stage_wgrad`).
 """
+import collections
 import ctypes
 import os
 
@@ -33,6 +37,11 @@ class _PrepDesc(ctypes.Structure):           # mirrors gsage_prep_desc (include/
                 ("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("dst_ld", ctypes.c_int32),
                 ("dst_t_ld", ctypes.c_int32), ("dst_p", ctypes.c_void_p), ("kc_p", ctypes.c_int64),
                 ("dst_f32", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# one K5b problem dW = dC^T A (the arguments of ops.wgrad_multi but the slab and the target) + the Parameter
+# whose gradient its slab is summed into
+_Wgrad = collections.namedtuple("_Wgrad", "dC A lda a_gstride M Ntot K n_per_group rows param")
 
 
 def _r8(v):
@@ -359,9 +368,12 @@ class FusedTrainStep(object):
                 self.tg_all = torch.zeros(self.world * self.B, dtype=torch.float32, device=self.dev)
 
     def _install_reduce(self, rdesc):
-        """Append the head's gradient source, check that every parameter is covered, upload."""
+        """Append the prep bias's and the head's gradient sources, check that every parameter is covered, upload."""
         model, dev = self.model, self.dev
         f32 = torch.float32
+        if self.emb:                                      # prep.fc.bias: column sums of the level-0 input gradient
+            E, ib = self.E, self.pidx[id(model.prep.fc.bias)]
+            rdesc.append(_ReduceDesc(self.prep_bpart.data_ptr(), E, self.poff[ib], self.prep_bpart.shape[0], 1, E, E))
         Cc, D2c = model.fc.weight.shape
         ifc = self.pidx[id(model.fc.weight)]
         assert self.pidx[id(model.fc.bias)] == ifc + 1
@@ -388,6 +400,8 @@ class FusedTrainStep(object):
         self.n_partial = nat.lib().gsage_finalize_partials(self.n_rdesc, self.r_max)
         self.partial = torch.zeros(max(self.n_partial, self.partial.numel()), dtype=f32, device=dev)
         self.refresh_weights()
+        if self.emb:
+            self._init_emb_optimizer()
 
     def _debug_addresses(self):
         """GSAGE_DEBUG_ADDR=1: the address range of every device buffer the engine's kernels are handed, on stderr
@@ -760,6 +774,35 @@ class FusedTrainStep(object):
                 self.batch_idx.data_ptr() if self.queue else None, 1), "wgrad_ticks_next")
             self._ticks_issued = True
 
+    # ---- K5b: every weight gradient of the step, planned once, issued eight problems to a launch ----------------
+    def _plan_wgrad(self):
+        """Slice every K5b problem (the launch order and the targets fix the fp32 summation order of every weight
+        gradient), allocate its slab of partial tiles; returns {id(parameter): finalisation descriptor of its slab}."""
+        probs = self._wgrad_problems(0)
+        self._wgrad_plan, srcs = [], {}
+        for p, target in zip(probs, self._wgrad_targets(probs)):
+            _rps, S, ldk = ops.wgrad_plan(p.M, p.Ntot, p.K, target)
+            slab = torch.zeros(S, p.Ntot, ldk, dtype=torch.float32, device=self.dev)
+            self._wgrad_plan.append(((p.M, p.Ntot, p.K, p.n_per_group, id(p.param)), slab, target))
+            srcs[id(p.param)] = _ReduceDesc(slab.data_ptr(), p.Ntot * ldk, self.poff[self.pidx[id(p.param)]], S,
+                                            p.Ntot, p.K, ldk)
+        return srcs
+
+    def _stage_wgrad(self, s):
+        """The K5b launches of batch set s: its problems against the plan, eight to a launch; the step's ticks (no
+        finalisation launch) and the timing marks of an engine that names "k5b" in TIMED go with the first."""
+        probs = self._wgrad_problems(s)
+        assert len(probs) == len(self._wgrad_plan)
+        args = []
+        for p, (planned, slab, target) in zip(probs, self._wgrad_plan):
+            assert (p.M, p.Ntot, p.K, p.n_per_group, id(p.param)) == planned, "K5b problem differs from its plan"
+            args.append((p.dC, p.A, p.lda, p.a_gstride, p.M, p.Ntot, p.K, p.n_per_group, slab, target, p.rows))
+        self._wgrad_ticks()
+        if "k5b" in self.TIMED:
+            self._time_next(*self.TIMED["k5b"])
+        for i in range(0, len(args), 8):
+            ops.wgrad_multi(args[i:i + 8])
+
     def _head_live_rows(self):
         """tell the next head launch how many seeds of the batch are live (padded chunks, see _pad_batch)"""
         if os.environ.get("GSAGE_NO_NVALID", "0") == "1":      # (measurement: the head without the live-row word)
@@ -813,9 +856,6 @@ class FusedTrainStep(object):
 
     def _tail_on_mfma(self):
         return False
-
-    def _wg_target(self):
-        return 240
 
     def _tail_gather_rows(self):
         return 0
@@ -974,7 +1014,7 @@ class FusedTrainStep(object):
     # are copied beside the prep's output each step, and only columns [D0, D0 + E) of the level-0 input gradient
     # are formed (the features take none).  Shared by the mean and the
     # attention engines; a subclass calls _init_emb() from _init_levels, adds _emb_wgrad_problem() to its K5b
-    # problems of level 0, forms the level-0 input gradient (din0f / din0) and hands over to _prep_backward().
+    # problems, forms the level-0 input gradient (din0f / din0) and hands over to _prep_backward().
     # =================================================================================================
     def _init_emb(self, copies):
         """copies(parameter, need_transposed) -> (operand copy, transposed copy): the subclass's operand-copy factory
@@ -1002,18 +1042,13 @@ class FusedTrainStep(object):
                             nat.lib().gsage_prep_rows_ok(self.code, E))
 
     def _emb_wgrad_problem(self):
-        """(dC, A, lda, M, Ntot, K, parameter, row list) of the prep's affine: d out^T x embedding rows"""
+        """K5b problem of the prep's affine: d out^T x embedding rows"""
         E = self.E
-        return (self.din0, self.eraw, self.eraw.stride(0), self.off[self.L + 1], E, E, self.model.prep.fc.weight, None)
-
-    def _emb_reduce_desc(self):
-        """finalisation source of prep.fc.bias (column sums of the level-0 input gradient)"""
-        E = self.E
-        ib = self.pidx[id(self.model.prep.fc.bias)]
-        return _ReduceDesc(self.prep_bpart.data_ptr(), E, self.poff[ib], self.prep_bpart.shape[0], 1, E, E)
+        return _Wgrad(self.din0, self.eraw, self.eraw.stride(0), 0, self.off[self.L + 1], E, E, E, None,
+                      self.model.prep.fc.weight)
 
     def _init_emb_optimizer(self):
-        """after _install_reduce: the table's gradient comes from scatter-adds, its squared norm from a pass of its
+        """(end of _install_reduce) the table's gradient comes from scatter-adds, its squared norm from a pass of its
         own whose partials sit behind the finalisation's in the same array; deferred row updates (gsage_rows_*)."""
         dev, f32 = self.dev, torch.float32
         self.n_tab = int(self.table.numel())

@@ -10,7 +10,7 @@ import torch
 from .. import _native as nat
 from .. import ops
 from ..nn_modules import IdentityPrep, MeanAggregator
-from .common import FusedTrainStep, _PrepDesc, _ReduceDesc, _r8
+from .common import FusedTrainStep, _PrepDesc, _Wgrad, _r8
 
 
 class FusedMeanTrainStep(FusedTrainStep):
@@ -156,54 +156,43 @@ class FusedMeanTrainStep(FusedTrainStep):
 
 
     def _init_reduce(self):
-        """Gradient partial buffers + the descriptor table gsage_finalize_grads sums them with."""
-        model, dev, L = self.model, self.dev, self.L
-        f32 = torch.float32
-        rdesc, self.slabs = [], []
-        # K5b workgroups per problem.  Two layers: every problem aims at the chip (196 + 16 workgroups at Reddit's
-        # shapes).  Deeper models would ask for more workgroups than there are CUs (one fits per CU: config 5's three
-        # levels 240 + 128 + 8) and run in rounds: those are sized together (ops.wgrad_balance), in issue order.
-        def parts_of(l):
-            return [(2 * self.h[l], 0)] if self.h[l] % 128 == 0 else [(self.h[l], 0), (self.h[l], 1)]
-        order = [("prep", 0)] if self.emb else []
-        order += [(l, g) for l in range(L - 1, -1, -1) for _nt, g in parts_of(l)]
-        def shape_of(key):
-            if key[0] == "prep":
-                _dC, _A, _lda, M_, ntot, K, _prm, _rows = self._emb_wgrad_problem()
-                return (M_, ntot, K)
-            return (self.rows[key[0]], parts_of(key[0])[0][0], self.din[key[0]])
-        shapes = [shape_of(k) for k in order]
-        plain = [self._wg_target()] * len(order)
-        def n_wg(targets):
-            return sum((ops.wgrad_plan(m, nt, k, t)[1]) * ((nt + 127) // 128) * ((k + 127) // 128)
-                       for (m, nt, k), t in zip(shapes, targets))
-        cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-        balanced = n_wg(plain) > cus
-        self.wg_target = dict(zip(order, ops.wgrad_balance(shapes, budget=cus - 8) if balanced else plain))
-        for l in range(L):
-            h, din, R = self.h[l], self.din[l], self.rows[l]
-            ix = self.pidx[id(self.layers[l].fc_x.weight)]
-            parts = parts_of(l)
-            bufs = []
-            for ntot, g in parts:
-                rps, S, ldk = ops.wgrad_plan(R, ntot, din, self.wg_target[(l, g)])
-                buf = torch.zeros(S, ntot, ldk, dtype=f32, device=dev)
-                bufs.append(buf)
-                rdesc.append(_ReduceDesc(buf.data_ptr(), ntot * ldk, self.poff[ix + g], S, ntot, din, ldk))
-            self.slabs.append(bufs)
-        if self.emb:                                  # prep.fc: weight through K5b, bias through column sums
-            dC, A, lda, M_, ntot, K, prm, _rows = self._emb_wgrad_problem()
-            rps, S, ldk = ops.wgrad_plan(M_, ntot, K, self.wg_target[("prep", 0)])
-            self.slab_prep = torch.zeros(S, ntot, ldk, dtype=f32, device=dev)
-            rdesc.append(_ReduceDesc(self.slab_prep.data_ptr(), ntot * ldk, self.poff[self.pidx[id(prm)]], S, ntot, K, ldk))
-            rdesc.append(self._emb_reduce_desc())
-        self._install_reduce(rdesc)
-        if self.emb:
-            self._init_emb_optimizer()
+        """Gradient partial buffers + the descriptor table gsage_finalize_grads sums them with: levels 0 .. L-1
+        (fc_x's slab, covering fc_neib too where the level is one grouped problem, else fc_x's and fc_neib's),
+        then the prep's."""
+        srcs = self._plan_wgrad()
+        prms = [p for layer in self.layers for p in (layer.fc_x.weight, layer.fc_neib.weight)]
+        prms += [self.model.prep.fc.weight] if self.emb else []
+        self._install_reduce([srcs[id(p)] for p in prms if id(p) in srcs])
 
-    def _wg_target(self):
-        """K5b workgroups to plan for: the chip (one workgroup fits per CU)"""
-        return int(os.environ.get("GSAGE_WGRAD_TARGET", "240"))
+    def _wgrad_problems(self, s):
+        """[the prep's], then levels L-1 .. 0: ONE grouped problem (x | agg, a_gstride apart: both weights) where h is
+        a multiple of 128, else fc_x and fc_neib apart"""
+        probs = [self._emb_wgrad_problem()] if self.emb else []
+        for l in range(self.L - 1, -1, -1):
+            R, h, din, dc, layer = self.rows[l], self.h[l], self.din[l], self.dc[l], self.layers[l]
+            xbuf, lda = (self.xa0_set[s][0], self.ldin[0]) if l == 0 else (self.hout[l - 1], din)
+            rows = None
+            if l == 0 and self.inplace_x:
+                xbuf, rows = self.store.data, (self._q_ids if self._q_ids is not None else self.ids_set[s])
+            aggl = self.xa0_set[s][1] if l == 0 else self.agg[l]
+            if h % 128 == 0:
+                delta = (aggl.data_ptr() - xbuf.data_ptr()) // self.esz
+                probs.append(_Wgrad(dc, xbuf, lda, delta, R, 2 * h, din, h, rows, layer.fc_x.weight))
+            else:
+                probs += [_Wgrad(dc, xbuf, lda, 0, R, h, din, h, rows, layer.fc_x.weight),
+                          _Wgrad(dc[:, h:], aggl, lda, 0, R, h, din, h, None, layer.fc_neib.weight)]
+        return probs
+
+    def _wgrad_targets(self, probs):
+        """Two layers: every problem aims at the chip (196 + 16 workgroups at Reddit's shapes; one fits per CU).
+        Deeper models would ask for more workgroups than there are CUs (config 5's three levels 240 + 128 + 8) and run
+        in rounds: those are sized together (ops.wgrad_balance), in issue order."""
+        shapes = [(p.M, p.Ntot, p.K) for p in probs]
+        plain = [int(os.environ.get("GSAGE_WGRAD_TARGET", "240"))] * len(shapes)
+        n_wg = sum(ops.wgrad_plan(m, nt, k, t)[1] * ((nt + 127) // 128) * ((k + 127) // 128)
+                   for (m, nt, k), t in zip(shapes, plain))
+        cus = int(torch.cuda.get_device_properties(self.dev).multi_processor_count)
+        return ops.wgrad_balance(shapes, budget=cus - 8) if n_wg > cus else plain
 
     def _stage_gather(self, s, with_adam=False, ids=None, hops=None, skip_rows=0, part=None, adam=None, stop_rows=None):
         """Level-0 gathers of batch set s (x rows of every hop + each hop's neighbour means), one
@@ -314,7 +303,7 @@ class FusedMeanTrainStep(FusedTrainStep):
         self._backward_levels(s)
 
     def _backward_levels(self, s):
-        L, st, lib = self.L, self.store, nat.lib()
+        L, lib = self.L, nat.lib()
         stream = ops._stream()
         esz = self.esz
         # (1) the chain of input gradients down the levels: dC[l] -> (dX | dAgg) -> mask/route -> dC[l-1]
@@ -352,30 +341,7 @@ class FusedMeanTrainStep(FusedTrainStep):
                     self.din0.data_ptr() if lp else None, self.din0.stride(0) if lp else 0, stream), "merge_bwd (level 0)")
                 self._prep_backward(s)
         # (2) every level's weight gradient in ONE launch: each alone fills a fraction of the chip
-        probs = []
-        if self.emb:
-            dC, A, lda, M_, ntot, K, _prm, _rows = self._emb_wgrad_problem()
-            probs.append((dC, A, lda, 0, M_, ntot, K, ntot, self.slab_prep, self.wg_target[("prep", 0)], None))
-        for l in range(L - 1, -1, -1):
-            R, h, din = self.rows[l], self.h[l], self.din[l]
-            dc = self.dc[l]
-            xbuf, lda = (self.xa0_set[s][0], self.ldin[0]) if l == 0 else (self.hout[l - 1], din)
-            rows = None
-            if l == 0 and self.inplace_x:
-                xbuf, rows = st.data, (self._q_ids if self._q_ids is not None else self.ids_set[s])
-            aggl = self.xa0_set[s][1] if l == 0 else self.agg[l]
-            delta = (aggl.data_ptr() - xbuf.data_ptr()) // esz
-            if h % 128 == 0:
-                probs.append((dc, xbuf, lda, delta, R, 2 * h, din, h, self.slabs[l][0], self.wg_target[(l, 0)], rows))
-            else:
-                for g in range(2):
-                    probs.append((dc[:, g * h:], xbuf if g == 0 else aggl, lda, 0, R, h, din, h,
-                                  self.slabs[l][g], self.wg_target[(l, g)], rows if g == 0 else None))
-        for i in range(0, len(probs), 8):
-            if i == 0:
-                self._wgrad_ticks()
-                self._time_next(6, 7)
-            ops.wgrad_multi(probs[i:i + 8])
+        self._stage_wgrad(s)
         self._stage_finalize(s)
 
     def gather_launch_rows(self):

@@ -9,7 +9,7 @@ import torch
 from .. import _native as nat
 from .. import ops
 from ..nn_modules import IdentityPrep, MaxPoolAggregator, MeanPoolAggregator, NodeEmbeddingPrep
-from .common import FusedTrainStep, _PrepDesc, _ReduceDesc, _r8, _r64
+from .common import FusedTrainStep, _PrepDesc, _ReduceDesc, _Wgrad, _r8, _r64
 
 
 class FusedPoolTrainStep(FusedTrainStep):
@@ -168,49 +168,49 @@ class FusedPoolTrainStep(FusedTrainStep):
             return self.xn0_set[s], self.store.ld, None
         return self.hout[l - 1][self.off[1]:], self.din[l], None
 
-    def _wg_shapes(self, l):
-        """(key, parameter, M, Ntot, K) of level l's three weight gradients, in the order they are issued"""
-        layer = self.layers[l]
-        R, NR, Hm, h, din = self.rows[l], self.nrows[l], self.Hm[l], self.h[l], self.din[l]
-        return (("x", layer.fc_x.weight, R, h, din), ("n", layer.fc_neib.weight, R, h, Hm),
-                ("m", layer.mlp[0].weight, NR, Hm, din))
-
     def _init_reduce(self):
-        dev, L, f32 = self.dev, self.L, torch.float32
-        # K5b workgroups per problem: the MLP's weight gradients get the chip's worth of slices each (the small one's
-        # many short workgroups fill the tail of the big one's), the two projections few, long ones (fewer partial
-        # tiles to write and to sum).  Sizing all six for ONE round of equal-length slices (ops.wgrad_balance: 232
-        # workgroups, the big problem on 200) measured SLOWER here -- 180 against 150 us: the launch is bound by what
-        # its 240 big workgroups pull from HBM (785 MB per launch), and fewer, longer slices only stretch that.
-        self.wg_target = {(l, key): {"m": 240, "x": 40, "n": 40}[key] for l in range(L) for key in "mxn"}
-        for l in range(L):
-            # two output tiles per workgroup (gsage_wgrad_pair_ok): slices half as long keep the workgroup count
-            for key, _prm, M, ntot, K in self._wg_shapes(l):
-                t = self.wg_target[(l, key)]
-                if nat.lib().gsage_wgrad_pair_ok(self.code, M, ntot, ntot, ops.wgrad_plan(M, ntot, K, 2 * t)[0]):
-                    self.wg_target[(l, key)] = 2 * t
-        rdesc, self.slabs = [], []
+        """finalisation table: per level l = 0 .. L-1 the slabs of mlp, fc_x, fc_neib and the MLP bias partials, then
+        the prep's slab"""
+        srcs, rdesc = self._plan_wgrad(), []
         for l, layer in enumerate(self.layers):
-            Hm = self.Hm[l]
-            bufs = {}
-            for key, prm, M, ntot, K in sorted(self._wg_shapes(l), key=lambda spec: "mxn".index(spec[0])):
-                rps, S, ldk = ops.wgrad_plan(M, ntot, K, self.wg_target[(l, key)])
-                buf = torch.zeros(S, ntot, ldk, dtype=f32, device=dev)
-                bufs[key] = buf
-                rdesc.append(_ReduceDesc(buf.data_ptr(), ntot * ldk, self.poff[self.pidx[id(prm)]], S, ntot, K, ldk))
-            ib = self.pidx[id(layer.mlp[0].bias)]
+            Hm, ib = self.Hm[l], self.pidx[id(layer.mlp[0].bias)]
+            rdesc += [srcs[id(p)] for p in (layer.mlp[0].weight, layer.fc_x.weight, layer.fc_neib.weight)]
             rdesc.append(_ReduceDesc(self.bpart[l].data_ptr(), Hm, self.poff[ib], self.bpart[l].shape[0], 1, Hm, Hm))
-            self.slabs.append(bufs)
-        if self.emb:                                  # prep.fc: weight through K5b, bias through column sums
-            dC, A, lda, M_, ntot, K, prm, _rows = self._emb_wgrad_problem()
-            self.wg_target[("prep", 0)] = 40
-            rps, S, ldk = ops.wgrad_plan(M_, ntot, K, 40)
-            self.slab_prep = torch.zeros(S, ntot, ldk, dtype=f32, device=dev)
-            rdesc.append(_ReduceDesc(self.slab_prep.data_ptr(), ntot * ldk, self.poff[self.pidx[id(prm)]], S, ntot, K, ldk))
-            rdesc.append(self._emb_reduce_desc())
-        self._install_reduce(rdesc)
         if self.emb:
-            self._init_emb_optimizer()
+            rdesc.append(srcs[id(self.model.prep.fc.weight)])
+        self._install_reduce(rdesc)
+
+    def _wgrad_problems(self, s):
+        """[the prep's], then levels L-1 .. 0: fc_x, fc_neib, the pooling MLP"""
+        probs = [self._emb_wgrad_problem()] if self.emb else []
+        for l in range(self.L - 1, -1, -1):
+            R, NR, Hm, h, din, layer = self.rows[l], self.nrows[l], self.Hm[l], self.h[l], self.din[l], self.layers[l]
+            x, ldx = self._x_operand(l, s)
+            nb, ldnb, nrows = self._nb_operand(l, s)
+            dc, pb = self.dc[l], self.pooled_b[l]
+            probs += [_Wgrad(dc[:, :h], x, ldx, 0, R, h, din, h, None, layer.fc_x.weight),
+                      _Wgrad(dc[:, h:], pb, pb.shape[1], 0, R, h, Hm, h, None, layer.fc_neib.weight),
+                      _Wgrad(self.ghc[l], nb, ldnb, 0, NR, Hm, din, Hm, nrows, layer.mlp[0].weight)]
+        return probs
+
+    def _wgrad_targets(self, probs):
+        """The MLP's weight gradients get the chip's worth of slices each (the small one's many short workgroups fill
+        the tail of the big one's), the two projections and the prep few, long ones (fewer partial tiles to write and
+        to sum).  Sizing all six for ONE round of equal-length slices (ops.wgrad_balance: 232 workgroups, the big
+        problem on 200) measured SLOWER here -- 180 against 150 us: the launch is bound by what its 240 big workgroups
+        pull from HBM (785 MB per launch), and fewer, longer slices only stretch that.  With two output tiles per
+        workgroup (gsage_wgrad_pair_ok) the levels' problems get twice the target: slices half as long keep the
+        workgroup count."""
+        mlp = {id(layer.mlp[0].weight) for layer in self.layers}
+        prep = self.model.prep.fc.weight if self.emb else None
+        targets = []
+        for p in probs:
+            t = 240 if id(p.param) in mlp else 40
+            if p.param is not prep and nat.lib().gsage_wgrad_pair_ok(self.code, p.M, p.Ntot, p.Ntot,
+                                                                     ops.wgrad_plan(p.M, p.Ntot, p.K, 2 * t)[0]):
+                t *= 2
+            targets.append(t)
+        return targets
 
     # ---- stages ----------------------------------------------------------------------------------------
     def _stage_gather(self, s, with_adam=False, ids=None, hops=None, skip_rows=0):
@@ -330,23 +330,5 @@ class FusedPoolTrainStep(FusedTrainStep):
                         None, self.din0f.data_ptr(), nat.F32, E, RA0, E, L + 1, self.off_host, self.fan_host,
                         self.din0.data_ptr() if lp else None, self.din0.stride(0) if lp else 0, stream), "merge_bwd (level 0)")
                     self._prep_backward(s)
-        probs = []
-        if self.emb:
-            dC, A, lda, M_, ntot, K, _prm, _rows = self._emb_wgrad_problem()
-            probs.append((dC, A, lda, 0, M_, ntot, K, ntot, self.slab_prep, self.wg_target[("prep", 0)], None))
-        for l in range(L - 1, -1, -1):
-            R, NR, Hm, h, din = self.rows[l], self.nrows[l], self.Hm[l], self.h[l], self.din[l]
-            x, ldx = self._x_operand(l, s)
-            nb, ldnb, nrows = self._nb_operand(l, s)
-            dc = self.dc[l]
-            T = self.wg_target
-            probs.append((dc[:, :h], x, ldx, 0, R, h, din, h, self.slabs[l]["x"], T[(l, "x")]))
-            probs.append((dc[:, h:], self.pooled_b[l], self.pooled_b[l].shape[1], 0, R, h, Hm, h, self.slabs[l]["n"],
-                          T[(l, "n")]))
-            probs.append((self.ghc[l], nb, ldnb, 0, NR, Hm, din, Hm, self.slabs[l]["m"], T[(l, "m")], nrows))
-        for i in range(0, len(probs), 8):
-            if i == 0:
-                self._wgrad_ticks()
-                self._time_next(6, 7)
-            ops.wgrad_multi(probs[i:i + 8])
+        self._stage_wgrad(s)
         self._stage_finalize(s)
