@@ -111,11 +111,20 @@ class FusedAttnTrainStep(FusedTrainStep):
             self.da.append(z(RA, HL, dt=T)); self.dhid.append(z(RA, HL, dt=T))
             ing = l > 0 or self.emb
             self.datt.append(z(RA, ld) if ing else None); self.dx.append(z(R, ld) if ing else None)
+        # levels whose rows are too wide for the grouped K4 kernels: K4 writes the aggregate in fp32 there, and the
+        # operand copy aggc is cast from it (gsage_attn_aggregate_lp); other levels write aggc directly (None)
+        self.agg32 = [z(self.rows[l], self.ldin[l]) if self._k4_wide(self.din[l]) else None for l in range(L)]
         # the LAST hop of a level (most of its rows) through K4 / K4' with the attention MLP inside
         # (csrc/gsage_attn_fused.hip: the rows are read once per direction); GSAGE_ATTN_FUSED=0: the separate launches
         on = os.environ.get("GSAGE_ATTN_FUSED", "1") != "0"
         self.fuse = [bool(on and nat.lib().gsage_attn_fused_ok(self.code, self.ldin[l], self.din[l], self.fan[L - l], Ha))
                      for l in range(L)]
+
+    def _k4_wide(self, D):
+        """rows of D columns take K4's wide kernels, which write fp32 only: csrc/gsage_attn.hip attn_group_lanes, more
+        than 32 * ATTN_TMAX = 96 chunks of 16 bytes (8 bf16 or 4 fp32 columns) per row"""
+        vec = 8 if self.code == nat.BF16 else 4
+        return -(-D // vec) > 32 * 3
 
     def _in(self, l, s):
         """input rows of level l (all hops it reads): (row block, leading dimension, row list or None) -- with a
@@ -210,9 +219,10 @@ class FusedAttnTrainStep(FusedTrainStep):
                         self.hid[l][c0:].data_ptr(), HL, self.a[l][c0:].data_ptr(), Ha,
                         self.ws[l][c0 - self.off[1]:].data_ptr(), self.aggc[l][r0:].data_ptr(), ld, stream), "attn_fused_fwd")
                     continue
+                agg32 = self.agg32[l][r0:].data_ptr() if self.agg32[l] is not None else None
                 nat.check(lib.gsage_attn_aggregate_lp(
                     self.a[l][c0:].data_ptr(), Ha, self.a[l][r0:].data_ptr(), Ha, tab, self.code, ld,
-                    idp, self.size[k], self.fan[k + 1], Ha, D, None, ld,
+                    idp, self.size[k], self.fan[k + 1], Ha, D, agg32, ld,
                     self.ws[l][c0 - self.off[1]:].data_ptr(), self.aggc[l][r0:].data_ptr(), ld, stream), "attn_aggregate")
             last = l == L - 1
             out, code = self.hout[l], (nat.F32 if last else self.code)

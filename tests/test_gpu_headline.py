@@ -5,24 +5,12 @@ N = 232 965, D = 602 (rows padded to 640), B = 512, fan-out 25/10, hidden 128 --
 gather roles, Adam riding in the gather launch), bf16 storage against the rounding-aware oracle and fp32 storage
 against the plain fp32 oracle.  The oracle runs on the frontier's rows relabelled to a compact table (the technique
 of test_gpu_large.py): two consecutive train steps, predictions / gradient norm / weights after each."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import pkg
-from util import close, close_fro, close_update
-
-_LOG = os.environ.get("GSAGE_PARITY_LOG")
-
-
-def _note(key, **vals):
-    """measured errors -> profiles/rNN_parity_errors.jsonl (tools/gpu_round.sh sets GSAGE_PARITY_LOG)"""
-    if _LOG:
-        with open(_LOG, "a") as f:
-            f.write(json.dumps(dict(key=key, **{k: float(v) for k, v in vals.items()})) + "\n")
+from util import close, close_fro, close_update, note_parity as _note, oracle_train_step, philox_frontier
 
 pytestmark = pytest.mark.gpu
 gs = pkg()
@@ -53,18 +41,20 @@ def _setup():
 # run).  Measured (profiles/r06_parity_errors.jsonl, headline/*/update): mean 3.2e-3, max pool 3.9e-2, attention 6.3e-2
 # -- the bounds are 1.3 - 2 x those (round-5 review: "2 x the measured error"; max pool's 5e-2 already sits below that).
 UPDATE_BOUND = {"mean": 5e-3, "max_pool": 5e-2, "attention": 0.13}
+# fp32 max pool and attention: after one Adam step at this size the weights already differ by whole-lr moves (about a
+# dozen argmax flips over 128 000 segments move whole rows of the pooling MLP; attention-MLP gradients that are sums
+# of cancelling terms flip sign), so step 2's gradients differ in every tensor -- measured 4.6e-3 (mlp.0), 7.8e-3
+# (att.0), 7.0e-3 (fc_neib) in norm, with up to 2 % of the entries past close_update's 1e-4.  Their updates are bounded
+# in norm; fp32 mean keeps close_update
+FP32_NORM_BOUND = {"max_pool": 1e-2, "attention": 1e-2}
 
 
-def _frontier(csr, seeds, batch, L=2):
-    """the queue pipeline's frontier of batch `batch`: hop k is Philox call batch * L + k of the sampler's seed"""
-    cur, hops = seeds, []
-    for k, f in enumerate(FAN):
-        cur = ops.sample_csr(csr, cur, f, philox={"seed": SEED, "call_base": batch * L + k})
-        hops.append(cur)
-    return hops
+def _frontier(csr, seeds, batch):
+    return philox_frontier(ops, csr, seeds, FAN, SEED, batch)
 
 
-@pytest.mark.parametrize("agg,prec", [("mean", "bf16"), ("mean", "fp32"), ("max_pool", "bf16"), ("attention", "bf16")])
+@pytest.mark.parametrize("agg,prec", [("mean", "bf16"), ("mean", "fp32"), ("max_pool", "bf16"), ("max_pool", "fp32"),
+                                      ("attention", "bf16"), ("attention", "fp32")])
 def test_bench_workload_steps_equal_the_oracle(reddit, agg, prec):
     import bench
     from oracle import torch_ref as tref
@@ -84,8 +74,10 @@ def test_bench_workload_steps_equal_the_oracle(reddit, agg, prec):
     eng = gs.engine.fused_engine_for(model, store)(model, store, gs.ProblemLosses.classification, ids[0], tg[0],
                                                    capture="cmdlist")
     assert eng.capture_mode == "cmdlist" and eng.fused_head
-    if agg == "attention":
+    if agg == "attention" and prec == "bf16":
         assert eng.fuse[0] and not eng.fuse[1]            # the last hop (fan-out 10) through K4 / K4' with the MLP inside
+    if agg == "attention" and prec == "fp32":
+        assert not any(eng.fuse)                          # (the fused K4 is bf16 only; level 0: 151 chunks, the wide K4)
     if agg == "mean":
         assert eng.fused_tail and eng.B == B and eng.fan[1:] == [25, 10]        # the seed-level kernel (k_mean_tail_mfma<25, 10> at B = 512, bf16)
     eng.load_epoch(ids, tg)
@@ -112,11 +104,8 @@ def test_bench_workload_steps_equal_the_oracle(reddit, agg, prec):
     bf = prec == "bf16"
     for s in range(n_steps):
         hops = [h.cpu().numpy() for h in _frontier(csr, ids[s], s)]
-        uniq, inv = np.unique(np.concatenate([ids[s].cpu().numpy()] + hops), return_inverse=True)
-        small = store.data[torch.from_numpy(uniq).to(dev), :store.dim].float().cpu()
-        parts = np.split(inv, np.cumsum([B, hops[0].shape[0]]))
-        r = tref.train_step(w, opt, 0.01, "classification", parts[0], small, tg[s].cpu(), None, None, FAN, None, agg,
-                            "identity", 232966, rounding="bf16" if bf else None, frontier=parts[1:])
+        r = oracle_train_step(tref, w, opt, store, ids[s].cpu().numpy(), tg[s].cpu(), hops, FAN, agg,
+                              "bf16" if bf else None)
         _note("headline/%s/%s/step%d" % (agg, prec, s), preds=np.abs(preds[s] - r["preds"].numpy()).max(),
               gnorm_rel=abs(norms[s] - r["gradnorm"]) / max(1.0, r["gradnorm"]))
         close(preds[s], r["preds"].numpy(), "preds vs oracle, step %d (%s %s)" % (s, agg, prec), *(((1e-3, 1e-3) if agg == "mean" else (3e-3, 3e-3)) if bf else (2e-4, 2e-4)))
@@ -124,11 +113,11 @@ def test_bench_workload_steps_equal_the_oracle(reddit, agg, prec):
             (s, norms[s], r["gradnorm"])
     worst = 0.0
     for k, v in model.named_parameters():
-        if bf:
+        if bf or agg in FP32_NORM_BOUND:
             got, want = v.detach().cpu().numpy() - w0[k].numpy(), w[k].numpy() - w0[k].numpy()
             worst = max(worst, float(np.linalg.norm(got - want)) / max(float(np.linalg.norm(want)), 1e-12))
-            close_fro(got, want, ("Adam updates", k), UPDATE_BOUND[agg])
+            close_fro(got, want, ("Adam updates", k), UPDATE_BOUND[agg] if bf else FP32_NORM_BOUND[agg])
         else:
             close_update(v.detach().cpu().numpy(), w[k].numpy(), w0[k].numpy(), ("weights after 2 steps", k))
-    if bf:
+    if bf or agg in FP32_NORM_BOUND:
         _note("headline/%s/%s/update" % (agg, prec), upd_fro=worst)

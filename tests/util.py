@@ -1,4 +1,7 @@
 """Shared helpers for the product tests."""
+import json
+import os
+
 import numpy as np
 import torch
 from scipy import sparse
@@ -60,6 +63,45 @@ def close_fro(a, b, what, tol):
     assert a.shape == b.shape, (what, a.shape, b.shape)
     err = float(np.linalg.norm(a - b)) / max(float(np.linalg.norm(b)), 1e-12)
     assert err <= tol, (what, "relative Frobenius error %g" % err)
+
+
+def note_parity(key, **vals):
+    """measured errors -> one JSON line of the file GSAGE_PARITY_LOG names (profiles/*parity*.jsonl); no-op without it"""
+    path = os.environ.get("GSAGE_PARITY_LOG")
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps(dict(key=key, **{k: float(v) for k, v in vals.items()})) + "\n")
+
+
+def philox_frontier(ops, csr, seeds, fans, seed, batch):
+    """the frontier a fused engine draws for its `batch`-th batch with the Philox sampler: hop k of an L-hop frontier is
+    Philox call batch * L + k of the sampler's seed (queue pipeline, per-call mode and evaluation alike)"""
+    cur, hops, L = seeds, [], len(fans)
+    for k, f in enumerate(fans):
+        cur = ops.sample_csr(csr, cur, f, philox={"seed": seed, "call_base": batch * L + k})
+        hops.append(cur)
+    return hops
+
+
+def compact_rows(store, ids, hops, dtype=torch.float32):
+    """the frontier's rows relabelled to a compact table: (rows [U, D] as `dtype` on the CPU, seed positions, hop
+    positions) -- what oracle.torch_ref takes as (feats, ids, frontier) without a graph"""
+    ids = np.asarray(ids)
+    hops = [np.asarray(h) for h in hops]
+    uniq, inv = np.unique(np.concatenate([ids] + hops), return_inverse=True)
+    rows = store.data[torch.from_numpy(uniq).to(store.data.device), :store.dim].cpu().to(dtype)
+    parts = np.split(inv, np.cumsum([ids.shape[0]] + [h.shape[0] for h in hops[:-1]]))
+    return rows, parts[0], parts[1:]
+
+
+def oracle_train_step(tref, w, opt, store, ids, targets, hops, fans, agg, rounding, dtype=torch.float32, edit=None):
+    """oracle.torch_ref.train_step on the frontier's rows relabelled to a compact table, in `dtype` (`w` and `opt`'s
+    state must be of that dtype too).  edit(rows) -> rows: a change to the oracle's input only."""
+    rows, seeds, frontier = compact_rows(store, ids, hops, dtype)
+    if edit is not None:
+        rows = edit(rows)
+    return tref.train_step(w, opt, 0.01, "classification", seeds, rows, targets, None, None, fans, None, agg,
+                           "identity", int(store.data.shape[0]), rounding=rounding, frontier=frontier)
 
 
 class SelReplay(object):
