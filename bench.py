@@ -2,7 +2,7 @@
 """
 bench.py -- seed-nodes/sec of the GraphSAGE training hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]            # N=1: plain python
+    python bench.py [--gpus N --steps K --warmup W] [--full]   # N=1: plain python
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one `train_step` (reference models.py:97-104) over one batch of 512 seed nodes per
@@ -27,7 +27,10 @@ initial weights come from fixed seeds, so two builds run with the same arguments
 output for output.  A weight of more than 4 Mi elements (the Pokec shape's embedding table) is dumped
 as a fixed, seeded sample of its rows; the whole dump stays below 64 MB.
 
-Extra objects on the line (tier contract, section 4 of the task):
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line, with `roofline` and `cpu_baseline` null and `extra` empty.  `--full` measures
+everything else after the timed region and adds it to the line (a data-parallel run: config.exchange_in_list_us,
+the exchange timed inside the step's list, instead of the in-step roofline):
   roofline     the step's dominant launch, timed IN PLACE (engine_roofline): the command list of the queue-mode
                step is re-recorded with HIP-event marks on the dispatch of k_gather_multi_adam (the launch that
                gathers the next batch's level-0 rows, with Adam and the sampler riding along) and of the
@@ -36,6 +39,7 @@ Extra objects on the line (tier contract, section 4 of the task):
                whole-step figure (all 276 rows/seed / ms_per_step).  Every `extra` entry carries the same object
                for ITS dominant launch, timed the same way inside ITS step: K3 over the last hop (max-pool; MFMA),
                K4 over the last hop (attention, Reddit and Pokec shapes; HBM), the gather launch (papers).
+  extra        the configurations named by --extra (default: every one), each measured after the main line
   cpu_baseline two CPU restatements of train_step on the host, bounded sample each: the OpenMP C one
                (oracle/gsage_train_omp.c, OpenMP, register-blocked AVX2 / FMA products without BLAS) and the plain-torch port of the reference's
                op sequence (oracle/torch_ref.py, MKL GEMMs, fixed thread count); `value` is the faster.
@@ -490,10 +494,11 @@ def _placeholder_adj():
     return sparse.csr_matrix((np.array([1, 1]), np.array([0, 0]), np.array([0, 0, 1, 2])), shape=(3, 1))
 
 
-def extra_papers(gs, dev, steps=60, warmup=5, n_nodes=111_059_956, B=BATCH, ddp=None, keep=False):
+def extra_papers(gs, dev, steps=60, warmup=5, n_nodes=111_059_956, B=BATCH, ddp=None, keep=False, full=True):
     """BASELINE configs[4] on one GPU at its REAL size: 111 059 956 nodes, ~3.2e9 edges (int64 row offsets, 13 GB of
     int32 neighbour ids), 128-d bf16 features (28 GB), mean aggregator, three layers, fan-out 15/10/5 -- graph and
     table generated on the device (store.DeviceCSR.synthetic / FeatureStore.synthetic; ~43 GB of the 288 GB).
+    full: also time the dominant launch in place (`roofline`; data-parallel: `exchange_us`) after the timed steps.
     Parity at this size: tests/test_gpu_large.py::test_three_layer_engine_step_at_papers_scale."""
     from torch.nn import functional as F
     n_rows = n_nodes + 1
@@ -529,9 +534,9 @@ def extra_papers(gs, dev, steps=60, warmup=5, n_nodes=111_059_956, B=BATCH, ddp=
            "ms_per_step": dt * 1e3, "value": world * B / dt, "unit": "seed-nodes/sec", "engine": "FusedMeanTrainStep",
            "alg_bytes_per_seed": rows * 128 * 2,
            "frac_of_hbm_gather_roofline": (B / dt) / (HBM_PEAK_GBS * 1e9 / (rows * 128 * 2))}
-    if ddp is None:
+    if full and ddp is None:
         rec["roofline"] = engine_roofline(eng, lambda k: eng.step_queue(), "papers_gather", n_steps=32)
-    else:
+    elif full:
         rec["exchange_us"] = exchange_in_list_us(eng, lambda k: eng.step_queue())
     rec["_engine"] = eng
     if keep:
@@ -539,12 +544,12 @@ def extra_papers(gs, dev, steps=60, warmup=5, n_nodes=111_059_956, B=BATCH, ddp=
     return rec
 
 
-def extra_pokec(gs, dev, steps=40, warmup=5, B=BATCH, precision=None, engine="fused", ddp=None, keep=False):
+def extra_pokec(gs, dev, steps=40, warmup=5, B=BATCH, precision=None, engine="fused", ddp=None, keep=False, full=True):
     """BASELINE configs[3] at its SHAPE on one GPU: Pokec-sized graph (1.63 M nodes, ~6e7 edges), no features,
     trainable 64-d node embeddings (node_embedding prep), attention aggregator (hidden 32), fan-out 20/15,
     regression_mae.  The step keeps the reference's DENSE embedding-gradient semantics (every row of the 418 MB
     table moves every step; dense_table_bytes_per_step is what streaming it would cost), applied row by row when a
-    row is touched or read (engine.FusedAttnTrainStep.sync_rows)."""
+    row is touched or read (engine.FusedAttnTrainStep.sync_rows).  full: as extra_papers."""
     from torch.nn import functional as F
     if precision:
         gs.ops.set_compute_dtype(precision)
@@ -592,7 +597,7 @@ def extra_pokec(gs, dev, steps=40, warmup=5, B=BATCH, precision=None, engine="fu
            "ms_per_step": dt * 1e3, "value": world * B / dt, "unit": "seed-nodes/sec",
            "engine": how, "alg_bytes_per_seed": rows * 64 * 4, "dense_table_bytes_per_step": 7 * 4 * 64 * (N + 2),
            "frac_of_hbm_gather_roofline": (B / dt) / (HBM_PEAK_GBS * 1e9 / (rows * 64 * 4))}
-    if cls is not None and step_fn.capture_mode == "cmdlist":
+    if full and cls is not None and step_fn.capture_mode == "cmdlist":
         if ddp is None:
             rec["roofline"] = engine_roofline(step_fn, lambda k: step_fn(ids[k % total], tg[k % total]), "pokec_k4",
                                               n_steps=32)
@@ -745,8 +750,8 @@ def extra_b4096(args):
     """The headline step at B = 4 096 seeds per GPU ("512/GPU (also sweep 4096)"): the same engine, eight
     times the work per launch -- fixed launch costs amortised, the seed level 256 workgroups wide.  A child process
     (its own seed queue and engine)."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--extra", "",
-           "--min-time", "0.3", "--batch-size", "4096", "--precision", args.precision]
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline",
+           "--extra", "", "--min-time", "0.3", "--batch-size", "4096", "--precision", args.precision]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -764,7 +769,7 @@ def extra_fp32(args):
     """BASELINE configs[1] with fp32 storage and exact-fp32 arithmetic (`--precision fp32`: the reference's own number
     format, reference problem.py:119; BASELINE.md section 4's tight-parity row, roofline 8 TB/s / (276 x 602 x 4 B) =
     12.0 M seed-nodes/s): the same engine code instantiated on float.  A child process (its own feature table)."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup),
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup), "--full",
            "--no-cpu-baseline", "--extra", "", "--min-time", "0.3", "--batch-size", str(args.batch_size), "--precision", "fp32"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -805,6 +810,9 @@ def self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
+FULL_EXTRA = "max_pool,attention,papers,pokec,ddp_1rank,cli,b4096,fp32"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -840,13 +848,21 @@ def main():
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
                     help="write the predictions and weights of the last timed step as DIR/<name>.npy (needs one timed "
                          "region: --min-time 0)")
-    ap.add_argument("--extra", type=str, default="max_pool,attention,papers,pokec,ddp_1rank,cli,b4096,fp32",
-                    help="comma-separated additional configurations measured after the main line (N=1 only) and "
-                         "reported under `extra`: an aggregator name (same graph), `papers` / `pokec` (BASELINE "
-                         "configs[4] / configs[3] shapes on their own synthetic graphs); '' for none")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the in-step roofline (or the exchange "
+                         "timed in the step's list), the --extra configurations and the CPU baseline")
+    ap.add_argument("--extra", type=str, default=None,
+                    help="with --full: comma-separated additional configurations measured after the main line (N=1 "
+                         "only) and reported under `extra`: an aggregator name (same graph), `papers` / `pokec` "
+                         "(BASELINE configs[4] / configs[3] shapes on their own synthetic graphs); '' for none "
+                         "(default: %s)" % FULL_EXTRA)
     args = ap.parse_args()
     if args.dump_outputs and args.min_time > 0:
         ap.error("--dump-outputs needs exactly one timed region of K steps (--min-time 0)")
+    if args.extra is None:
+        args.extra = FULL_EXTRA if args.full else ""
+    elif args.extra and not args.full:
+        ap.error("--extra %s: the other configurations are measured with --full" % args.extra)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
 
@@ -871,7 +887,7 @@ def main():
         # BASELINE configs[3] / configs[4] as the main line (one command per configuration and GPU count)
         fn = extra_pokec if args.config == "pokec" else extra_papers
         rec = fn(gs, dev, steps=args.steps, warmup=args.warmup, B=args.batch_size, ddp=ddp,
-                 keep=bool(args.dump_outputs) and rank == 0)
+                 keep=bool(args.dump_outputs) and rank == 0, full=args.full)
         rec.pop("_engine", None)
         if rank == 0:
             if args.dump_outputs:
@@ -982,7 +998,7 @@ def main():
                 break
         outputs = snapshot_outputs(last, model, step_fn) if keep else None
         model.train_sampler.csr(dev).check()
-        xus = exchange_in_list_us(step_fn, run_step) if ddp is not None else None      # (collective steps: every rank)
+        xus = exchange_in_list_us(step_fn, run_step) if (args.full and ddp is not None) else None  # (every rank)
         med = float(np.median(times))
         return {"model": model, "step_fn": step_fn, "engine": engine, "queued": queued, "use_graph": use_graph,
                 "elapsed": med, "times": times, "launches_per_step": float(np.median(launches)), "exchange_us": xus,
@@ -996,17 +1012,19 @@ def main():
 
     if rank == 0:
         value = args.steps * B * world / elapsed
-        instrumentable = (res["queued"] and ddp is None and getattr(step_fn, "capture_mode", None) == "cmdlist")
-        if instrumentable:
-            roof = engine_roofline(step_fn, lambda k: step_fn.step_queue(),
-                                   {"mean": "reddit_gather", "max_pool": "maxpool_k3",
-                                    "attention": "attention_k4"}.get(args.aggregator, args.aggregator))
-        else:
-            roof = standalone_gather_probe(gs, model, store, data, dev, fanout, B)
-        step_alg = rows_per_seed(fanout) * FEAT_DIM * elem * B
-        roof["step"] = {"alg_bytes_per_step": step_alg, "ms_per_step": elapsed / args.steps * 1e3,
-                        "achieved": step_alg / (elapsed / args.steps) / 1e9,
-                        "frac": step_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS}
+        roof = None
+        if args.full:
+            instrumentable = (res["queued"] and ddp is None and getattr(step_fn, "capture_mode", None) == "cmdlist")
+            if instrumentable:
+                roof = engine_roofline(step_fn, lambda k: step_fn.step_queue(),
+                                       {"mean": "reddit_gather", "max_pool": "maxpool_k3",
+                                        "attention": "attention_k4"}.get(args.aggregator, args.aggregator))
+            else:
+                roof = standalone_gather_probe(gs, model, store, data, dev, fanout, B)
+            step_alg = rows_per_seed(fanout) * FEAT_DIM * elem * B
+            roof["step"] = {"alg_bytes_per_step": step_alg, "ms_per_step": elapsed / args.steps * 1e3,
+                            "achieved": step_alg / (elapsed / args.steps) / 1e9,
+                            "frac": step_alg / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS}
         line = {
             "metric": "seed-nodes/sec", "value": value, "unit": "seed-nodes/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1036,9 +1054,9 @@ def main():
                 rows_per_seed(fanout) * FEAT_DIM * elem)),
             "roofline": roof,
         }
-        # other BASELINE configurations on the same graph, so that the driver's run measures them too
+        # other BASELINE configurations on the same graph (--full)
         extra = {}
-        if world == 1:
+        if args.full and world == 1:
             del res, step_fn, model
             torch.cuda.empty_cache()
             names = [a for a in args.extra.split(",") if a and a != args.aggregator]
@@ -1082,7 +1100,7 @@ def main():
             if "fp32" in names and args.precision != "fp32":
                 extra["fp32"] = extra_fp32(args)
         line["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(data, budget_s=args.cpu_budget)
         else:
             line["cpu_baseline"] = None

@@ -37,3 +37,19 @@ def test_bench_dumps_the_last_timed_step_reproducibly(tmp_path):
         assert a[k].dtype in (np.float32, np.float64), (k, a[k].dtype)
         assert np.isfinite(a[k]).all(), k
         close(a[k], b[k], k, 1e-3, 1e-3)
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without --full the run sets up, warms up, times its steps and prints the line: no in-step roofline, no other
+    configurations, no CPU baseline.  Naming other configurations without --full is refused before anything runs."""
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "2"], cwd=ROOT, capture_output=True,
+                       text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "seed-nodes/sec" and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["dtype"] == "bf16"
+    assert rec["roofline"] is None and rec["extra"] == {} and rec["cpu_baseline"] is None
+    r = subprocess.run([sys.executable, "bench.py", "--extra", "max_pool"], cwd=ROOT, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-2000:]

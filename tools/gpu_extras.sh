@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 OUT=gpurun_out
 mkdir -p $OUT
-timeout 400 python bench.py > $OUT/bench.log 2>&1; echo "== bench rc=$?"
+timeout 400 python bench.py --full > $OUT/bench.log 2>&1; echo "== bench rc=$?"
 timeout 200 env GSAGE_FORCE_DDP=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --extra "" 2>/dev/null | grep "^{" > $OUT/bench_ddp1.json; echo "== ddp1 rc=$?"
 for cfg in pokec papers; do
   rm -rf $OUT/prof_$cfg
@@ -15,7 +15,7 @@ for cfg in pokec papers; do
 done
 for agg in attention max_pool; do
   rm -rf $OUT/prof_x_$agg
-  timeout 250 rocprofv3 --kernel-trace --stats -d $OUT/prof_x_$agg -o r --output-format csv -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --extra $agg --min-time 0 > $OUT/prof_x_$agg.log 2>&1
+  timeout 250 rocprofv3 --kernel-trace --stats -d $OUT/prof_x_$agg -o r --output-format csv -- python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --extra $agg --min-time 0 > $OUT/prof_x_$agg.log 2>&1
   echo "== prof $agg rc=$?"
   find $OUT/prof_x_$agg -name "*kernel_trace*" -size +10M -delete
 done

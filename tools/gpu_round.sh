@@ -23,11 +23,11 @@ for w in $WHAT; do
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       echo "== smoke rc=$?"; tail -5 $OUT/smoke.log ;;
     bench)
-      timeout 900 python bench.py > $OUT/bench.log 2>&1
+      timeout 900 python bench.py --full > $OUT/bench.log 2>&1
       echo "== bench rc=$?"; tail -3 $OUT/bench.log ;;
     pool|attn)
       a=max_pool; [ $w = attn ] && a=attention
-      timeout 600 python bench.py --aggregator $a --steps 50 --warmup 10 --no-cpu-baseline --extra '' > $OUT/bench_$w.log 2>&1
+      timeout 600 python bench.py --aggregator $a --steps 50 --warmup 10 --full --no-cpu-baseline --extra '' > $OUT/bench_$w.log 2>&1
       echo "== bench $a rc=$?"; tail -1 $OUT/bench_$w.log | cut -c1-900 ;;
     sq)
       # where the waves of one configuration wait: SQ counters (one pass), then L2 hit / miss (second pass)
@@ -59,7 +59,7 @@ for w in $WHAT; do
       echo "== gemmref rc=$?"; grep gemmref $OUT/gemmref.log ;;
     benchx)
       # bench.py with caller-chosen arguments: GSAGE_BENCH_ARGS="--extra ddp_1rank,pokec --no-cpu-baseline"
-      timeout 900 python bench.py ${GSAGE_BENCH_ARGS} > $OUT/benchx.log 2>&1
+      timeout 900 python bench.py --full ${GSAGE_BENCH_ARGS} > $OUT/benchx.log 2>&1
       echo "== benchx rc=$?"; tail -1 $OUT/benchx.log | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
@@ -68,7 +68,7 @@ for k, v in d.get('extra', {}).items():
     print(k, {a: (b if not isinstance(b, dict) else {x: y for x, y in b.items() if x in ('ms_per_step', 'error')}) for a, b in v.items() if a in ('ms_per_step', 'overlapped', 'inline', 'error', 'cli_seeds_per_s', 'wall_s')})
 " ;;
     bench20)
-      timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench20.log 2>&1
+      timeout 900 python bench.py --steps 20 --warmup 5 --full > $OUT/bench20.log 2>&1
       echo "== bench20 rc=$?"; tail -2 $OUT/bench20.log ;;
     prof)
       rm -rf $OUT/prof

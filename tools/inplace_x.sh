@@ -3,7 +3,7 @@
 # (default); the engine tests once more on the copy path.
 cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 export TMPDIR=/tmp
-run() { timeout 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --extra "" 2>/dev/null | grep "^{" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.4f ms/step, gather launch %.1f us' % (d['ms_per_step'], d['roofline']['avg_launch_us']))"; }
+run() { timeout 200 python bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --extra "" 2>/dev/null | grep "^{" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.4f ms/step, gather launch %.1f us' % (d['ms_per_step'], d['roofline']['avg_launch_us']))"; }
 echo -n "x rows copied:   "; GSAGE_MEAN_INPLACE_X=0 run
 echo -n "x rows in place: "; run
 echo -n "x rows copied:   "; GSAGE_MEAN_INPLACE_X=0 run

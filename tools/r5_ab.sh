@@ -10,7 +10,7 @@ if [ "${R5_TESTS:-1}" = "1" ]; then
 fi
 b() {  # name, env...
   name=$1; shift
-  env "$@" timeout 300 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --extra '' --min-time 0.4 > $OUT/ab_$name.log 2>&1
+  env "$@" timeout 300 python bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --extra '' --min-time 0.4 > $OUT/ab_$name.log 2>&1
   python - "$name" $OUT/ab_$name.log <<'PY'
 import sys, json
 name, path = sys.argv[1:3]

@@ -8,7 +8,7 @@ if "--" in args:
 name, values = args[0], args[1:]
 for v in values:
     env = dict(os.environ); env[name] = v
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--extra", ""] + extra,
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--extra", ""] + extra,
                          env=env, capture_output=True, text=True)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not line:
