@@ -11,7 +11,7 @@ import torch
 from .. import _native as nat
 from .. import ops
 from ..nn_modules import AttentionAggregator, IdentityPrep, NodeEmbeddingPrep
-from .common import FusedTrainStep, _PrepDesc, _Wgrad, _r64
+from .common import FusedTrainStep, _Wgrad, _round64
 
 
 class FusedAttnTrainStep(FusedTrainStep):
@@ -60,7 +60,7 @@ class FusedAttnTrainStep(FusedTrainStep):
         self.h = [l.output_dim_ for l in self.layers]
         if self.emb:                                 # level-0 rows = [features |] prep.fc(embedding[ids])
             d0 = self.D0 + self.E
-            ld0 = _r64(d0) if T == torch.bfloat16 else (-(-d0 // 8) * 8 if self.D0 else d0)
+            ld0 = _round64(d0) if T == torch.bfloat16 else (-(-d0 // 8) * 8 if self.D0 else d0)
         else:
             d0, ld0 = feats.dim, feats.ld
         self.din = [d0] + [2 * h for h in self.h[:-1]]
@@ -68,15 +68,7 @@ class FusedAttnTrainStep(FusedTrainStep):
         self.rows = [self.off[L - l] for l in range(L)]              # x rows of level l
         self.rall = [self.off[L - l + 1] for l in range(L)]          # all input rows of level l
         assert all(d % 8 == 0 for d in self.ldin)
-        descs = []
-
-        def copies(prm, need_t):
-            r, c = prm.shape
-            w = torch.zeros(r, _r64(c), dtype=T, device=dev)
-            wt = torch.zeros(c, _r64(r), dtype=T, device=dev) if need_t else None
-            descs.append(_PrepDesc(prm.data_ptr(), w.data_ptr(), wt.data_ptr() if need_t else None, r, c, w.shape[1],
-                                   wt.shape[1] if need_t else 0, None, 0, int(self.code == nat.F32), 0))
-            return w, wt
+        copies = self._operand_copies
         self.w0, self.w0T, self.w2, self.w2T, self.wx, self.wxT, self.wn, self.wnT = ([] for _ in range(8))
         for l, layer in enumerate(self.layers):
             ing = l > 0 or self.emb                  # does this level's input need a gradient?
@@ -85,16 +77,12 @@ class FusedAttnTrainStep(FusedTrainStep):
             a, b = copies(layer.fc_x.weight, ing); self.wx.append(a); self.wxT.append(b)
             a, b = copies(layer.fc_neib.weight, True); self.wn.append(a); self.wnT.append(b)
         if self.emb:
-            self._init_emb(copies)
-        self.descs = torch.frombuffer(bytearray(bytes((_PrepDesc * len(descs))(*descs))), dtype=torch.uint8).to(dev)
-        self.n_desc = len(descs)
-        self.max_elems = max(d.rows * d.cols for d in descs)
+            self._init_emb()
 
         # level-0 rows of every hop.  Feature rows are read IN PLACE through the frontier's row list (K5 / K4 / K4' /
         # K5b all take one; GSAGE_ATTN_COPY_ROWS=1: gathered once per step into one buffer per batch in flight, as
         # the embedding prep needs anyway for its output rows); the gather launch then only carries the seeds' rows
         self.inplace0 = (not self.emb) and os.environ.get("GSAGE_ATTN_COPY_ROWS", "0") != "1"
-        self._q_ids, self._cur_ids = None, self.ids_set[0]
         self.g0_set = [torch.zeros(self.B if self.inplace0 else self.rall[0], self.ldin[0], dtype=T, device=dev)
                        for _ in range(self.nset)]
         Ha, HL = self.Ha, self.HA_LD
@@ -132,7 +120,7 @@ class FusedAttnTrainStep(FusedTrainStep):
         if l > 0:
             return self.hout[l - 1], self.ldin[l], None
         if self.inplace0:
-            return self.store.data, self.ldin[0], self._cur_ids
+            return self.store.data, self.ldin[0], self._front
         return self.g0_set[s], self.ldin[0], None
 
     def _init_reduce(self):
@@ -197,7 +185,6 @@ class FusedAttnTrainStep(FusedTrainStep):
     def _stage_compute(self, s):
         L, B, lib, stream, m = self.L, self.B, nat.lib(), ops._stream(), self.model
         Ha, HL, esz = self.Ha, self.HA_LD, self.esz
-        self._cur_ids = self._q_ids if self._q_ids is not None else self.ids_set[s]
         if self.emb:
             self._prep_forward(s)
         for l in range(L):

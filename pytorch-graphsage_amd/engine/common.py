@@ -10,7 +10,8 @@ ahead) live in mean.py / pool.py / attn.py: subclasses implement `why_not`, `_in
 `_stage_gather`, `_stage_compute`, `_backward_levels`, and for the weight gradients `_wgrad_problems(s)` (the
 step's K5b problems of batch set s, `_Wgrad`s in launch order) and `_wgrad_targets(problems)` (workgroups to aim at,
 one per problem).  This module slices those problems once (`_plan_wgrad`) and issues them against that plan
-(`_stage_wgrad`).
+(`_stage_wgrad`).  It also allocates the weights' operand copies for `_init_levels` (`_operand_copies`) and names
+the frontier the batch being computed lives in (`self._front`: set on entry to a step's stages, read inside them).
 """
 import collections
 import ctypes
@@ -44,8 +45,8 @@ class _PrepDesc(ctypes.Structure):           # mirrors gsage_prep_desc (include/
 _Wgrad = collections.namedtuple("_Wgrad", "dC A lda a_gstride M Ntot K n_per_group rows param")
 
 
-def _r8(v):
-    return (v + 63) // 64 * 64          # whole 128-byte bf16 lines: enables the LDS-DMA GEMM path
+def _round64(v):
+    return (int(v) + 63) // 64 * 64     # whole 128-byte bf16 lines: enables the LDS-DMA GEMM path
 
 
 class _ListRunner(object):
@@ -56,10 +57,6 @@ class _ListRunner(object):
 
     def replay(self):
         self.cl.replay(ops._stream())
-
-
-def _r64(v):
-    return (int(v) + 63) // 64 * 64
 
 
 class FusedTrainStep(object):
@@ -73,6 +70,7 @@ class FusedTrainStep(object):
 
     MEAN_ENGINE = False       # FusedMeanTrainStep only: seed-level kernel, gathers cut around the exchange
     ROW_HIST = 1 << 15        # updates whose constants are kept for deferred table rows (sync_rows() before it wraps)
+    FRAG_COPIES = False       # FusedPoolTrainStep only: its refresh descriptors carry the MFMA fragment geometry
 
     # ---- which (model, feature store) pairs an engine covers ----------------------------------------
     @classmethod
@@ -184,6 +182,7 @@ class FusedTrainStep(object):
         assert not (self.eval_only and (ddp is not None or pipelined)), "eval_only: single process, sequential"
         self._init_common(model, feats, loss_fn, example_ids, example_targets, ddp, pipelined)
         self._init_levels(example_ids, example_targets)
+        self._upload_prep_descs()
         self._init_head(loss_fn, example_targets)
         if self.eval_only:
             Cc, D2c = model.fc.weight.shape
@@ -222,6 +221,14 @@ class FusedTrainStep(object):
         self._front_ready, self._qstep = False, 0
         self.g_prime, self.g_qfront, self.g_queue = None, None, None
         self._tail_gather, self._tail_rows = None, 0
+        self.P, self._k1_where = 2, None          # ring of frontier buffers / where K1 rides: load_epoch decides
+        self._k5_hops, self._marks = None, False  # sampler role of a compute launch (P == 3) / instrument() is on
+        self._prep_descs = []                     # refresh descriptors of the operand copies (_operand_copies)
+        self.n_rdesc, self._rdesc_max_S = None, None       # finalisation table (_install_reduce)
+        self._norm_slots, self._meet_ok, self._fold = None, None, None     # (_slots, _meet_fits, _fold_finalize: once)
+        self._ticks_issued = False                # _wgrad_ticks ran for the step being issued (no finalisation launch)
+        self._warm_reset = ()                     # device state of the warm-up steps that _finish_init zeroes
+        self._closed, self._lr_host = False, None          # close() ran / the lr last written to the device
         self._reduce_op = None
         if ddp is not None:
             # averaging inside the collective saves a launch; fall back to divide-then-sum where
@@ -321,12 +328,16 @@ class FusedTrainStep(object):
         self.n_calls = 0
         # optional device-resident batch queue (load_epoch): the graph then needs no per-step copies
         self.queue = None
-        self._q_ids = None                            # frontier of the batch a queue-mode compute stage works on
         self.batch_idx = torch.zeros(1, dtype=torch.int64, device=dev)
         self.ids_set = [torch.zeros(self.off[L + 1], dtype=torch.int64, device=dev) for _ in range(self.nset)]
         self.tg_set = [example_targets.clone() for _ in range(self.nset)]
         self.ids_set[0][:B].copy_(example_ids)
-
+        # The frontier buffer that the launches being issued or recorded right now belong to (ids_set[s], or the queue
+        # ring's ids_q[par]): set on entry to a step's compute / exchange / update stages, only read inside them.
+        # pipelined=True keeps two batches in flight on two streams, but one host thread issues both, stage after
+        # stage: "set at stage entry" stays well defined.  What works on a LATER batch (_stage_gather(ids=...),
+        # _hops_desc) is handed its buffer and does not look here.
+        self._front = self.ids_set[0]
 
     def _will_fuse_head(self, example_targets):
         from ..problem import ProblemLosses
@@ -428,7 +439,6 @@ class FusedTrainStep(object):
         os.write(2, text.encode())          # (fd 2, not sys.stderr: survives a test runner's sys-level capture)
 
     def _finish_init(self, capture, warmup):
-        ddp = self.ddp
         if os.environ.get("GSAGE_DEBUG_ADDR", "0") == "1":
             self._debug_addresses()
         if self.eval_only:
@@ -446,8 +456,8 @@ class FusedTrainStep(object):
         self.flat_p.copy_(saved)
         for t, v in zip((self.flat_m, self.flat_v, self.step), saved_opt):
             t.copy_(v)
-        slots = getattr(self, "_norm_slots", None)     # (tags of the warm-up's update numbers must not meet the run's)
-        for t in (self.counter,) + tuple(getattr(self, "_warm_reset", ())) + ((slots,) if slots is not None else ()):
+        slots = self._norm_slots                       # (tags of the warm-up's update numbers must not meet the run's)
+        for t in (self.counter,) + tuple(self._warm_reset) + ((slots,) if slots is not None else ()):
             t.zero_()
         if self.lazy_rows and int(self.step.item()) > 0:      # deferred table rows: every row is current at that count
             self.row_last.fill_(int(self.step.item()))
@@ -493,6 +503,7 @@ class FusedTrainStep(object):
         one_list = self._one_list_ddp()
 
         def main(st_):
+            self._front = self.ids_set[st_]
             if not self.pipelined:
                 self._stage_sample_gather(0)
             self._stage_compute(st_)
@@ -541,6 +552,29 @@ class FusedTrainStep(object):
         self._pool = g.pool()
         return g
 
+    def _operand_copies(self, prm, need_t, packed=False):
+        """Operand copies of the weight prm [r, c] in the storage type, rows padded to whole 128-byte bf16 lines:
+        (w [r, c+], the transposed wt [c, r+] or None[, with packed: the copy in MFMA fragment order that the
+        gsage_*_packed forwards read -- bf16 storage only, else None]).  Appends their refresh descriptor."""
+        (r, c), T, dev = prm.shape, self.tdt, self.dev
+        w = torch.zeros(r, _round64(c), dtype=T, device=dev)
+        wt = torch.zeros(c, _round64(r), dtype=T, device=dev) if need_t else None
+        wp = (torch.zeros(nat.lib().gsage_packed_weight_elems(r, c, 1), dtype=T, device=dev)
+              if packed and self.code == nat.BF16 else None)
+        self._prep_descs.append(_PrepDesc(prm.data_ptr(), w.data_ptr(), wt.data_ptr() if need_t else None, r, c,
+                                          w.shape[1], wt.shape[1] if need_t else 0,
+                                          wp.data_ptr() if wp is not None else None,
+                                          4 * (-(-c // 64)) if self.FRAG_COPIES else 0, int(self.code == nat.F32), 0))
+        return (w, wt, wp) if packed else (w, wt)
+
+    def _upload_prep_descs(self):
+        """(after _init_levels) the table gsage_prep_weights and Adam refresh the operand copies from"""
+        descs = self._prep_descs
+        raw = bytes((_PrepDesc * len(descs))(*descs))
+        self.descs = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
+        self.n_desc = len(descs)
+        self.max_elems = max(d.rows * d.cols for d in descs)
+
     def refresh_weights(self):
         """Rebuild the bf16 operand copies from the fp32 Parameters.  Adam keeps them current;
         call this after changing the weights from outside (load_state_dict, manual edits)."""
@@ -553,12 +587,9 @@ class FusedTrainStep(object):
         base, es = self.flat_p.data_ptr(), 4
         return all(p.data_ptr() == base + o * es for p, o in zip(self.params, self.poff))
 
-    def _settled(self):
-        self.sync_rows()
-
     def optimizer_state_dict(self):
         """torch.optim.Adam's format (as optim.FlatAdam.state_dict): the engine's exp_avg / exp_avg_sq / step."""
-        self._settled()
+        self.sync_rows()
         state, n = {}, int(self.step.item())
         if n > 0:
             step = torch.tensor(float(n))
@@ -577,7 +608,7 @@ class FusedTrainStep(object):
         continue instead of restarting)."""
         assert [p.numel() for p in flat_adam.params] == [p.numel() for p in self.params], \
             "export_optimizer_state: different parameter lists"
-        self._settled()
+        self.sync_rows()
         flat_adam.flat_m.copy_(self.flat_m)
         flat_adam.flat_v.copy_(self.flat_v)
         flat_adam.step_count.copy_(self.step)
@@ -696,6 +727,7 @@ class FusedTrainStep(object):
             nat.check(nat.lib().gsage_counter_add(self.counter.data_ptr(), self.L, ops._stream()), "counter_add")
 
     def _adam_desc(self):
+        assert not self.eval_only, "an eval_only engine has no buckets and issues no update"
         d = nat.AdamDesc()
         d.p, d.g, d.m, d.v = (self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_m.data_ptr(),
                               self.flat_v.data_ptr())
@@ -720,7 +752,7 @@ class FusedTrainStep(object):
         return d
 
     def _slots(self):
-        if getattr(self, "_norm_slots", None) is None:
+        if self._norm_slots is None:
             self._norm_slots = torch.zeros(1024, dtype=torch.int64, device=self.dev)
         return self._norm_slots
 
@@ -728,7 +760,7 @@ class FusedTrainStep(object):
         """The in-launch norm is a meeting of the update's workgroups (one per 1 024 parameters): every one of them
         must be RESIDENT at once in the launch that carries them -- asked of the device (occupancy of the gather
         launch with the sampler role's LDS, times the CU count, one workgroup per CU kept as margin), not assumed."""
-        if getattr(self, "_meet_ok", None) is None:
+        if self._meet_ok is None:
             n_wg = -(-(-(-self.flat_p.numel() // 4)) // 256)
             widest, width = 1, 1
             for k in range(1, self.L + 1):
@@ -758,11 +790,12 @@ class FusedTrainStep(object):
         gathers, an update workgroup's six to eight dependent rounds of partial loads (16 in flight per lane is what
         the launch's 72-register cap leaves) take ~28 us against 6.5 + 16 for the finalisation launch and the
         update without them -- 0.0916 against 0.0836 ms/step at configs[1]."""
-        if getattr(self, "_fold", None) is None:
+        if self._fold is None:
+            assert self.n_rdesc is not None, "asked before _install_reduce(): the kept answer would not be the table's"
             mode = os.environ.get("GSAGE_FOLD_FINALIZE", "0")
             ok = (mode in ("1", "all") and (self.MEAN_ENGINE or mode == "all") and self.ddp is None and not self.emb
-                  and (self.fused_head or self.fused_l1) and getattr(self, "n_rdesc", 99) <= 16
-                  and getattr(self, "_rdesc_max_S", 1 << 30) <= 32 and self._meet_fits())
+                  and (self.fused_head or self.fused_l1) and self.n_rdesc <= 16
+                  and self._rdesc_max_S <= 32 and self._meet_fits())
             self._fold = bool(ok)
         return self._fold
 
@@ -889,7 +922,7 @@ class FusedTrainStep(object):
         Adam step, Philox call counter, batch-queue index (nothing else in this launch reads them)."""
         L, lib, stream = self.L, nat.lib(), ops._stream()
         if self._fold_finalize():
-            assert getattr(self, "_ticks_issued", False), "no finalisation launch: _wgrad_ticks() must precede K5b"
+            assert self._ticks_issued, "no finalisation launch: _wgrad_ticks() must precede K5b"
             self._ticks_issued = False
             return
         nat.check(lib.gsage_finalize_grads(self.rdescs.data_ptr(), self.n_rdesc, self.r_max,
@@ -950,7 +983,7 @@ class FusedTrainStep(object):
         them apply the identical touched-row set to the deferred-row Adam."""
         if self.ddp is None:
             return
-        if getattr(self, "_marks", False) and self._in_list:           # (instrument(): events around the exchange)
+        if self._marks and self._in_list:                              # (instrument(): events around the exchange)
             nat.check(nat.lib().gsage_cmdlist_mark(8), "cmdlist_mark")
             try:
                 self._exchange_nodes()
@@ -962,7 +995,7 @@ class FusedTrainStep(object):
     def _exchange_nodes(self):
         if self.emb and self.lazy_rows:
             B, RA0 = self.B, self.off[self.L + 1]
-            ids = self._cur_ids
+            ids = self._front
             if self.comm is not None:
                 self.comm.group(True, ops._stream())
             self._x_all_reduce(self.flat_g[self.n_tab:])
@@ -998,13 +1031,11 @@ class FusedTrainStep(object):
                   "clip_adam_step")
 
     def _run_sequential(self, s):
-        if self.emb:
-            self._cur_ids = self.ids_set[s]
+        self._front = self.ids_set[s]
         self._stage_sample_gather(s)
         self._stage_compute(s)
         self._stage_exchange()
         self._stage_opt()
-
 
     # =================================================================================================
     # Trainable node-embedding prep (reference nn_modules.py:126-155; BASELINE configs[3], utils/pokec.sh).
@@ -1016,14 +1047,13 @@ class FusedTrainStep(object):
     # attention engines; a subclass calls _init_emb() from _init_levels, adds _emb_wgrad_problem() to its K5b
     # problems, forms the level-0 input gradient (din0f / din0) and hands over to _prep_backward().
     # =================================================================================================
-    def _init_emb(self, copies):
-        """copies(parameter, need_transposed) -> (operand copy, transposed copy): the subclass's operand-copy factory
-        (it also records the refresh descriptor).  Allocates the prep's work buffers."""
+    def _init_emb(self):
+        """Operand copies of prep.fc.weight (behind the levels' in the refresh table) and the prep's work buffers."""
         prep, dev, T, f32 = self.model.prep, self.dev, self.tdt, torch.float32
         RA0, E = self.off[self.L + 1], self.E
         ld0 = self.ldE = -(-E // 8) * 8 if T == torch.bfloat16 else E          # (the prep's own operands: E wide)
         assert self.din[0] == self.D0 + E and tuple(prep.fc.weight.shape) == (E, E)
-        self.wprep, self.wprepT = copies(prep.fc.weight, True)   # (operand copies of prep.fc.weight)
+        self.wprep, self.wprepT = self._operand_copies(prep.fc.weight, True)
         self.table = prep.embedding.weight                 # a view of the flat parameter bucket
         assert self.pidx[id(self.table)] == 0 and self.table.shape[1] == E and self.table.numel() % 4 == 0
         self.seed_rows = torch.full((self.B,), int(prep.n_nodes), dtype=torch.int64, device=dev)
@@ -1034,7 +1064,6 @@ class FusedTrainStep(object):
         self.prep_bpart = torch.zeros(256, E, dtype=f32, device=dev)             # prep.fc.bias gradient partials
         self.seed_grad = torch.zeros(min(16, self.B), E, dtype=f32, device=dev)   # partial sums of the gradient of
         #                                                                             the spare row the seeds read
-        self._cur_ids = self.ids_set[0]
         # the prep as row pipelines (csrc/gsage_prep_rows.hip: gather + prep.fc in one launch; the level-0 input
         # gradient, the bias sums, the product through prep.fc^T and the table's atomics in another);
         # GSAGE_PREP_ROWS=0: the separate launches
@@ -1104,7 +1133,7 @@ class FusedTrainStep(object):
 
     def _prep_forward(self, s):
         lib, stream, prep = nat.lib(), ops._stream(), self.model.prep
-        ids, B, RA0, E = self._cur_ids, self.B, self.off[self.L + 1], self.E
+        ids, B, RA0, E = self._front, self.B, self.off[self.L + 1], self.E
         tab = self.table
         if self.lazy_rows:       # the rows this step reads, brought up to the last update
             nat.check(lib.gsage_rows_catch_up(ctypes.byref(self.row_desc), self.seed_rows.data_ptr(), 1,
@@ -1134,7 +1163,7 @@ class FusedTrainStep(object):
         gradient as gsage_attn_merge_bwd2 takes them (pointers already at the prep's columns), or d hid + the transposed
         operand copy of att.0 instead of the gradient through att(.) -> din0, the bias partials, the table's gradient."""
         lib, stream = nat.lib(), ops._stream()
-        ids, B, RA0, E, L = self._cur_ids, self.B, self.off[self.L + 1], self.E, self.L
+        ids, B, RA0, E, L = self._front, self.B, self.off[self.L + 1], self.E, self.L
         g = self._grad_slice(self.table)
         sorted_rows = self.lazy_rows and self.sorted_rows       # (the rows then meet in _stage_opt_emb, from deraw)
         nat.check(lib.gsage_prep_rows_bwd(
@@ -1152,7 +1181,7 @@ class FusedTrainStep(object):
         """level 0's input gradient (din0f fp32, din0 = its operand copy; formed by the subclass) -> prep.fc (weight:
         a K5b problem of level 0; bias: column sums) -> the table's gradient."""
         lib, stream = nat.lib(), ops._stream()
-        ids, B, RA0, E = self._cur_ids, self.B, self.off[self.L + 1], self.E
+        ids, B, RA0, E = self._front, self.B, self.off[self.L + 1], self.E
         nat.check(lib.gsage_colsum_partials(self.din0f.data_ptr(), E, RA0, E, self.prep_bpart.data_ptr(),
                                             self.prep_bpart.shape[0], stream), "colsum_partials")
         ops._linear_launch(self.din0.data_ptr(), self.din0.stride(0), None, 0, self.wprepT.data_ptr(), self.wprepT.shape[1],
@@ -1175,7 +1204,7 @@ class FusedTrainStep(object):
         g = self._grad_slice(self.table)
         n_all = self.n_partial + self.n_tab_partial
         if self.lazy_rows:
-            ids = self._cur_ids
+            ids = self._front
             base = self.n_partial             # norm partials of the other parameters: the finalisation's ...
             if self.ddp is not None:          # ... or, after an exchange, those of the AVERAGED gradient
                 nd = self.flat_p.numel() - nt
@@ -1230,7 +1259,7 @@ class FusedTrainStep(object):
                                                d.weight_decay, d.max_norm, d.norm_out, cur, n_all, prep, n_prep, None,
                                                0, None, 0, stream), "clip_adam_step")
         # the table's gradient goes back to zero by touching the rows this step wrote
-        ids = self._cur_ids
+        ids = self._front
         for idv, M in ((self.seed_rows[:1], 1), (ids[B:RA0], RA0 - B)):
             nat.check(lib.gsage_zero_rows(g.data_ptr(), E, idv.data_ptr(), M, E, stream), "zero_rows")
 
@@ -1256,7 +1285,7 @@ class FusedTrainStep(object):
             self._closed = True
 
     def _rows_tick(self):
-        if getattr(self, "_closed", False):
+        if self._closed:
             raise RuntimeError("this engine was closed (deferred table rows settled, hooks removed): build a new one")
         if self.lazy_rows:
             if self._rows_since >= self.ROW_HIST - 2:
@@ -1298,8 +1327,7 @@ class FusedTrainStep(object):
     def _eval_step(self):
         """sample (the queue's next batch, its recorded draws) -> gather -> forward -> tick"""
         lib, st = nat.lib(), ops._stream()
-        if self.emb:
-            self._cur_ids = self.ids_set[0]
+        self._front = self.ids_set[0]
         self._stage_sample(0)
         self._stage_gather(0)
         self._stage_compute(0)
@@ -1345,7 +1373,7 @@ class FusedTrainStep(object):
     def set_progress(self, progress):
         self.model.lr = self.model.lr_scheduler(progress)
         lr = float(self.model.lr)
-        if lr != getattr(self, "_lr_host", None):      # (a constant schedule costs no launch per batch)
+        if lr != self._lr_host:                        # (a constant schedule costs no launch per batch)
             self._lr_host = lr
             self.lr.fill_(lr)
 
@@ -1491,7 +1519,7 @@ class FusedTrainStep(object):
 
     def last_launch_ms(self):
         if self.queue is not None:
-            par = (self._qstep - 1) % getattr(self, "P", 2)
+            par = (self._qstep - 1) % self.P
             cl = self.g_queue[par].cl
             front = cl
         else:
@@ -1507,7 +1535,7 @@ class FusedTrainStep(object):
 
     def _time_next(self, a, b):
         """While recording an instrumented list: attach start / stop events a, b to the next kernel."""
-        if getattr(self, "_marks", False) and self.capture_mode == "cmdlist":
+        if self._marks and self.capture_mode == "cmdlist":
             nat.check(nat.lib().gsage_cmdlist_time_next(a, b), "cmdlist_time_next")
 
     # the queue pipeline's pieces; par = parity of the step: batch i+1 is gathered from ids_q[1 - par]
@@ -1523,11 +1551,11 @@ class FusedTrainStep(object):
 
     def _nx(self, par):
         """ring position of the NEXT batch (gathered during this step)"""
-        return (par + 1) % getattr(self, "P", 2)
+        return (par + 1) % self.P
 
     def _nx2(self, par):
         """ring position the batch AFTER the next is sampled into"""
-        return (par + 2) % getattr(self, "P", 2)
+        return (par + 2) % self.P
 
     def _queue_prime(self):
         self._stage_sample(0, ids=self.ids_q[0])
@@ -1538,7 +1566,7 @@ class FusedTrainStep(object):
     def _queue_front(self, par, with_adam):
         if self.emb:
             assert with_adam
-            self._cur_ids = self.ids_q[par]
+            self._front = self.ids_q[par]
             self._stage_opt()                                  # Adam(i) + zeroing of the rows batch i touched
             self._stage_sample(0, ids=self.ids_q[par], ahead=True)      # batch i+2 (batch i's frontier is done with)
             return
@@ -1555,11 +1583,8 @@ class FusedTrainStep(object):
                            skip_rows=self._ahead_rows())
 
     def _queue_compute(self, par):
-        self._q_ids = self.ids_q[par]
-        try:
-            return self._queue_compute_body(par)
-        finally:
-            self._q_ids = None
+        self._front = self.ids_q[par]
+        self._queue_compute_body(par)
 
     def _queue_step(self, par):
         self._queue_compute(par)
@@ -1574,7 +1599,6 @@ class FusedTrainStep(object):
         self._queue_compute(par)
         if self.emb:
             # the level-0 rows are weights: nothing of batch i+1 can run before Adam(i) -- exchange, then update
-            self._cur_ids = self.ids_q[par]
             self._stage_exchange()
             self._queue_front(par, True)
             return
@@ -1643,7 +1667,7 @@ class FusedTrainStep(object):
         # (Order and priority were measured on one rank, 0.1205 ms/step as written: the means submitted BEFORE
         # the collective 0.137; RCCL's stream at high priority 0.46 -- its kernel then preempts the gathers.)
         if self.emb:
-            self._cur_ids = self.ids_q[par]
+            self._front = self.ids_q[par]         # (the exchange is issued from here, between two recordings)
             self._stage_exchange()
             self.g_qfront[par].replay()
             return self.preds
@@ -1656,7 +1680,7 @@ class FusedTrainStep(object):
     def _pad_batch(self, ids, targets):
         """A batch one or a few seeds short of B (the reference's near-equal chunks): pad with its first seed."""
         b = int(ids.shape[0])
-        if not (2 <= b < self.B) or not (self.fused_head or getattr(self, "fused_l1", False)):
+        if not (2 <= b < self.B) or not (self.fused_head or self.fused_l1):
             raise ValueError("this engine was recorded for batches of %d seeds (got %d); shorter batches need one of "
                              "the fused heads" % (self.B, b))
         pad = self.B - b
@@ -1729,6 +1753,7 @@ class FusedTrainStep(object):
         with torch.cuda.stream(self.s_back):
             self.s_back.wait_event(self.ev_front[par])
             if self.g_main is None:
+                self._front = self.ids_set[par]
                 self._stage_compute(par)
                 if self.ddp is not None:
                     self._all_reduce()

@@ -10,7 +10,7 @@ import torch
 from .. import _native as nat
 from .. import ops
 from ..nn_modules import IdentityPrep, MeanAggregator
-from .common import FusedTrainStep, _PrepDesc, _Wgrad, _r8
+from .common import FusedTrainStep, _PrepDesc, _Wgrad, _round64
 
 
 class FusedMeanTrainStep(FusedTrainStep):
@@ -46,7 +46,6 @@ class FusedMeanTrainStep(FusedTrainStep):
     MEAN_ENGINE = True
     TIMED = {"gather": (0, 1), "seed_level": (2, 3), "k5": (4, 5), "k5b": (6, 7)}
 
-
     @classmethod
     def why_not(cls, model, feats, ddp=None):
         # bf16 storage = the production path; fp32 storage = the exact-arithmetic parity mode (same engine, same
@@ -67,20 +66,20 @@ class FusedMeanTrainStep(FusedTrainStep):
         self.h = [l.output_dim_ for l in self.layers]
         if self.emb:                                 # level-0 rows = [features |] prep.fc(embedding[ids])
             d0 = self.D0 + self.E
-            ld0 = _r8(d0) if (self.tdt == torch.bfloat16 or self.D0) else d0
+            ld0 = _round64(d0) if (self.tdt == torch.bfloat16 or self.D0) else d0
         else:
             d0, ld0 = feats.dim, feats.ld
         self.din = [d0] + [2 * h for h in self.h[:-1]]
         self.ldin = [ld0] + [2 * h for h in self.h[:-1]]
         self.rows = [self.off[L - l] for l in range(L)]           # R_l = rows of level l
-        self.w2, self.w2t, self.wp, descs = [], [], [], []
+        self.w2, self.w2t, self.wp = [], [], []
         for l, layer in enumerate(self.layers):
             h, din = self.h[l], self.din[l]
             assert tuple(layer.fc_x.weight.shape) == (h, din) == tuple(layer.fc_neib.weight.shape)
             ix, inb = self.pidx[id(layer.fc_x.weight)], self.pidx[id(layer.fc_neib.weight)]
             assert inb == ix + 1, "fc_x / fc_neib must be adjacent in the parameter order"
-            w2 = torch.zeros(2, h, _r8(din), dtype=self.tdt, device=dev)
-            w2t = torch.zeros(2, din, _r8(h), dtype=self.tdt, device=dev) if (l > 0 or self.emb) else None
+            w2 = torch.zeros(2, h, _round64(din), dtype=self.tdt, device=dev)
+            w2t = torch.zeros(2, din, _round64(h), dtype=self.tdt, device=dev) if (l > 0 or self.emb) else None
             tail_level = self._will_fuse_tail(example_targets) and l == L - 1
             self.w2.append(w2)
             self.w2t.append(w2t)
@@ -94,24 +93,13 @@ class FusedMeanTrainStep(FusedTrainStep):
             self.wp.append(wp)
             for g, prm in enumerate((layer.fc_x.weight, layer.fc_neib.weight)):
                 # (a copy nobody reads is not refreshed: w2 serves the unpacked K5 and the seed-level kernel)
-                descs.append(_PrepDesc(prm.data_ptr(), w2[g].data_ptr() if (not packed or tail_level) else None,
-                                       w2t[g].data_ptr() if w2t is not None else None,
-                                       h, din, w2.shape[2], w2t.shape[2] if w2t is not None else 0,
-                                       wp[g * gstride:].data_ptr() if packed else None, 4 * (-(-din // 64)),
-                                       int(self.code == nat.F32), 0))
+                self._prep_descs.append(_PrepDesc(
+                    prm.data_ptr(), w2[g].data_ptr() if (not packed or tail_level) else None,
+                    w2t[g].data_ptr() if w2t is not None else None, h, din, w2.shape[2],
+                    w2t.shape[2] if w2t is not None else 0, wp[g * gstride:].data_ptr() if packed else None,
+                    4 * (-(-din // 64)), int(self.code == nat.F32), 0))
         if self.emb:
-            def copies(prm, need_t):                              # operand copies of prep.fc.weight
-                r, c = prm.shape
-                w = torch.zeros(r, _r8(c), dtype=self.tdt, device=dev)
-                wt = torch.zeros(c, _r8(r), dtype=self.tdt, device=dev) if need_t else None
-                descs.append(_PrepDesc(prm.data_ptr(), w.data_ptr(), wt.data_ptr() if need_t else None, r, c,
-                                       w.shape[1], wt.shape[1] if need_t else 0, None, 0, int(self.code == nat.F32), 0))
-                return w, wt
-            self._init_emb(copies)
-        raw = bytes((_PrepDesc * len(descs))(*descs))
-        self.descs = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
-        self.n_desc = len(descs)
-        self.max_elems = max(d.rows * d.cols for d in descs)
+            self._init_emb()
 
         bf, f32 = self.tdt, torch.float32
         # per-batch inputs of the compute stage, one set per batch in flight:
@@ -154,7 +142,6 @@ class FusedMeanTrainStep(FusedTrainStep):
         GSAGE_TAIL_MFMA=0: the 4-seeds-per-workgroup VALU kernel (gsage_mean_tail_ce; the fp32 parity mode's)."""
         return self.code == nat.BF16 and os.environ.get("GSAGE_TAIL_MFMA", "1") == "1"
 
-
     def _init_reduce(self):
         """Gradient partial buffers + the descriptor table gsage_finalize_grads sums them with: levels 0 .. L-1
         (fc_x's slab, covering fc_neib too where the level is one grouped problem, else fc_x's and fc_neib's),
@@ -173,7 +160,7 @@ class FusedMeanTrainStep(FusedTrainStep):
             xbuf, lda = (self.xa0_set[s][0], self.ldin[0]) if l == 0 else (self.hout[l - 1], din)
             rows = None
             if l == 0 and self.inplace_x:
-                xbuf, rows = self.store.data, (self._q_ids if self._q_ids is not None else self.ids_set[s])
+                xbuf, rows = self.store.data, self._front
             aggl = self.xa0_set[s][1] if l == 0 else self.agg[l]
             if h % 128 == 0:
                 delta = (aggl.data_ptr() - xbuf.data_ptr()) // self.esz
@@ -236,7 +223,6 @@ class FusedMeanTrainStep(FusedTrainStep):
         stream = ops._stream()
         esz = self.esz
         if self.emb:
-            self._cur_ids = self._q_ids if self._q_ids is not None else self.ids_set[s]
             self._prep_forward(s)
         for l in range(L - 1 if self.fused_tail else L):
             R, h, din = self.rows[l], self.h[l], self.din[l]
@@ -249,7 +235,7 @@ class FusedMeanTrainStep(FusedTrainStep):
                 ops.gather_mean_multi(segs, ld0, din, ld0)
             elif l == 0 and self.inplace_x:      # the x rows of every hop, read in place through the frontier
                 xbuf, agg, lda = st.data, self.xa0_set[s][1], st.ld
-                rows = (self._q_ids if self._q_ids is not None else self.ids_set[s]).data_ptr()
+                rows = self._front.data_ptr()
             elif l == 0:
                 xbuf, agg, lda = self.xa0_set[s][0], self.xa0_set[s][1], st.ld
             else:
@@ -261,7 +247,7 @@ class FusedMeanTrainStep(FusedTrainStep):
             assert delta % esz == 0 and agg.stride(0) == lda
             last = l == L - 1
             if self.wp[l] is not None:
-                if l == 0 and getattr(self, "_k5_hops", None) is not None and self._k1_in_k5():
+                if l == 0 and self._k5_hops is not None and self._k1_in_k5():
                     # the projection's spare workgroup slots sample the frontier of the batch after the next
                     nat.check(lib.gsage_hops_role_next(ctypes.addressof(self._k5_hops)), "hops_role_next")
                 if l == 0:
@@ -290,7 +276,7 @@ class FusedMeanTrainStep(FusedTrainStep):
                     self.dc[L - 2].data_ptr(), self.head_scratch.data_ptr(),
                     ctypes.addressof(self._tail_gather) if self._tail_gather is not None else None)
             if self._tail_on_mfma():
-                if getattr(self, "_k5_hops", None) is not None and self._tail_gather is not None and self._k1_in_tail():
+                if self._k5_hops is not None and self._tail_gather is not None and self._k1_in_tail():
                     # workgroups behind the seed-level ones sample the frontier of the batch after the next
                     nat.check(lib.gsage_hops_role_next(ctypes.addressof(self._k5_hops)), "hops_role_next")
                 nat.check(lib.gsage_mean_tail_mfma(*args, stream), "mean_tail_mfma")
@@ -349,7 +335,7 @@ class FusedMeanTrainStep(FusedTrainStep):
         step: every sampled frontier row is read exactly once, by one of the two."""
         total = self.off[self.L + 1]
         tail = self._tail_rows * self.fan[self.L]
-        if getattr(self, "inplace_x", False):          # K5 / K5b read the x rows themselves
+        if self.inplace_x:                             # K5 / K5b read the x rows themselves
             total -= self.rows[0]
         return total - tail, tail
 
@@ -424,7 +410,7 @@ class FusedMeanTrainStep(FusedTrainStep):
         own chain) and the projection 2.8 us longer (14.0 -> 16.8: the sampler's 171 workgroups hold slots its 416
         want) -- 0.0846 against 0.0835 ms/step.  Needs the packed ReLU projection at level 0, a CSR sampler, one GPU;
         a ring of three frontier buffers (K5 / K5b of step i still read batch i's as their row list)."""
-        if getattr(self, "_k1_where", None) is not None:      # (decided in load_epoch)
+        if self._k1_where is not None:                        # (decided in load_epoch)
             return self._k1_where == "k5"
         return bool(self.wp and self.wp[0] is not None and self.L >= 2 and not self.dense and not self.emb and
                     self.ddp is None and os.environ.get("GSAGE_K1_IN_K5", "0") == "1")
@@ -435,7 +421,7 @@ class FusedMeanTrainStep(FusedTrainStep):
         gather role (~31 us at config 2) whatever else rides in it; K1's chain of dependent loads was the longer of the
         last launch's two.  Needs the matrix-core seed level with a gather role, a CSR sampler, one GPU; a ring of three
         frontier buffers as for _k1_in_k5.  GSAGE_K1_IN_TAIL=0: K1 stays in the launch that carries the update."""
-        if getattr(self, "_k1_where", None) is not None:      # (decided in load_epoch)
+        if self._k1_where is not None:                        # (decided in load_epoch)
             return self._k1_where == "tail"
         return bool(self.fused_tail and self._tail_on_mfma() and self.L >= 2 and not self.dense and not self.emb and
                     self.ddp is None and self.fan[self.L] in (5, 10, 15) and not self._k1_in_k5() and

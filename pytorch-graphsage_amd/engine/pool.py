@@ -9,7 +9,7 @@ import torch
 from .. import _native as nat
 from .. import ops
 from ..nn_modules import IdentityPrep, MaxPoolAggregator, MeanPoolAggregator, NodeEmbeddingPrep
-from .common import FusedTrainStep, _PrepDesc, _ReduceDesc, _Wgrad, _r8, _r64
+from .common import FusedTrainStep, _ReduceDesc, _Wgrad, _round64
 
 
 class FusedPoolTrainStep(FusedTrainStep):
@@ -37,6 +37,7 @@ class FusedPoolTrainStep(FusedTrainStep):
     """
 
     NPART = 256          # partial rows per hop for the MLP bias gradient (summed by the finalisation)
+    FRAG_COPIES = True   # every refresh descriptor carries the fragment geometry (kc_p), those without such a copy too
     TIMED = {"gather": (0, 1), "k3": (4, 5), "k5b": (6, 7)}      # K3 = level 0's launch over the LAST hop (the bulk)
 
     @classmethod
@@ -69,7 +70,7 @@ class FusedPoolTrainStep(FusedTrainStep):
         self.Hm = [int(l.mlp[0].weight.shape[0]) for l in self.layers]
         if self.emb:                                 # level-0 rows = [features |] prep.fc(embedding[ids])
             d0 = self.D0 + self.E
-            ld0 = _r64(d0) if is_bf else _r8(d0)
+            ld0 = _round64(d0)
         else:
             d0, ld0 = feats.dim, feats.ld
         self.din = [d0] + [2 * h for h in self.h[:-1]]
@@ -77,20 +78,7 @@ class FusedPoolTrainStep(FusedTrainStep):
         self.rows = [self.off[L - l] for l in range(L)]                     # x rows of level l
         self.nrows = [self.off[L - l + 1] - self.off[1] for l in range(L)]  # neighbour rows of level l
         assert all(d % 64 == 0 for d in self.din[1:]), "hidden widths must be multiples of 32"
-        descs = []
-
-        def copies(prm, need_t, packed=False):
-            r, c = prm.shape
-            w = torch.zeros(r, _r64(c), dtype=bf, device=dev)
-            wt = torch.zeros(c, _r64(r), dtype=bf, device=dev) if need_t else None
-            # forward operands of K3 / K5 also in MFMA fragment order (gsage_*_packed)
-            wp = (torch.zeros(nat.lib().gsage_packed_weight_elems(r, c, 1), dtype=bf, device=dev)
-                  if packed and is_bf else None)
-            descs.append(_PrepDesc(prm.data_ptr(), w.data_ptr(), wt.data_ptr() if need_t else None, r, c,
-                                   w.shape[1], wt.shape[1] if need_t else 0,
-                                   wp.data_ptr() if wp is not None else None, 4 * (-(-c // 64)),
-                                   int(not is_bf), 0))
-            return (w, wt, wp) if packed else (w, wt)
+        copies = self._operand_copies    # (forward operands of K3 / K5 also in MFMA fragment order: packed)
         self.wm, self.wx, self.wn, self.wmT, self.wxT, self.wnT = [], [], [], [], [], []
         self.wm_p, self.wx_p, self.wn_p = [], [], []
         for l, layer in enumerate(self.layers):
@@ -105,10 +93,7 @@ class FusedPoolTrainStep(FusedTrainStep):
             self.wn.append(wn); self.wnT.append(wnT)
             self.wm_p.append(wm_p); self.wx_p.append(wx_p); self.wn_p.append(wn_p)
         if self.emb:
-            self._init_emb(lambda prm, need_t: copies(prm, need_t))
-        self.descs = torch.frombuffer(bytearray(bytes((_PrepDesc * len(descs))(*descs))), dtype=torch.uint8).to(dev)
-        self.n_desc = len(descs)
-        self.max_elems = max(d.rows * d.cols for d in descs)
+            self._init_emb()
 
         # level-0 operands: x rows (hops 0..L-1) gathered once per step; the neighbour rows (hops 1..L: 141 k rows,
         # 180 MB at Reddit's shape) are read IN PLACE through the frontier's row list by K3 and by K5b
@@ -123,7 +108,6 @@ class FusedPoolTrainStep(FusedTrainStep):
             self.x0_set = [torch.zeros(self.rows[0], feats.ld, dtype=bf, device=dev) for _ in range(self.nset)]
             self.xn0_set = [None if self.inplace0 else torch.zeros(self.nrows[0], feats.ld, dtype=bf, device=dev)
                             for _ in range(self.nset)]
-        self._q_ids = None
         self.pooled, self.pooled_b, self.argmax, self.hout, self.dc = [], [], [], [], []
         self.dpool, self.ghc, self.dxb, self.dnb, self.bpart = [], [], [], [], []
         for l in range(L):
@@ -132,7 +116,7 @@ class FusedPoolTrainStep(FusedTrainStep):
             self.pooled.append(torch.zeros(R, Hm, dtype=f32, device=dev))
             # operand copy of `pooled` for the fc_neib projection and its weight gradient (parity mode:
             # the fp32 result itself)
-            self.pooled_b.append(torch.zeros(R, _r64(Hm), dtype=bf, device=dev) if is_bf else self.pooled[l])
+            self.pooled_b.append(torch.zeros(R, _round64(Hm), dtype=bf, device=dev) if is_bf else self.pooled[l])
             # what the backward needs of the hidden layer: the winning row (max) / the ReLU sign bits (mean)
             self.argmax.append(torch.zeros(R, Hm, dtype=i32, device=dev) if self.pool_mode == nat.POOL_MAX
                                else torch.zeros(NR, Hm // 32, dtype=i32, device=dev))
@@ -162,9 +146,8 @@ class FusedPoolTrainStep(FusedTrainStep):
         if l == 0 and self.emb:
             return self.g0_set[s][self.off[1]:], self.ldin[0], None
         if l == 0:
-            if self.inplace0:       # the frontier of the batch being computed: the queue's, else the set's own
-                ids = self._q_ids if self._q_ids is not None else self.ids_set[s]
-                return self.store.data, self.store.ld, ids[self.off[1]:]
+            if self.inplace0:
+                return self.store.data, self.store.ld, self._front[self.off[1]:]
             return self.xn0_set[s], self.store.ld, None
         return self.hout[l - 1][self.off[1]:], self.din[l], None
 
@@ -236,7 +219,6 @@ class FusedPoolTrainStep(FusedTrainStep):
     def _stage_compute(self, s):
         L, B, lib, stream, m = self.L, self.B, nat.lib(), ops._stream(), self.model
         if self.emb:
-            self._cur_ids = self._q_ids if self._q_ids is not None else self.ids_set[s]
             self._prep_forward(s)
         for l, layer in enumerate(self.layers):
             R, Hm, h, din = self.rows[l], self.Hm[l], self.h[l], self.din[l]
