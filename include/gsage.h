@@ -565,6 +565,29 @@ int gsage_prep_rows_bwd(const void *dhid, int64_t lddh, const void *W0T, int64_t
                         int64_t n_seed, int64_t spare, float *g_table, int64_t ldg, float *deraw, int64_t ldde,
                         void *stream);
 
+/* The recurrence of the LSTM aggregator and its backward (csrc/gsage_lstm.hip; reference nn_modules.py:259-286 keeps the
+ * LAST position of a batch_first LSTM over each node's n neighbour rows, and its autograd).  Gate order i, f, g, o;
+ * `dtype` is the compute type of the gates, of the packed weights, of h and of dG (bf16: v_mfma_f32_32x32x16_bf16; fp32:
+ * v_mfma_f32_32x32x2_f32); c and all gate arithmetic are fp32.  gsage_lstm_ok says whether a shape is covered (1 / 0; no
+ * GPU needed): 1 <= n <= 128, 1 <= H <= 1024 (bf16) / 512 (fp32).  Sequence m, step t is row m n + t of every [M n, .] array.
+ *   gsage_lstm_pack_whh   W_hh (fp32 [4 H, ldw]) -> both fragment-ordered copies, gsage_lstm_packed_elems(H) elements of
+ *                         `dtype` (16-byte aligned): the forward copy first, the backward copy in the second half
+ *   gsage_lstm_fwd        gates: GX = rows W_ih^T + b_ih + b_hh on entry (K5), the activated gates on exit (column g H + u);
+ *                         cseq[m n + t] = c_t (fp32 [M n, H]); hprev[m n + t + 1] = h_t for t < n - 1 -- row m n + t is
+ *                         the step's INPUT state, rows m n + 0 are the caller's (zero); out[m] = h_{n-1}.
+ *                         n == 1 (a zero initial state, no recurrent term): Wp and hprev may be NULL
+ *   gsage_lstm_bwd        dh: gradient of out (fp32 [M, lddh]); dG[m n + t] = gradient of step t's pre-activation gates,
+ *                         from which d W_ih, d W_hh (= dG^T hprev), the biases (column sums) and d rows (= dG W_ih) follow
+ *                         on K5b / K5.  Wp: the BACKWARD copy (second half of gsage_lstm_pack_whh's output); carry: fp32 [M, 2 H]
+ *                         scratch (dh_t and dc_t f_t between two steps; may be NULL when n == 1) */
+int gsage_lstm_ok(int dtype, int64_t H, int32_t n);
+int64_t gsage_lstm_packed_elems(int64_t H);
+int gsage_lstm_pack_whh(const float *W_hh, int64_t ldw, int64_t H, int dtype, void *Wp, void *stream);
+int gsage_lstm_fwd(void *gates, int dtype, int64_t ldg, const void *Wp, int64_t M, int32_t n, int64_t H, float *cseq,
+                   void *hprev, int64_t ldh, void *out, int64_t ldo, void *stream);
+int gsage_lstm_bwd(const void *gates, int dtype, int64_t ldg, const void *Wp, int64_t M, int32_t n, int64_t H,
+                   const float *cseq, const float *dh, int64_t lddh, void *dG, int64_t lddg, float *carry, void *stream);
+
 /* Glue of the native attention train step (engine.FusedAttnTrainStep): what autograd ran as separate cast /
  * add / tanh-backward / expand kernels between K4, K5 and K5b.
  *   gsage_add_cast        dst[m, c] = T(a[m, c] + (b ? b[m, c] : 0))             (fp32 in, bf16 / fp32 out)

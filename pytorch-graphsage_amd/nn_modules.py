@@ -12,6 +12,8 @@ calls into ops.py (C ABI of libgsage_hip.so).  What differs on purpose:
     rng="compat" draws `sel` from numpy's global legacy stream exactly like nn_modules.py:88
     (bit-identical samples for the same seed); rng="philox" draws it in-kernel (counter based).
 """
+import sys
+
 import numpy as np
 import torch
 from torch import nn
@@ -339,8 +341,14 @@ class MeanPoolAggregator(PoolAggregator):
 
 
 class LSTMAggregator(nn.Module, AggregatorMixin):
-    """nn_modules.py:259-286.  Not on the north-star path: the
-    recurrence runs on the stock torch/MIOpen LSTM, only the projection uses K5."""
+    """nn_modules.py:259-286: the output of a batch_first LSTM over each node's neighbour rows at the LAST position,
+    then the concat projection.  On CUDA the recurrence and its backward run on this library's kernels
+    (ops.lstm_last: K5 input projection with the neighbour gather fused for a RowRef, gsage_lstm_fwd / _bwd, K5b / K5
+    for the gradients) in either compute mode; the reverse direction of a bidirectional LSTM is ONE cell evaluation on
+    the last neighbour, which is all the reference's `[:, -1, :]` keeps of it.  `self.lstm` stays an nn.LSTM: it owns
+    the parameters (state_dict keys, initialisation) and is what host mode (CPU tensors) calls."""
+
+    _told = set()
 
     def __init__(self, input_dim, output_dim, activation, hidden_dim=512, bidirectional=False,
                  combine_fn=concat_combine):
@@ -354,7 +362,27 @@ class LSTMAggregator(nn.Module, AggregatorMixin):
         self.activation = activation
         self.combine_fn = combine_fn
 
+    def _why_stock(self, n):
+        """None when the recurrence kernels take this shape, else the reason (said once per reason on stderr)."""
+        H = self.lstm.hidden_size
+        if ops.lstm_ok(H, n):
+            return None
+        why = ("LSTMAggregator: %d hidden units per direction over %d neighbours in %s mode is outside what "
+               "gsage_lstm_ok covers (1..128 steps, up to 1024 units in bf16 / 512 in fp32); this call runs on "
+               "torch.nn.LSTM instead" % (H, n, ops.config.compute_dtype))
+        if why not in LSTMAggregator._told:
+            LSTMAggregator._told.add(why)
+            sys.stderr.write(why + "\n")
+        return why
+
     def forward(self, x, neibs):
+        M = x.size(0)
+        if neibs.is_cuda and self._why_stock(neibs.size(0) // M) is None:
+            l = self.lstm
+            rev = (l.weight_ih_l0_reverse, l.weight_hh_l0_reverse, l.bias_ih_l0_reverse,
+                   l.bias_hh_l0_reverse) if l.bidirectional else None
+            agg = ops.lstm_last(neibs, M, l.weight_ih_l0, l.weight_hh_l0, l.bias_ih_l0, l.bias_hh_l0, rev)
+            return self._project(x, agg)
         xt, nt = _as_tensor(x).float(), _as_tensor(neibs).float()
         seq, _ = self.lstm(nt.view(xt.size(0), -1, nt.size(1)))
         return self._project(xt, seq[:, -1, :].contiguous())

@@ -881,3 +881,150 @@ def attn_aggregate(na, xa, neibs, M):
     if isinstance(neibs, RowRef):
         return _AttnAggregate.apply(na, xa, None, neibs.store.data, neibs.ids, neibs.store.dim, M, n)
     return _AttnAggregate.apply(na, xa, neibs, None, None, 0, M, n)
+
+
+# =============================================================================================
+# LSTM aggregator: last position of a batch_first LSTM over each node's neighbour rows
+# =============================================================================================
+def lstm_ok(H, n, compute_dtype=None):
+    """Whether the recurrence kernels take a direction of H hidden units over n steps (gsage_lstm_ok)."""
+    return bool(nat.lib().gsage_lstm_ok(_code(torch_dtype(compute_dtype)), int(H), int(n)))
+
+
+def _lstm_pack_whh(w_hh, cdt):
+    """weight_hh [4H, H] -> both fragment-ordered operand copies (forward half, backward half) in the compute type."""
+    H = int(w_hh.shape[1])
+    w = w_hh.detach().float().contiguous()
+    wp = torch.empty(int(nat.lib().gsage_lstm_packed_elems(H)), dtype=cdt, device=w.device)
+    nat.check(nat.lib().gsage_lstm_pack_whh(_ptr(w), w.stride(0), H, _code(cdt), _ptr(wp), _stream()), "lstm_pack_whh")
+    return wp
+
+
+def _off(t, elems):
+    return _vp(t.data_ptr() + elems * t.element_size())
+
+
+class _LSTMLast(torch.autograd.Function):
+    """seq, _ = lstm(neibs.view(M, n, D)); seq[:, -1, :] (nn_modules.py:278-279) without the sequence: the forward
+    direction's final h, and for a bidirectional LSTM the reverse direction's FIRST step -- one cell evaluation on the
+    last neighbour from a zero state.  Input projection on K5 (gather fused for a RowRef), recurrence on
+    gsage_lstm_fwd / _bwd, weight and input gradients on K5b / K5 over the dG the backward recurrence writes.
+    Reserve per direction: activated gates (over GX, compute type), c (fp32) and the steps' input states."""
+
+    @staticmethod
+    def forward(ctx, neibs, table, ids, dim, M, n, cdt_name, w_ih, w_hh, b_ih, b_hh, rw_ih, rw_hh, rb_ih, rb_hh):
+        cdt = torch_dtype(cdt_name)
+        epc = 8 if cdt == torch.bfloat16 else 4
+        code = _code(cdt)
+        L = nat.lib()
+        H = int(w_hh.shape[1])
+        Hr = int(rw_hh.shape[1]) if rw_ih is not None else 0
+        if ids is not None:
+            K = dim
+            if table.dtype != cdt or table.stride(0) % epc != 0:
+                A = _gather_mean_raw(table, K, ids, M * n, 1, cdt, _round_up(K, epc))
+                a_rows = None
+            else:
+                A, a_rows = table, ids
+        else:
+            K = neibs.shape[1]
+            A, a_rows = _pad_cast(neibs.detach(), cdt, epc, _trusted(neibs)), None
+        dev = A.device
+        out = torch.empty(M, H + Hr, dtype=cdt, device=dev)
+
+        def project(w, b1, b2, rows, a_ptr, lda, r_ids):
+            wa = _prep_weight(w, cdt, epc)
+            bias = (b1.detach().float() + b2.detach().float()).contiguous()
+            N = int(w.shape[0])
+            ldg = _round_up(N, epc)
+            gates = (torch.zeros if ldg != N else torch.empty)(rows, ldg, dtype=cdt, device=dev)
+            _linear_launch(a_ptr, lda, _ptr(r_ids), 0, _ptr(wa), wa.stride(0), _ptr(bias), _ptr(gates), ldg, rows, N, K,
+                           nat.ACT_NONE, 1, 0, 0, 0, code, code)
+            return wa, gates, bias
+
+        wa, gates, bias = project(w_ih, b_ih, b_hh, M * n, _ptr(A), A.stride(0), a_rows)
+        wp = _lstm_pack_whh(w_hh, cdt) if n > 1 else None
+        cseq = torch.empty(M * n, H, dtype=torch.float32, device=dev)
+        ldh = _round_up(H, epc)
+        hprev = torch.zeros(M * n, ldh, dtype=cdt, device=dev) if n > 1 else None
+        nat.check(L.gsage_lstm_fwd(_ptr(gates), code, gates.stride(0), _ptr(wp), M, n, H, _ptr(cseq), _ptr(hprev), ldh,
+                                   _ptr(out), H + Hr, _stream()), "lstm_fwd")
+        rwa = rgates = rcseq = r_ids = rbias = None
+        if Hr:
+            # the reverse direction's output at the last position is its first step: project the last neighbour only
+            if a_rows is not None:
+                r_ids = a_rows.view(M, n)[:, n - 1].contiguous()
+                rwa, rgates, rbias = project(rw_ih, rb_ih, rb_hh, M, _ptr(A), A.stride(0), r_ids)
+            else:
+                rwa, rgates, rbias = project(rw_ih, rb_ih, rb_hh, M, _off(A, (n - 1) * A.stride(0)), n * A.stride(0),
+                                             None)
+            rcseq = torch.empty(M, Hr, dtype=torch.float32, device=dev)
+            nat.check(L.gsage_lstm_fwd(_ptr(rgates), code, rgates.stride(0), None, M, 1, Hr, _ptr(rcseq), None, 0,
+                                       _off(out, H), H + Hr, _stream()), "lstm_fwd (reverse)")
+        # (the summed biases are kept too: a recorded forward reads every operand again at each replay)
+        ctx.save_for_backward(A, a_rows, r_ids, wa, wp, gates, cseq, hprev, rwa, rgates, rcseq, bias, rbias)
+        ctx.meta = (M, n, H, Hr, K, cdt, epc, neibs.dtype if neibs is not None else None, w_ih.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        A, a_rows, r_ids, wa, wp, gates, cseq, hprev, rwa, rgates, rcseq = ctx.saved_tensors[:11]
+        M, n, H, Hr, K, cdt, epc, ndt, wdt = ctx.meta
+        L = nat.lib()
+        code = _code(cdt)
+        dev = g.device
+        g = g.float().contiguous()
+        need = ctx.needs_input_grad
+        ldg = gates.stride(0)
+        dG = (torch.zeros if ldg != 4 * H else torch.empty)(M * n, ldg, dtype=cdt, device=dev)
+        carry = torch.empty(M, 2 * H, dtype=torch.float32, device=dev) if n > 1 else None
+        Hp = _round_up(H, 32)
+        nat.check(L.gsage_lstm_bwd(_ptr(gates), code, ldg, _off(wp, 4 * Hp * Hp) if wp is not None else None, M, n, H,
+                                   _ptr(cseq), _ptr(g), H + Hr, _ptr(dG), ldg, _ptr(carry), _stream()), "lstm_bwd")
+        ones = torch.ones(M * n, epc, dtype=cdt, device=dev)          # bias gradient = dG^T 1 on K5b
+
+        def params(dg, rows, n_out, hp):
+            dw_ih = _wgrad_any(dg, rows, K)[:n_out].to(wdt) if rows is not None else None
+            dw_hh = _wgrad_any(dg, hp, n_out // 4)[:n_out].to(wdt) if hp is not None else None
+            db = _wgrad_any(dg, ones[:dg.shape[0]], 1)[:n_out, 0].to(wdt).contiguous()
+            return dw_ih, dw_hh, db
+
+        rows = None
+        if need[7]:           # the rows in storage precision, as the forward's projection read them
+            rows = A if a_rows is None else _gather_mean_raw(A, K, a_rows, M * n, 1, cdt, _round_up(K, epc))
+        dw_ih, dw_hh, db = params(dG, rows, 4 * H, hprev)
+        if dw_hh is None:
+            dw_hh = torch.zeros(4 * H, H, dtype=wdt, device=dev)     # n == 1: no recurrent term
+        dn = None
+        if need[0]:
+            dn = _dgrad(dG[:, :4 * H], wa, K)
+        rdw_ih = rdw_hh = rdb = None
+        if Hr:
+            ldr = rgates.stride(0)
+            rdG = (torch.zeros if ldr != 4 * Hr else torch.empty)(M, ldr, dtype=cdt, device=dev)
+            nat.check(L.gsage_lstm_bwd(_ptr(rgates), code, ldr, None, M, 1, Hr, _ptr(rcseq), _off(g, H), H + Hr,
+                                       _ptr(rdG), ldr, None, _stream()), "lstm_bwd (reverse)")
+            rrows = None
+            if need[11]:
+                rrows = A[n - 1::n] if a_rows is None else _gather_mean_raw(A, K, r_ids, M, 1, cdt, _round_up(K, epc))
+            rdw_ih, _, rdb = params(rdG, rrows, 4 * Hr, None)
+            rdw_hh = torch.zeros(4 * Hr, Hr, dtype=wdt, device=dev)  # its one step starts from a zero state
+            if dn is not None:
+                dn.view(M, n, K)[:, n - 1, :] += _dgrad(rdG[:, :4 * Hr], rwa, K)
+        if dn is not None:
+            dn = dn.to(ndt)
+        return (dn, None, None, None, None, None, None, dw_ih, dw_hh, db, db, rdw_ih, rdw_hh, rdb, rdb)
+
+
+def lstm_last(neibs, M, w_ih, w_hh, b_ih, b_hh, reverse=None, compute_dtype=None):
+    """neibs: Tensor [M*n, D] or RowRef; (w_ih, w_hh, b_ih, b_hh): one nn.LSTM direction; reverse: the four parameters
+    of the reverse direction or None.  Returns [M, hidden_dim] in the compute type: the LSTM's output at the LAST
+    position, the two directions side by side.  CUDA only (host mode keeps nn.LSTM, nn_modules.LSTMAggregator)."""
+    total = neibs.shape[0]
+    assert total % M == 0 and neibs.is_cuda
+    n = total // M
+    cd = compute_dtype or config.compute_dtype
+    rev = tuple(reverse) if reverse is not None else (None, None, None, None)
+    if isinstance(neibs, RowRef):
+        return _LSTMLast.apply(None, neibs.store.data, neibs.ids, neibs.store.dim, M, n, cd, w_ih, w_hh, b_ih, b_hh, *rev)
+    return _LSTMLast.apply(neibs, None, None, 0, M, n, cd, w_ih, w_hh, b_ih, b_hh, *rev)
