@@ -18,7 +18,8 @@
  *   - Return value: 0 on success, a negative GSAGE_E* code otherwise; gsage_last_error()
  *     returns a thread-local message.  Asynchronous data errors (an id outside the graph) are
  *     reported through the caller-supplied `err_flag` device word (0 = ok).
- *   - dtype codes: GSAGE_F32 / GSAGE_BF16 (bf16 = upper 16 bits of an IEEE fp32, RNE).
+ *   - dtype codes: GSAGE_F32 / GSAGE_BF16 (bf16 = upper 16 bits of an IEEE fp32, RNE).  GSAGE_FP8 names the storage
+ *     format of a quantised feature table ("FP8 feature table" below); only the *_fp8 entry points take it.
  *   - Graph layout ("device CSR", built once from the reference's scipy csr_matrix in the
  *     (v,r,c) convention of problem.py:70-72 / utils/convert.py:100-126):
  *         rowptr int64 [n_rows+1]   rowptr[i+1]-rowptr[i] = degree of node i
@@ -38,7 +39,7 @@ extern "C" {
 
 #define GSAGE_ABI_VERSION 6
 
-enum { GSAGE_F32 = 0, GSAGE_BF16 = 1 };
+enum { GSAGE_F32 = 0, GSAGE_BF16 = 1, GSAGE_FP8 = 2 };
 enum {
     GSAGE_OK = 0,
     GSAGE_EINVAL = -1,   /* bad argument (null pointer, bad size / alignment / dtype) */
@@ -324,6 +325,41 @@ int gsage_gather_mean(const void *table, int dtype, int64_t ld, const int64_t *i
 int gsage_gather_mean_multi(int32_t n_seg, const void *const *tables, const int64_t *const *ids,
                             void *const *outs, const int64_t *M, const int32_t *n, int dtype,
                             int64_t ld, int64_t D, int out_dtype, int64_t out_ld, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * FP8 feature table (opt-in storage of a fixed input-feature table; additive, ABI version unchanged)
+ *
+ *     table_q[r, c]  one OCP e4m3fn byte (gfx950's hardware format, not MI300X's fnuz), rows of ld_q bytes,
+ *                    ld_q % 16 == 0 (store.FeatureStore pads rows to 128 bytes), bytes of columns >= D zero
+ *     scale[c]       fp32 [ld_q], 16-byte aligned: an exact power of two, 1.0 for an all-zero or padding column
+ *     value          e4m3(table_q[r, c]) * scale[c]  -- exactly representable in bf16
+ *
+ * gsage_quantize_fp8: scale[c] = the smallest power of two s (2^-126 <= s) with max_r |x[r, c]| / s <= 448;
+ * table_q[r, c] = x[r, c] / s rounded to e4m3fn, round-to-nearest-even, saturating at +-448 (never a NaN
+ * encoding; a NaN input counts as 0, one beyond +-2^127 as +-2^127, so every decoded value is finite).  Two passes over x: the column maxima
+ * (integer atomic max of |x| bits: order-independent, hence deterministic), then the encoding.  dtype = type of
+ * x (GSAGE_F32 / GSAGE_BF16), ld its leading dimension in elements.  A one-off: `scale` is cleared by a memset on
+ * the stream, so the call is not for recording into a command list.
+ * ---------------------------------------------------------------------------------------- */
+int gsage_quantize_fp8(const void *table, int dtype, int64_t ld, int64_t n_rows, int64_t D, void *table_q,
+                       int64_t ld_q, float *scale, void *stream);
+
+/* out[i, :] = decode(table_q[ids[i], :]) as bf16 or fp32: the FP8 form of the n == 1 row gather. */
+int gsage_gather_rows_fp8(const void *table_q, int64_t ld, const float *scale, const int64_t *ids, int64_t M,
+                          int64_t D, void *out, int out_dtype, int64_t out_ld, void *stream);
+
+/* gsage_gather_mean / gsage_gather_mean_multi on an FP8 table: 16-byte chunks (16 columns) per lane, fp32
+ * accumulation of the UNSCALED e4m3 values in neighbour order, scale[c] applied once per output element before
+ * the division by n.  Scaling by a power of two commutes with fp32 rounding, so the result equals, bit for bit,
+ * gsage_gather_mean on a bf16 table that holds the decoded values.  out_dtype: GSAGE_BF16 or GSAGE_F32; same
+ * output layout, columns [D, round_up(D, 16 bytes of out)) written as zero.  The multi form needs 16-byte
+ * aligned outputs whose out_ld is a whole number of 16-byte pieces; the single form falls back to element
+ * stores (columns < D only) for any other output. */
+int gsage_gather_mean_fp8(const void *table_q, int64_t ld, const float *scale, const int64_t *ids, int64_t M,
+                          int32_t n, int64_t D, void *out, int out_dtype, int64_t out_ld, void *stream);
+int gsage_gather_mean_multi_fp8(int32_t n_seg, const void *const *tables_q, const int64_t *const *ids,
+                                void *const *outs, const int64_t *M, const int32_t *n, const float *scale,
+                                int64_t ld, int64_t D, int out_dtype, int64_t out_ld, void *stream);
 
 /* Backward of the segment mean w.r.t. contiguous neighbour rows (autograd of nn_modules.py:198):
  *     dneibs[i*n+j, c] = dagg[i, c] / n          (fp32 in, fp32 out) */

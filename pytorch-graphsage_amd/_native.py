@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgsage_hip.so")
 
-F32, BF16 = 0, 1
+F32, BF16, FP8 = 0, 1, 2
 POOL_MAX, POOL_MEAN = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 SEG_MEAN, SEG_MAX, SEG_SOFTMAX_WEIGHTED = 0, 1, 2
@@ -88,6 +88,10 @@ SIGNATURES = {
     "gsage_gather_mean_multi": (_int, [_i32, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _int, _i64, _vp]),
     "gsage_gather_mean_multi_adam": (_int, [_i32, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _int, _i64,
                                             _vp, _vp, _vp]),
+    "gsage_quantize_fp8": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "gsage_gather_rows_fp8": (_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _int, _i64, _vp]),
+    "gsage_gather_mean_fp8": (_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i64, _vp, _int, _i64, _vp]),
+    "gsage_gather_mean_multi_fp8": (_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _i64, _vp]),
     "gsage_segment_mean_bwd": (_int, [_vp, _i64, _i64, _i32, _i64, _vp, _i64, _vp]),
     "gsage_scatter_add_rows": (_int, [_vp, _i64, _vp, _i64, _i32, _i64, _f32, _vp, _i64, _vp]),
     "gsage_linear_nt": (_int, [_vp, _int, _i64, _vp, _int, _vp, _i64, _vp, _vp, _int, _i64, _i64,

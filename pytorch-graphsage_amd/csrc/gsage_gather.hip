@@ -26,7 +26,7 @@ struct chunk_io;
 template <int VEC>
 struct chunk_io<uint16_t, VEC> {
     static constexpr int kWords = (VEC * 2 + 3) / 4;
-    struct __attribute__((aligned(VEC * 2))) raw { uint16_t h[VEC]; };
+    struct __attribute__((aligned(VEC * 2 > 16 ? 16 : VEC * 2))) raw { uint16_t h[VEC]; };
     __device__ static __forceinline__ void accumulate(const raw &r, float (&acc)[VEC])
     {
 #pragma unroll
@@ -43,7 +43,7 @@ struct chunk_io<uint16_t, VEC> {
 
 template <int VEC>
 struct chunk_io<float, VEC> {
-    struct __attribute__((aligned(VEC * 4))) raw { float h[VEC]; };
+    struct __attribute__((aligned(VEC * 4 > 16 ? 16 : VEC * 4))) raw { float h[VEC]; };
     __device__ static __forceinline__ void accumulate(const raw &r, float (&acc)[VEC])
     {
 #pragma unroll
@@ -58,19 +58,67 @@ struct chunk_io<float, VEC> {
     }
 };
 
+// FP8 storage (GSAGE_FP8): one OCP e4m3fn byte per element, 16 columns per 16-byte chunk, decoded by the hardware
+// conversion.  The decoded values are the UNSCALED e4m3 numbers: gather_mean_chunk multiplies the neighbour sum by the
+// column's power-of-two scale once per output element -- (sum_j q_j) * s == sum_j (q_j * s) bit for bit in fp32, which
+// is what the bf16 kernel computes on a bf16 table of the decoded values (every q * s is exact in bf16).
+struct fp8_t { uint8_t b; };
+
+template <>
+struct chunk_io<fp8_t, 16> {
+    struct __attribute__((aligned(16))) raw { uint32_t w[4]; };
+    __device__ static __forceinline__ void accumulate(const raw &r, float (&acc)[16])
+    {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)r.w[k], false);    // bytes 0, 1
+            const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)r.w[k], true);     // bytes 2, 3
+            acc[4 * k + 0] += lo[0];
+            acc[4 * k + 1] += lo[1];
+            acc[4 * k + 2] += hi[0];
+            acc[4 * k + 3] += hi[1];
+        }
+    }
+};
+
+// The 16 results of an FP8 chunk leave as 16-byte pieces (two of bf16, four of fp32): a piece is written when its first
+// column is below D, which is exactly the range the bf16 / fp32 kernels write (columns [D, round_up(D, piece)) as
+// zero).  VS = false: the output cannot take 16-byte stores (odd leading dimension or base): element stores below D.
+template <typename TO, bool VS>
+__device__ __forceinline__ void store_fp8_chunk(TO *__restrict__ o, const float (&v)[16], int32_t c0, int32_t D)
+{
+    constexpr int E = 16 / (int)sizeof(TO);
+    if (VS) {
+#pragma unroll
+        for (int p = 0; p < 16 / E; ++p) {
+            if (c0 + p * E >= D) continue;
+            float w[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) w[e] = v[p * E + e];
+            *reinterpret_cast<typename chunk_io<TO, E>::raw *>(o + p * E) = chunk_io<TO, E>::pack(w);
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float w[1] = {v[e]};
+            if (c0 + e < D) o[e] = chunk_io<TO, 1>::pack(w).h[0];
+        }
+    }
+}
+
 // One work item: 16-byte column chunk c0 of output row `row` = mean of n table rows.
 // TI = table element type, TO = output element type, VEC elements per chunk (both sides).
 // BATCH = rows in flight per lane (8; 16 in k_gather_multi_adam_wide): the summation order j = 0 .. n-1 is the same.
-template <typename TI, typename TO, int VEC, int BATCH = 8>
+// scale (FP8 tables only): fp32 [>= round_up(D, 16)], 16-byte aligned; VS: see store_fp8_chunk.
+template <typename TI, typename TO, int VEC, int BATCH = 8, bool VS = true>
 __device__ __forceinline__ void gather_mean_chunk(const TI *__restrict__ table, int64_t ld,
                                                   const int64_t *__restrict__ ids, int64_t row,
                                                   int32_t n, int32_t D, int32_t c0,
-                                                  TO *__restrict__ out, int64_t out_ld)
+                                                  TO *__restrict__ out, int64_t out_ld,
+                                                  const float *__restrict__ scale = nullptr)
 {
     using in_io = chunk_io<TI, VEC>;
-    using out_io = chunk_io<TO, VEC>;
     using in_raw = typename in_io::raw;
-    using out_raw = typename out_io::raw;
     float acc[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
@@ -134,9 +182,23 @@ __device__ __forceinline__ void gather_mean_chunk(const TI *__restrict__ table, 
         }
     }
     const float fn = (float)n;
+    if constexpr (sizeof(TI) == 1) {
+        float sc[VEC];
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) acc[e] = (c0 + e < D) ? acc[e] / fn : 0.f;   // n == 1: exact
-    *reinterpret_cast<out_raw *>(out + row * out_ld + c0) = out_io::pack(acc);
+        for (int k = 0; k < VEC / 4; ++k) {
+            const float4 f = *reinterpret_cast<const float4 *>(scale + c0 + 4 * k);
+            sc[4 * k + 0] = f.x; sc[4 * k + 1] = f.y; sc[4 * k + 2] = f.z; sc[4 * k + 3] = f.w;
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] = (c0 + e < D) ? acc[e] * sc[e] / fn : 0.f;
+        store_fp8_chunk<TO, VS>(out + row * out_ld + c0, acc, c0, D);
+    } else {
+        using out_io = chunk_io<TO, VEC>;
+        using out_raw = typename out_io::raw;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] = (c0 + e < D) ? acc[e] / fn : 0.f;   // n == 1: exact
+        *reinterpret_cast<out_raw *>(out + row * out_ld + c0) = out_io::pack(acc);
+    }
 }
 
 template <typename TI, typename TO, int VEC>
@@ -151,6 +213,23 @@ k_gather_mean(const TI *__restrict__ table, int64_t ld, const int64_t *__restric
                                                     : t / chunks;
         const int32_t c0 = (int32_t)(t - row * chunks) * VEC;
         gather_mean_chunk<TI, TO, VEC>(table, ld, ids, row, n, D, c0, out, out_ld);
+    }
+}
+
+// The FP8 form: same work items (16 columns each), the column scales ride along.
+template <typename TO, bool VS>
+__global__ void __launch_bounds__(256)
+k_gather_mean_fp8(const fp8_t *__restrict__ table, int64_t ld, const float *__restrict__ scale,
+                  const int64_t *__restrict__ ids, int64_t M, int32_t n, int32_t D, int32_t chunks,
+                  TO *__restrict__ out, int64_t out_ld)
+{
+    const int64_t total = M * (int64_t)chunks;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += stride) {
+        const int64_t row = (total <= 0xffffffffLL) ? (int64_t)((uint32_t)t / (uint32_t)chunks)
+                                                    : t / chunks;
+        const int32_t c0 = (int32_t)(t - row * chunks) * 16;
+        gather_mean_chunk<fp8_t, TO, 16, 8, VS>(table, ld, ids, row, n, D, c0, out, out_ld, scale);
     }
 }
 
@@ -172,7 +251,8 @@ struct MultiSeg {
 
 template <typename TI, typename TO, int VEC, int BATCH = 8>
 __device__ __forceinline__ void gather_multi_workgroup(const MultiSeg &q, int64_t ld, int32_t D,
-                                                       int32_t chunks, int64_t out_ld, int bx, int gx)
+                                                       int32_t chunks, int64_t out_ld, int bx, int gx,
+                                                       const float *__restrict__ scale = nullptr)
 {
     const int64_t total = q.first[q.n_seg];
     const int64_t stride = (int64_t)gx * 256;
@@ -269,7 +349,7 @@ __device__ __forceinline__ void gather_multi_workgroup(const MultiSeg &q, int64_
             continue;
         }
         gather_mean_chunk<TI, TO, VEC, BATCH>((const TI *)q.table[s], ld, q.ids[s], row, q.n[s], D, c0,
-                                              (TO *)q.out[s], out_ld);
+                                              (TO *)q.out[s], out_ld, scale);
     }
 }
 
@@ -278,6 +358,14 @@ __global__ void __launch_bounds__(256)
 k_gather_mean_multi(const MultiSeg q, int64_t ld, int32_t D, int32_t chunks, int64_t out_ld)
 {
     gather_multi_workgroup<TI, TO, VEC>(q, ld, D, chunks, out_ld, blockIdx.x, gridDim.x);
+}
+
+template <typename TO>
+__global__ void __launch_bounds__(256)
+k_gather_mean_multi_fp8(const MultiSeg q, const float *__restrict__ scale, int64_t ld, int32_t D, int32_t chunks,
+                        int64_t out_ld)
+{
+    gather_multi_workgroup<fp8_t, TO, 16>(q, ld, D, chunks, out_ld, blockIdx.x, gridDim.x, scale);
 }
 
 // The level-0 gathers of batch i+1, the clip + Adam update of batch i and the frontier sampling of
@@ -443,18 +531,31 @@ int gsage_gather_mean(const void *table, int dtype, int64_t ld, const int64_t *i
     return GSAGE_EINVAL;
 }
 
+// Can an FP8 launch write `out` in 16-byte pieces (store_fp8_chunk)?
+static inline bool fp8_out_vec_ok(const void *out, int out_dtype, int64_t D, int64_t out_ld)
+{
+    const int e = out_dtype == GSAGE_BF16 ? 8 : 4;
+    return out_ld % e == 0 && ceil_div(D, e) * e <= out_ld && aligned_to(out, 16);
+}
+
 static int fill_multi(MultiSeg &q, int32_t &chunks, int32_t n_seg, const void *const *tables,
                       const int64_t *const *ids, void *const *outs, const int64_t *M, const int32_t *n,
                       int dtype, int64_t ld, int64_t D, int out_dtype, int64_t out_ld)
 {
     GSAGE_REQUIRE(n_seg >= 1 && n_seg <= 8, "gather_mean_multi: 1..8 segments");
     GSAGE_REQUIRE(tables && ids && outs && M && n, "gather_mean_multi: null pointer");
-    GSAGE_REQUIRE((dtype == GSAGE_BF16 || dtype == GSAGE_F32) && (out_dtype == dtype || out_dtype == GSAGE_BF16),
-                  "gather_mean_multi: bf16 -> bf16, fp32 -> fp32 (the exact-arithmetic parity mode) or fp32 -> bf16 "
-                  "(fp32 embedding rows as a bf16 operand)");
-    const int vec = dtype == GSAGE_BF16 ? 8 : 4;
-    GSAGE_REQUIRE(D > 0 && ld % vec == 0 && out_ld % vec == 0 && ceil_div(D, vec) * vec <= ld &&
-                  ceil_div(D, vec) * vec <= out_ld, "gather_mean_multi: needs 16-byte row chunks");
+    const int vec = dtype == GSAGE_FP8 ? 16 : dtype == GSAGE_BF16 ? 8 : 4;
+    if (dtype == GSAGE_FP8) {            // (reached from gsage_gather_mean_multi_fp8 only)
+        GSAGE_REQUIRE(out_dtype == GSAGE_BF16 || out_dtype == GSAGE_F32, "gather_mean_multi_fp8: bf16 or fp32 output");
+        GSAGE_REQUIRE(D > 0 && ld % 16 == 0 && ceil_div(D, 16) * 16 <= ld && fp8_out_vec_ok(nullptr, out_dtype, D, out_ld),
+                      "gather_mean_multi_fp8: needs 16-byte row chunks");
+    } else {
+        GSAGE_REQUIRE((dtype == GSAGE_BF16 || dtype == GSAGE_F32) && (out_dtype == dtype || out_dtype == GSAGE_BF16),
+                      "gather_mean_multi: bf16 -> bf16, fp32 -> fp32 (the exact-arithmetic parity mode) or fp32 -> bf16 "
+                      "(fp32 embedding rows as a bf16 operand)");
+        GSAGE_REQUIRE(D > 0 && ld % vec == 0 && out_ld % vec == 0 && ceil_div(D, vec) * vec <= ld &&
+                      ceil_div(D, vec) * vec <= out_ld, "gather_mean_multi: needs 16-byte row chunks");
+    }
     chunks = (int32_t)ceil_div(D, vec);
     q.n_seg = n_seg;
     q.first[0] = 0;
@@ -487,6 +588,7 @@ int gsage_gather_mean_multi(int32_t n_seg, const void *const *tables, const int6
 {
     MultiSeg q;
     int32_t chunks = 0;
+    GSAGE_REQUIRE(dtype != GSAGE_FP8, "gather_mean_multi: an FP8 table carries column scales (gsage_gather_mean_multi_fp8)");
     int rc = fill_multi(q, chunks, n_seg, tables, ids, outs, M, n, dtype, ld, D, out_dtype, out_ld);
     if (rc != GSAGE_OK) return rc;
     if (q.first[n_seg] == 0) return GSAGE_OK;
@@ -500,6 +602,71 @@ int gsage_gather_mean_multi(int32_t n_seg, const void *const *tables, const int6
         launch(k_gather_mean_multi<uint16_t, uint16_t, 8>, dim3(grid_for(q.first[n_seg])),
                dim3(256), 0, (hipStream_t)stream, q, ld, (int32_t)D, chunks, out_ld);
     return check_launch("gather_mean_multi");
+}
+
+// ---- FP8 (e4m3fn bytes + one power-of-two fp32 scale per column) forms of the two entry points above ----
+static int check_fp8_table(const char *what, const void *table_q, int64_t ld, const float *scale, int64_t D)
+{
+    GSAGE_REQUIRE(table_q && scale && aligned_to(table_q, 16) && aligned_to(scale, 16),
+                  "%s: table_q and scale must be 16-byte aligned", what);
+    GSAGE_REQUIRE(ld % 16 == 0 && ceil_div(D, 16) * 16 <= ld,
+                  "%s: rows are whole 16-byte chunks (ld %% 16 == 0, round_up(D, 16) <= ld)", what);
+    return GSAGE_OK;
+}
+
+int gsage_gather_mean_fp8(const void *table_q, int64_t ld, const float *scale, const int64_t *ids, int64_t M,
+                          int32_t n, int64_t D, void *out, int out_dtype, int64_t out_ld, void *stream)
+{
+    GSAGE_REQUIRE(n > 0 && M >= 0 && D > 0, "gather_mean_fp8: bad sizes M=%lld n=%d D=%lld",
+                  (long long)M, n, (long long)D);
+    GSAGE_REQUIRE(ld >= D && out_ld >= D, "gather_mean_fp8: leading dimension smaller than D");
+    GSAGE_REQUIRE(D <= 0x7fffffff, "gather_mean_fp8: D too large");
+    GSAGE_REQUIRE(out_dtype == GSAGE_BF16 || out_dtype == GSAGE_F32, "gather_mean_fp8: bf16 or fp32 output");
+    if (M == 0) return GSAGE_OK;
+    GSAGE_REQUIRE(out, "gather_mean_fp8: null pointer");
+    int rc = check_fp8_table("gather_mean_fp8", table_q, ld, scale, D);
+    if (rc != GSAGE_OK) return rc;
+    GSAGE_REQUIRE(aligned_to(out, out_dtype == GSAGE_BF16 ? 2 : 4), "gather_mean_fp8: misaligned output");
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t chunks = (int32_t)ceil_div(D, 16);
+    const dim3 grid(grid_for(M * chunks));
+    const fp8_t *t = (const fp8_t *)table_q;
+    const bool vs = fp8_out_vec_ok(out, out_dtype, D, out_ld);
+    if (out_dtype == GSAGE_BF16 && vs)
+        launch(k_gather_mean_fp8<uint16_t, true>, grid, dim3(256), 0, s, t, ld, scale, ids, M, n, (int32_t)D, chunks, (uint16_t *)out, out_ld);
+    else if (out_dtype == GSAGE_BF16)
+        launch(k_gather_mean_fp8<uint16_t, false>, grid, dim3(256), 0, s, t, ld, scale, ids, M, n, (int32_t)D, chunks, (uint16_t *)out, out_ld);
+    else if (vs)
+        launch(k_gather_mean_fp8<float, true>, grid, dim3(256), 0, s, t, ld, scale, ids, M, n, (int32_t)D, chunks, (float *)out, out_ld);
+    else
+        launch(k_gather_mean_fp8<float, false>, grid, dim3(256), 0, s, t, ld, scale, ids, M, n, (int32_t)D, chunks, (float *)out, out_ld);
+    return check_launch("gather_mean_fp8");
+}
+
+int gsage_gather_rows_fp8(const void *table_q, int64_t ld, const float *scale, const int64_t *ids, int64_t M,
+                          int64_t D, void *out, int out_dtype, int64_t out_ld, void *stream)
+{
+    GSAGE_REQUIRE(ids || M == 0, "gather_rows_fp8: null row list");
+    return gsage_gather_mean_fp8(table_q, ld, scale, ids, M, 1, D, out, out_dtype, out_ld, stream);
+}
+
+int gsage_gather_mean_multi_fp8(int32_t n_seg, const void *const *tables_q, const int64_t *const *ids,
+                                void *const *outs, const int64_t *M, const int32_t *n, const float *scale,
+                                int64_t ld, int64_t D, int out_dtype, int64_t out_ld, void *stream)
+{
+    MultiSeg q;
+    int32_t chunks = 0;
+    int rc = fill_multi(q, chunks, n_seg, tables_q, ids, outs, M, n, GSAGE_FP8, ld, D, out_dtype, out_ld);
+    if (rc != GSAGE_OK) return rc;
+    GSAGE_REQUIRE(scale && aligned_to(scale, 16), "gather_mean_multi_fp8: scale must be 16-byte aligned");
+    if (q.first[n_seg] == 0) return GSAGE_OK;
+    if (out_dtype == GSAGE_BF16)
+        launch(k_gather_mean_multi_fp8<uint16_t>, dim3(grid_for(q.first[n_seg])), dim3(256), 0, (hipStream_t)stream,
+               q, scale, ld, (int32_t)D, chunks, out_ld);
+    else
+        launch(k_gather_mean_multi_fp8<float>, dim3(grid_for(q.first[n_seg])), dim3(256), 0, (hipStream_t)stream,
+               q, scale, ld, (int32_t)D, chunks, out_ld);
+    return check_launch("gather_mean_multi_fp8");
 }
 
 // Workgroups of k_gather_multi_adam that can be RESIDENT at once with `lds_bytes` of dynamic LDS (the sampler role's
@@ -539,6 +706,7 @@ int gsage_gather_mean_multi_adam(int32_t n_seg, const void *const *tables, const
 {
     MultiSeg q;
     int32_t chunks = 0;
+    GSAGE_REQUIRE(dtype != GSAGE_FP8, "gather_mean_multi_adam: no FP8 form (gsage_gather_mean_multi_fp8 has no side roles)");
     int rc = fill_multi(q, chunks, n_seg, tables, ids, outs, M, n, dtype, ld, D, out_dtype, out_ld);
     if (rc != GSAGE_OK) return rc;
     GSAGE_REQUIRE(out_dtype == dtype, "gather_mean_multi_adam: table and output share a type");

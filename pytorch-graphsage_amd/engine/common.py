@@ -45,6 +45,11 @@ class _PrepDesc(ctypes.Structure):           # mirrors gsage_prep_desc (include/
 _Wgrad = collections.namedtuple("_Wgrad", "dC A lda a_gstride M Ntot K n_per_group rows param")
 
 
+# what every engine without an FP8 form says of an FP8 store (train.py --engine auto then takes the module path)
+_FP8_REFUSAL = ("an FP8 feature table, which this engine's kernels do not decode (the module path reads it through "
+                "the FP8 gather kernels)")
+
+
 def _round64(v):
     return (int(v) + 63) // 64 * 64     # whole 128-byte bf16 lines: enables the LDS-DMA GEMM path
 
@@ -133,16 +138,19 @@ class FusedTrainStep(object):
         return None
 
     @staticmethod
-    def _why_not_input(model, feats, ddp=None, concat_ok=False):
+    def _why_not_input(model, feats, ddp=None, concat_ok=False, fp8_ok=False):
         """Level-0 rows: an identity prep over a FeatureStore in HBM, or the trainable node-embedding prep
         (nn_modules.py:126-155) -- without features (BASELINE configs[3] / utils/pokec.sh) or, where the engine says
-        concat_ok, concatenated behind them (nn_modules.py:152-153: [feats | fc(embedding)])."""
+        concat_ok, concatenated behind them (nn_modules.py:152-153: [feats | fc(embedding)]).  fp8_ok: the engine
+        reads an FP8 store (identity prep, bf16 compute, one process)."""
         if isinstance(model.prep, NodeEmbeddingPrep):
             if (feats is None) != (not model.prep.input_dim):
                 return "a node-embedding prep whose input_dim disagrees with the features it is given"
             if feats is not None:
                 if not concat_ok:
                     return "a node-embedding prep concatenated with features"
+                if isinstance(feats, FeatureStore) and feats.is_fp8:
+                    return _FP8_REFUSAL
                 if not isinstance(feats, FeatureStore) or not feats.is_cuda or feats.dim != int(model.prep.input_dim) \
                         or feats.dtype not in (torch.bfloat16, torch.float32):
                     return "features beside the node embedding that are not a bf16 / fp32 FeatureStore in HBM"
@@ -158,6 +166,13 @@ class FusedTrainStep(object):
             return "a prep class other than identity / node_embedding (%s)" % type(model.prep).__name__
         if not isinstance(feats, FeatureStore):
             return "features that are not a FeatureStore"
+        if feats.is_fp8:
+            if not fp8_ok:
+                return _FP8_REFUSAL
+            if ops.config.compute_dtype != "bf16" or not feats.is_cuda or ddp is not None:
+                return ("an FP8 feature table outside its one fused form (bf16 compute, in HBM, one process: the "
+                        "FP8 gather launch carries no update and forms no in-launch norm)")
+            return None
         if feats.dtype not in (torch.bfloat16, torch.float32) or not feats.is_cuda:
             return "a feature table that is not bf16 / fp32 in HBM"
         return None
@@ -243,8 +258,12 @@ class FusedTrainStep(object):
                 self._reduce_op = torch.distributed.ReduceOp.SUM
         dev = feats.device if feats is not None else next(model.parameters()).device
         self.dev = dev
-        # storage type of features, activations and weight operand copies
-        self.tdt = feats.dtype if feats is not None else ops.torch_dtype()
+        # storage type of the feature table ...
+        self.sdt = feats.dtype if feats is not None else None
+        self.fp8 = bool(feats is not None and feats.is_fp8)
+        # ... and of activations, level-0 operands and weight operand copies: the table's, except over an FP8 table,
+        # whose rows are decoded into bf16 operands by the gather launch (every decoded value is a bf16 number)
+        self.tdt = torch.bfloat16 if self.fp8 else feats.dtype if feats is not None else ops.torch_dtype()
         self.code = nat.BF16 if self.tdt == torch.bfloat16 else nat.F32
         self.esz = 2 if self.tdt == torch.bfloat16 else 4
         self.sel, self.sel_queue = None, None     # caller-supplied sampler draws (set_sel / load_epoch)
@@ -790,6 +809,8 @@ class FusedTrainStep(object):
         gathers, an update workgroup's six to eight dependent rounds of partial loads (16 in flight per lane is what
         the launch's 72-register cap leaves) take ~28 us against 6.5 + 16 for the finalisation launch and the
         update without them -- 0.0916 against 0.0836 ms/step at configs[1]."""
+        if self.fp8:                     # (the FP8 gather launch has no update role to fold the finalisation into)
+            return False
         if self._fold is None:
             assert self.n_rdesc is not None, "asked before _install_reduce(): the kept answer would not be the table's"
             mode = os.environ.get("GSAGE_FOLD_FINALIZE", "0")
@@ -1016,11 +1037,11 @@ class FusedTrainStep(object):
             self.flat_g.div_(self.ddp.world)
         return torch.distributed.all_reduce(self.flat_g, op=self._reduce_op, async_op=async_op)
 
-    def _stage_opt(self):
-        """clip_grad_norm(5) + Adam over the flat bucket."""
+    def _stage_opt(self, d=None):
+        """clip_grad_norm(5) + Adam over the flat bucket (d: a descriptor the caller built, else the step's own)."""
         if self.emb:
             return self._stage_opt_emb()
-        d = self._adam_desc()
+        d = self._adam_desc() if d is None else d
         if d.reduce_descs:               # (no finalisation launch ran: the update sums the partial buffers itself)
             nat.check(nat.lib().gsage_clip_adam_meet(ctypes.addressof(d), ops._stream()), "clip_adam_meet")
             return

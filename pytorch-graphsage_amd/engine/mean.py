@@ -1,6 +1,7 @@
 """
 engine/mean.py -- FusedMeanTrainStep: the north-star configuration (BASELINE configs[1], [4]): mean aggregators
-(reference nn_modules.py:185-204) over an identity prep and a bf16 / fp32 FeatureStore.
+(reference nn_modules.py:185-204) over an identity prep and a bf16 / fp32 FeatureStore -- or an FP8 one, whose rows
+the gather launch decodes into the same bf16 operands.
 """
 import ctypes
 import os
@@ -51,7 +52,10 @@ class FusedMeanTrainStep(FusedTrainStep):
         # bf16 storage = the production path; fp32 storage = the exact-arithmetic parity mode (same engine, same
         # kernel sources instantiated on fp32: golden fixtures replay at 2e-4).  With the node-embedding prep
         # (utils/pokec.sh:5-13) the level-0 rows are weights: computed per step, nothing is gathered ahead.
-        why = cls._why_not_common(model, feats, (MeanAggregator,), "mean") or cls._why_not_input(model, feats, ddp, concat_ok=True)
+        # FP8 storage (identity prep, bf16 compute): the level-0 gathers run on the FP8 gather launch, which writes
+        # the bf16 operands the bf16 engine would have gathered, bit for bit; everything behind them is that engine.
+        why = cls._why_not_common(model, feats, (MeanAggregator,), "mean") or \
+            cls._why_not_input(model, feats, ddp, concat_ok=True, fp8_ok=True)
         if why:
             return why
         if not all(l.output_dim_ % 8 == 0 for l in model.agg_layers.children()):
@@ -67,6 +71,8 @@ class FusedMeanTrainStep(FusedTrainStep):
         if self.emb:                                 # level-0 rows = [features |] prep.fc(embedding[ids])
             d0 = self.D0 + self.E
             ld0 = _round64(d0) if (self.tdt == torch.bfloat16 or self.D0) else d0
+        elif self.fp8:                               # bf16 operands of an FP8 table: whole 128-byte lines of bf16
+            d0, ld0 = feats.dim, _round64(feats.dim)
         else:
             d0, ld0 = feats.dim, feats.ld
         self.din = [d0] + [2 * h for h in self.h[:-1]]
@@ -113,7 +119,10 @@ class FusedMeanTrainStep(FusedTrainStep):
         # K5 and K5b read the x rows of level 0 in place through the frontier's row list (gsage_linear_nt_packed
         # a_rows / gsage_wgrad_desc.a_rows) instead of from xa0[0]: no row copies in the gather launch (28.5 vs
         # 32.9 us in-step, 0.092 vs 0.095 ms/step at config 2; GSAGE_MEAN_INPLACE_X=0 brings the copies back)
-        self.inplace_x = (os.environ.get("GSAGE_MEAN_INPLACE_X", "1") == "1" and self.L >= 2 and not self.emb)
+        # (an FP8 table: K5 / K5b read bf16 rows, so the x rows -- B (1 + n1 + ...) of them, a tenth of the neighbour
+        #  rows -- are decoded into xa0[0] by the gather launch's row-gather segment and read from there, no a_rows)
+        self.inplace_x = (os.environ.get("GSAGE_MEAN_INPLACE_X", "1") == "1" and self.L >= 2 and not self.emb
+                          and not self.fp8)
         #                                                               (one level: the copies ARE the "rest" launch
         #                                                                that carries Adam in data-parallel runs)
         self.agg, self.hout, self.dc, self.dg = [], [], [], []
@@ -209,11 +218,21 @@ class FusedMeanTrainStep(FusedTrainStep):
                              xa[1][self.off[k] + r0:self.off[k] + r1], r1 - r0, n))
         if part != "means" and not self.inplace_x:
             segs.append((st.data, ids[:R], xa[0], R, 1))
+        if adam is None and with_adam:
+            adam = self._adam_desc()
+        if self.fp8:
+            # the FP8 gather launch takes every row and carries no side role: the update and the sampler, which
+            # touch data disjoint from the gather's, follow as the launches of their own that the per-call path uses
+            if segs:
+                ops.gather_mean_multi(segs, st.ld, st.dim, self.ldin[0], scale=st.scale)
+            if adam is not None:
+                self._stage_opt(adam)
+            if hops is not None:
+                nat.check(nat.lib().gsage_sample_hops(ctypes.addressof(hops), ops._stream()), "sample_hops")
+            return bool(segs)
         if not segs:
             return False
         # (D = the real width: the pad columns of the operand buffers were zeroed once and stay zero)
-        if adam is None and with_adam:
-            adam = self._adam_desc()
         ops.gather_mean_multi(segs, st.ld, st.dim, st.ld, adam=adam, hops=hops)
         return True
 
@@ -237,7 +256,7 @@ class FusedMeanTrainStep(FusedTrainStep):
                 xbuf, agg, lda = st.data, self.xa0_set[s][1], st.ld
                 rows = self._front.data_ptr()
             elif l == 0:
-                xbuf, agg, lda = self.xa0_set[s][0], self.xa0_set[s][1], st.ld
+                xbuf, agg, lda = self.xa0_set[s][0], self.xa0_set[s][1], self.ldin[0]
             else:
                 xbuf, agg, lda = self.hout[l - 1], self.agg[l], din
                 segs = [(xbuf[self.off[k + 1]:self.off[k + 2]], None, agg[self.off[k]:self.off[k + 1]],
@@ -342,7 +361,9 @@ class FusedMeanTrainStep(FusedTrainStep):
     def _tail_gather_rows(self):
         """Rows of the last hop's neighbour means that the seed-level launch of the previous step
         gathers (0: none)."""
-        if not self.fused_tail or self.emb or self.fan[self.L] not in (5, 10, 15) or self.code != nat.BF16:
+        # (an FP8 table: the gather roles of gsage_gather_dev.h read bf16 rows and are not played -- n_workgroups = 0
+        #  by never building the descriptor; the FP8 gather launch takes all rows)
+        if not self.fused_tail or self.emb or self.fan[self.L] not in (5, 10, 15) or self.code != nat.BF16 or self.fp8:
             return 0
         mfma = self._tail_on_mfma()
         n_idle = self._tail_idle_cus(self._k1_in_tail())

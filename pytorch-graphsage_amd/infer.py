@@ -213,6 +213,8 @@ def _feature_rows(feats, n):
         if int(feats.data.shape[0]) < n:
             raise ValueError("full-neighbour inference: %d feature rows for an adjacency of %d rows"
                              % (int(feats.data.shape[0]), n))
+        if feats.is_fp8:                       # level 0 is decoded ONCE (the FP8 row gather); every layer reads the copy
+            feats = feats.decoded(ops.config.compute_dtype if feats.is_cuda else "fp32", n_rows=n)
         return ops.mark_zero_padded(feats.data[:n, :feats.dim])
     if int(feats.shape[0]) < n:
         raise ValueError("full-neighbour inference: %d feature rows for an adjacency of %d rows" % (int(feats.shape[0]), n))

@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native as nat
-from .store import FeatureStore, RowRef, _round_up
+from .store import FP8, FeatureStore, RowRef, _round_up, quantize_fp8_host
 
 _vp = ctypes.c_void_p
 
@@ -45,6 +45,8 @@ def _code(dtype):
         return nat.F32
     if dtype == torch.bfloat16:
         return nat.BF16
+    if dtype == FP8:
+        return nat.FP8
     raise TypeError("gsage: unsupported dtype %s" % dtype)
 
 
@@ -326,6 +328,65 @@ def _gather_mean_raw(table, D, ids, M, n, out_dtype, out_ld=None, out=None):
     return out
 
 
+def quantize_fp8(table, D, ld_q):
+    """[R, ld] fp32 / bf16 table (columns [0, D) live) -> (table_q [R, ld_q] float8_e4m3fn, scale [ld_q] fp32): the
+    FP8 feature-table format of include/gsage.h (gsage_quantize_fp8; CPU tensors: store.quantize_fp8_host)."""
+    R = int(table.shape[0])
+    assert table.dtype in (torch.float32, torch.bfloat16) and table.stride(1) == 1 and ld_q % 16 == 0 and ld_q >= D
+    if table.is_cuda:
+        q = torch.empty(R, ld_q, dtype=FP8, device=table.device)
+        scale = torch.empty(ld_q, dtype=torch.float32, device=table.device)
+        nat.check(nat.lib().gsage_quantize_fp8(_ptr(table), _code(table.dtype), table.stride(0), R, D, _ptr(q), ld_q,
+                                               _ptr(scale), _stream()), "quantize_fp8")
+        return q, scale
+    q = torch.zeros(R, ld_q, dtype=torch.uint8).view(FP8)
+    scale = torch.ones(ld_q, dtype=torch.float32)
+    q[:, :D], scale[:D] = quantize_fp8_host(table[:, :D])
+    return q, scale
+
+
+def _gather_mean_fp8_raw(table_q, scale, D, ids, M, n, out_dtype, out_ld=None, out=None):
+    """_gather_mean_raw on an FP8 table: out[i] = (sum_j e4m3(table_q[ids[i*n+j]])) * scale / n, the sum in fp32
+    in neighbour order -- bit for bit what _gather_mean_raw gives on a bf16 table of the decoded values."""
+    assert table_q.dtype == FP8 and scale is not None and scale.dtype == torch.float32
+    if out_ld is None:
+        out_ld = D
+    if table_q.is_cuda:
+        if out is None:
+            out = (torch.zeros if out_ld != D else torch.empty)(M, out_ld, dtype=out_dtype, device=table_q.device)
+        else:
+            assert out.dtype == out_dtype and out.stride(0) == out_ld and out.shape[0] == M
+        nat.check(nat.lib().gsage_gather_mean_fp8(_ptr(table_q), table_q.stride(0), _ptr(scale), _ptr(ids), M, n, D,
+                                                  _ptr(out), _code(out_dtype), out_ld, _stream()), "gather_mean_fp8")
+        return out
+    rows = table_q[ids.view(-1), :D] if ids is not None else table_q[:M * n, :D]
+    # the lines of _gather_mean_raw's host mode on the unscaled e4m3 values, then the scales: a power of two commutes
+    # with every rounding of the mean, so this IS that host mode on the decoded table, bit for bit
+    res = (rows.float().view(M, n, D).mean(dim=1) if n > 1 else rows.float().view(M, D)) * scale[:D]
+    out = torch.zeros(M, out_ld, dtype=out_dtype)
+    out[:, :D] = res.to(out_dtype)
+    return out
+
+
+def _store_gather(store, D, ids, M, n, out_dtype, out_ld=None):
+    if store.is_fp8:
+        return _gather_mean_fp8_raw(store.data, store.scale, D, ids, M, n, out_dtype, out_ld)
+    return _gather_mean_raw(store.data, D, ids, M, n, out_dtype, out_ld)
+
+
+def decoded_rows(ref, compute_dtype=None):
+    """A RowRef into an FP8 store -> its rows decoded into the compute type by the FP8 row gather (a [:, :D] view
+    of zero-padded rows); anything else is returned as it is.  K5 and the aggregator kernels gather bf16 / fp32
+    table rows through a row list (`a_rows`); they never see FP8 bytes."""
+    if not (isinstance(ref, RowRef) and ref.store.is_fp8):
+        return ref
+    st = ref.store
+    cdt = torch_dtype(compute_dtype)
+    ld = _round_up(st.dim, 64 if cdt == torch.bfloat16 else 32)
+    buf = _gather_mean_fp8_raw(st.data, st.scale, st.dim, ref.ids, int(ref.ids.shape[0]), 1, cdt, ld)
+    return mark_zero_padded(buf[:, :st.dim])
+
+
 class _GatherTrainable(torch.autograd.Function):
     """Row gather from a TRAINABLE fp32 table with the reference's dense gradient
     (nn.Embedding, nn_modules.py:134,146-149): backward = K6 scatter-add into a zeroed table."""
@@ -372,7 +433,7 @@ def embedding_rows(table, ids):
 def gather_rows(store, ids, out_dtype=torch.float32):
     """feats[ids] (models.py:76,80) materialised: [M, D] tensor of `out_dtype`."""
     ids = ids.contiguous().view(-1)
-    return _gather_mean_raw(store.data, store.dim, ids, int(ids.shape[0]), 1, out_dtype)
+    return _store_gather(store, store.dim, ids, int(ids.shape[0]), 1, out_dtype)
 
 
 def gather_mean(store, ids, M, n, out_dtype=torch.float32, out_ld=None):
@@ -382,8 +443,8 @@ def gather_mean(store, ids, M, n, out_dtype=torch.float32, out_ld=None):
     assert ids.shape[0] == M * n
     if out_ld is not None and out_ld == store.ld:
         # the table's pad columns are zero, so averaging them writes the output's pad columns
-        return _gather_mean_raw(store.data, store.ld, ids, M, n, out_dtype, out_ld)
-    return _gather_mean_raw(store.data, store.dim, ids, M, n, out_dtype, out_ld)
+        return _store_gather(store, store.ld, ids, M, n, out_dtype, out_ld)
+    return _store_gather(store, store.dim, ids, M, n, out_dtype, out_ld)
 
 
 class _SegmentMean(torch.autograd.Function):
@@ -453,11 +514,12 @@ def _prep_weight(W, cdt, epc):
     return _pad_cast(W.detach(), cdt, epc)
 
 
-def gather_mean_multi(segments, ld, D, out_ld, adam=None, hops=None):
+def gather_mean_multi(segments, ld, D, out_ld, adam=None, hops=None, scale=None):
     """All hops of a level in one K2 launch.  segments: list of (table, ids|None, out, M, n) with
     bf16 (or, parity mode, fp32) row-major tensors sharing ld / out_ld.  adam: optional _native.AdamDesc -- the clip + Adam
     update of the previous batch rides in the same launch; hops: optional _native.HopsDesc -- so does
-    the frontier sampling of a later batch (gsage_gather_mean_multi_adam)."""
+    the frontier sampling of a later batch (gsage_gather_mean_multi_adam).  scale: the column scales of an FP8 store
+    whose `data` every segment reads (gsage_gather_mean_multi_fp8: bf16 or fp32 outputs, no side roles)."""
     k = len(segments)
     T = (ctypes.c_void_p * k)(*[s[0].data_ptr() for s in segments])
     I = (ctypes.c_void_p * k)(*[(s[1].data_ptr() if s[1] is not None else None) for s in segments])
@@ -466,6 +528,12 @@ def gather_mean_multi(segments, ld, D, out_ld, adam=None, hops=None):
     ns = (ctypes.c_int32 * k)(*[int(s[4]) for s in segments])
     code, ocode = _code(segments[0][0].dtype), _code(segments[0][2].dtype)
     assert all(s[0].dtype == segments[0][0].dtype and s[2].dtype == segments[0][2].dtype for s in segments)
+    assert (code == nat.FP8) == (scale is not None), "an FP8 table, and only an FP8 table, comes with its scales"
+    if code == nat.FP8:
+        assert adam is None and hops is None, "gather_mean_multi: the FP8 launch carries no side roles"
+        nat.check(nat.lib().gsage_gather_mean_multi_fp8(k, T, I, O, Ms, ns, _ptr(scale), ld, D, ocode, out_ld,
+                                                        _stream()), "gather_mean_multi_fp8")
+        return
     if adam is not None or hops is not None:
         nat.check(nat.lib().gsage_gather_mean_multi_adam(
             k, T, I, O, Ms, ns, code, ld, D, code, out_ld,
@@ -704,6 +772,7 @@ def sage_project(x, agg, Wx, Wn, act=nat.ACT_NONE, compute_dtype=None, out_dtype
         y = torch.cat([F.linear(xt.float(), Wx), F.linear(agg.float(), Wn)], dim=1)
         return torch.relu(y) if act == nat.ACT_RELU else y
     cd = compute_dtype or config.compute_dtype
+    x = decoded_rows(x, cd)
     if isinstance(x, RowRef):
         return _SageProject.apply(None, agg, Wx, Wn, x.store.data, x.ids, x.store.dim, act, cd,
                                   out_dtype)
@@ -795,6 +864,7 @@ def pool_mlp(neibs, Wm, bm, M, mode, compute_dtype=None):
         hid = torch.relu(F.linear(nb.float(), Wm, bm)).view(M, n, -1)
         return hid.max(dim=1)[0] if mode == nat.POOL_MAX else hid.mean(dim=1)
     cd = compute_dtype or config.compute_dtype
+    neibs = decoded_rows(neibs, cd)
     if n > 64:      # tile holds whole segments only up to 64 rows: unfused route, still K5
         nb = neibs.materialize() if isinstance(neibs, RowRef) else neibs
         hid = linear(nb, Wm, bm, nat.ACT_RELU, cd).view(M, n, -1)
@@ -873,6 +943,7 @@ def attn_aggregate(na, xa, neibs, M):
         s = torch.bmm(na.view(M, n, -1), xa.view(M, -1, 1)).squeeze(2)
         w = torch.softmax(s, dim=1)
         return (nb.float().view(M, n, -1) * w.unsqueeze(-1)).sum(dim=1)
+    neibs = decoded_rows(neibs)
     if n > 64:
         nb = neibs.materialize() if isinstance(neibs, RowRef) else neibs
         s = torch.bmm(na.view(M, n, -1), xa.view(M, -1, 1)).squeeze(2)
@@ -1025,6 +1096,7 @@ def lstm_last(neibs, M, w_ih, w_hh, b_ih, b_hh, reverse=None, compute_dtype=None
     n = total // M
     cd = compute_dtype or config.compute_dtype
     rev = tuple(reverse) if reverse is not None else (None, None, None, None)
+    neibs = decoded_rows(neibs, cd)
     if isinstance(neibs, RowRef):
         return _LSTMLast.apply(None, neibs.store.data, neibs.ids, neibs.store.dim, M, n, cd, w_ih, w_hh, b_ih, b_hh, *rev)
     return _LSTMLast.apply(neibs, None, None, 0, M, n, cd, w_ih, w_hh, b_ih, b_hh, *rev)

@@ -281,6 +281,21 @@ class NodeProblem(object):
             else:
                 self.feats = torch.FloatTensor(np.asarray(self.feats, dtype=np.float32))
 
+    def quantize_features(self):
+        """Replace the features by their FP8 store (store.FeatureStore.quantize; a CPU problem's tensor becomes a
+        CPU store: host mode).  Returns (bytes before, bytes after, largest absolute quantisation error)."""
+        assert self.feats is not None, "quantize_features: this problem has no features"
+        old = self.feats if isinstance(self.feats, FeatureStore) else FeatureStore.wrap(self.feats)
+        if old.is_fp8:
+            return old.nbytes(), old.nbytes(), 0.0
+        new = old.quantize()
+        err, rows = 0.0, int(old.data.shape[0])
+        for o in range(0, rows, 1 << 20):                     # (chunks: two fp32 copies of a 28 GB table do not fit)
+            ids = torch.arange(o, min(o + (1 << 20), rows), device=old.device)
+            err = max(err, float((ops.gather_rows(new, ids) - ops.gather_rows(old, ids)).abs().max()))
+        self.feats = new
+        return old.nbytes(), new.nbytes(), err
+
     def _batch(self, mids, targets):
         mids = torch.LongTensor(mids)
         if self.task == 'classification':

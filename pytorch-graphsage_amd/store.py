@@ -8,7 +8,10 @@ store.py -- HBM-resident data layouts of the hot path.
   FeatureStore  the node-feature table feats[N+1, D] (problem.py:118-121) kept in HBM as a
                 row-major [n_rows, ld] matrix, bf16 (default on GPU) or fp32, rows padded with zeros
                 to a multiple of 128 bytes so every row is a whole number of cache lines and
-                16-byte lane loads are aligned.
+                16-byte lane loads are aligned.  Opt-in FP8 storage (dtype="fp8", .quantize()): one
+                OCP e4m3fn byte per element (torch.float8_e4m3fn) plus `scale`, one power-of-two
+                fp32 per column; value = e4m3(data[r, c]) * scale[c] (include/gsage.h, "FP8 feature
+                table").  Its `dtype` says so: no consumer can mistake the bytes for bf16.
   RowRef        what `feats[ids]` (models.py:76,80) returns for a FeatureStore: a *reference* to
                 rows, consumed by the fused gather kernels; the [B*f1*f2, D] frontier the reference
                 materialises per batch never exists unless someone asks for `.materialize()`.
@@ -19,6 +22,30 @@ import torch
 
 def _round_up(v, m):
     return (v + m - 1) // m * m
+
+
+FP8 = torch.float8_e4m3fn
+_DTYPES = {"bf16": torch.bfloat16, "fp32": torch.float32, "fp8": FP8}
+_FP8_MAX = 448.0
+
+
+def _ld_for(dim, tdt):
+    """Leading dimension (elements) of a row padded to a multiple of 128 bytes."""
+    return _round_up(int(dim), 128 // torch.empty(0, dtype=tdt).element_size())
+
+
+def quantize_fp8_host(x):
+    """Host-mode statement of gsage_quantize_fp8 in stock torch: x [R, D] fp32 / bf16 (CPU) -> (q [R, D]
+    float8_e4m3fn, scale [D] fp32).  scale[c] = the smallest power of two s >= 2^-126 with max|x[:, c]| / s <= 448
+    (1.0 for an all-zero column); q = x / s rounded to e4m3fn, nearest even, saturating (never a NaN byte).  A NaN
+    input counts as 0, one beyond +-2^127 as +-2^127."""
+    x = torch.nan_to_num(x.float(), nan=0.0).clamp(-2.0 ** 127, 2.0 ** 127)    # (every decoded value stays finite)
+    amax = x.abs().amax(dim=0) if x.shape[0] else torch.zeros(x.shape[1])
+    mant, exp = torch.frexp(amax)                            # amax = mant * 2^exp, mant in [0.5, 1): 448 = 0.875 * 2^9
+    k = (exp - 9 + (mant > 0.875).to(exp.dtype)).clamp(-126, 119)
+    scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), k), torch.ones_like(amax))
+    q = (x / scale).clamp(-_FP8_MAX, _FP8_MAX).to(FP8)       # x / s is exact; the cast rounds to nearest even
+    return q, scale
 
 
 def row_positions(indptr):
@@ -144,30 +171,54 @@ class FeatureStore(object):
     """Device-resident node-feature table.  Quacks enough like the reference's `problem.feats`
     tensor for models.py / train.py: `.shape`, `.size()`, `feats[ids]`, `.is_cuda`."""
 
-    def __init__(self, data, dim):
+    def __init__(self, data, dim, scale=None):
         assert data.dim() == 2 and data.is_contiguous()
+        assert (data.dtype == FP8) == (scale is not None), "an FP8 store, and only an FP8 store, carries column scales"
         if int(data.shape[0]) >= 2 ** 31:            # the gather kernels read the low 32-bit word of a node id
             raise ValueError("FeatureStore: %d rows; node ids must stay below 2^31 (include/gsage.h, gsage_gather_mean)"
                              % int(data.shape[0]))
         self.data = data               # [n_rows, ld]
         self.dim = int(dim)            # logical D (columns [D, ld) are zero)
+        self.scale = scale             # FP8 only: fp32 [ld], powers of two (1.0 in the pad columns)
 
     @staticmethod
     def from_array(feats, device, dtype="bf16"):
         feats = torch.as_tensor(np.asarray(feats) if not torch.is_tensor(feats) else feats)
         n_rows, dim = feats.shape
-        tdt = {"bf16": torch.bfloat16, "fp32": torch.float32}[dtype]
-        ld = _round_up(dim, 128 // (2 if dtype == "bf16" else 4))
+        tdt = _DTYPES[dtype]
+        if tdt == FP8:
+            # (quantised where the result lives: the device's kernel, or the host mode for a CPU store)
+            return FeatureStore.wrap(feats.to(device=device, dtype=torch.float32)).quantize()
+        ld = _ld_for(dim, tdt)
         data = torch.zeros(n_rows, ld, dtype=tdt, device=device)
         data[:, :dim] = feats.to(device=device, dtype=torch.float32).to(tdt)
         return FeatureStore(data, dim)
+
+    def quantize(self):
+        """An FP8 store of this bf16 / fp32 store's values (gsage_quantize_fp8 on the GPU, quantize_fp8_host
+        on the CPU: the same bytes and scales)."""
+        if self.is_fp8:
+            return self
+        from . import ops
+        q, scale = ops.quantize_fp8(self.data, self.dim, _ld_for(self.dim, FP8))
+        return FeatureStore(q, self.dim, scale)
+
+    @property
+    def is_fp8(self):
+        return self.data.dtype == FP8
+
+    def nbytes(self):
+        """Bytes of HBM (or host memory) the table occupies, scales included."""
+        n = self.data.numel() * self.data.element_size()
+        return n + (self.scale.numel() * 4 if self.scale is not None else 0)
 
     @staticmethod
     def synthetic(n_rows, dim, device, dtype="bf16", seed=0, chunk=1 << 23):
         """N(0, 1) rows generated on the device in chunks (a 111 M x 128 bf16 table is 28 GB; its fp32 staging copy
         would be twice that); row 0 (the dummy node) is zero."""
-        tdt = {"bf16": torch.bfloat16, "fp32": torch.float32}[dtype]
-        ld = _round_up(int(dim), 128 // (2 if dtype == "bf16" else 4))
+        assert dtype in ("bf16", "fp32"), "synthetic: bf16 or fp32 (then .quantize() for FP8)"
+        tdt = _DTYPES[dtype]
+        ld = _ld_for(dim, tdt)
         data = torch.zeros(int(n_rows), ld, dtype=tdt, device=device)
         gen = torch.Generator(device=device).manual_seed(int(seed))
         for o in range(0, int(n_rows), chunk):
@@ -179,6 +230,7 @@ class FeatureStore(object):
     @staticmethod
     def wrap(t):
         """Zero-copy view of an existing [n_rows, D] fp32 / bf16 tensor (ld == D)."""
+        assert t.dtype in (torch.bfloat16, torch.float32), "wrap: fp32 / bf16 tensors (FP8 bytes need their scales)"
         return FeatureStore(t.detach().contiguous(), t.shape[1])
 
     @property
@@ -205,14 +257,29 @@ class FeatureStore(object):
         return self.data.dtype
 
     def cuda(self):
-        return FeatureStore(self.data.cuda(), self.dim)
+        return FeatureStore(self.data.cuda(), self.dim, None if self.scale is None else self.scale.cuda())
 
     def __getitem__(self, ids):
         return RowRef(self, ids)
 
     def dense(self):
-        """fp32 [n_rows, D] copy (tests / CPU mode)."""
+        """fp32 [n_rows, D] copy (tests / CPU mode); an FP8 store decodes (the row gather over all rows)."""
+        if self.is_fp8:
+            from . import ops
+            return ops.gather_rows(self, torch.arange(self.data.shape[0], device=self.device))
         return self.data[:, :self.dim].float()
+
+    def decoded(self, dtype="bf16", n_rows=None):
+        """The bf16 (or fp32) store that holds the decoded values of this FP8 store (of its first n_rows rows)
+        exactly: every e4m3 value times a power of two is a bf16 number.  What full-neighbourhood inference reads
+        as level 0, and what the FP8 paths are compared against."""
+        assert self.is_fp8 and dtype in ("bf16", "fp32")
+        from . import ops
+        tdt = _DTYPES[dtype]
+        ld = _ld_for(self.dim, tdt)
+        rows = torch.arange(self.data.shape[0] if n_rows is None else int(n_rows), device=self.device)
+        data = ops._gather_mean_fp8_raw(self.data, self.scale, self.dim, rows, int(rows.shape[0]), 1, tdt, ld)
+        return FeatureStore(data, self.dim)
 
 
 class RowRef(object):

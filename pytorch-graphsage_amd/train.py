@@ -23,6 +23,11 @@ when launched under torch.distributed.run (one process per GPU, RCCL grad all-re
   eager           the module path (GSSupervised.train_step), one launch per operator.
 Data-parallel runs keep batches of one fixed size (--batch-size / world per rank, counter-based sampler).
 
+--feature-dtype {native,fp8} (default native: nothing changes): fp8 quantises the problem's feature table after
+loading to one OCP e4m3 byte per element with a power-of-two scale per column (store.FeatureStore.quantize) and says
+on stderr how large the table was and is and the largest absolute error.  The mean engine reads the FP8 table through
+the FP8 gather launch; every other model takes the module path (said on stderr, as for every uncovered model).
+
 Layer-wise full-neighbourhood inference (infer.py, opt-in; the default output is unchanged):
   --full-neighbour-eval   val_metric / test_f1 come from infer.full_neighbour on the val / test folds (deterministic:
                           every neighbour of every node, no sampling) instead of the sampled forward
@@ -205,6 +210,7 @@ def parse_args(argv=None):
     parser.add_argument('--rng', type=str, default='compat', choices=['compat', 'philox'])
     parser.add_argument('--precision', type=str, default='bf16', choices=['bf16', 'fp32'])
     parser.add_argument('--engine', type=str, default='auto', choices=['auto', 'eager', 'fused'])
+    parser.add_argument('--feature-dtype', type=str, default='native', choices=['native', 'fp8'])
     parser.add_argument('--full-neighbour-eval', action="store_true")
     parser.add_argument('--save-embeddings', type=str, default=None)
 
@@ -253,6 +259,12 @@ def main(argv=None, problem=None):
     ddp = gs.dist.init_from_env(args.cuda)            # no-op outside torch.distributed.run
     if problem is None:
         problem = NodeProblem(problem_path=args.problem_path, cuda=args.cuda)
+    if args.feature_dtype == 'fp8':
+        if problem.feats is None:
+            raise SystemExit('gsage: --feature-dtype fp8: this problem has no feature table')
+        before, after, err = problem.quantize_features()
+        print('gsage: feature table quantised to FP8 (e4m3, power-of-two column scales): %.1f MB -> %.1f MB, '
+              'largest absolute error %.4g' % (before / 1e6, after / 1e6, err), file=sys.stderr)
     model = build_model(args, problem)
     if args.cuda:
         model = model.cuda()
