@@ -615,8 +615,11 @@ int gsage_prep_rows_bwd(const void *dhid, int64_t lddh, const void *W0T, int64_t
  *   gsage_lstm_bwd        dh: gradient of out (fp32 [M, lddh]); dG[m n + t] = gradient of step t's pre-activation gates,
  *                         from which d W_ih, d W_hh (= dG^T hprev), the biases (column sums) and d rows (= dG W_ih) follow
  *                         on K5b / K5.  Wp: the BACKWARD copy (second half of gsage_lstm_pack_whh's output); carry: fp32 [M, 2 H]
- *                         scratch (dh_t and dc_t f_t between two steps; may be NULL when n == 1) */
+ *                         scratch (dh_t and dc_t f_t between two steps; may be NULL when n == 1)
+ *   gsage_lstm_tile       [host] sequences per workgroup (16 or 32) that gsage_lstm_fwd (backward == 0) / gsage_lstm_bwd
+ *                         choose for M sequences of H units on the current device; 0 for an H gsage_lstm_ok refuses */
 int gsage_lstm_ok(int dtype, int64_t H, int32_t n);
+int gsage_lstm_tile(int dtype, int64_t M, int64_t H, int backward);
 int64_t gsage_lstm_packed_elems(int64_t H);
 int gsage_lstm_pack_whh(const float *W_hh, int64_t ldw, int64_t H, int dtype, void *Wp, void *stream);
 int gsage_lstm_fwd(void *gates, int dtype, int64_t ldg, const void *Wp, int64_t M, int32_t n, int64_t H, float *cseq,

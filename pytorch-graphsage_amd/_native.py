@@ -155,6 +155,7 @@ SIGNATURES = {
     "gsage_prep_rows_bwd": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i64,
                                    _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "gsage_lstm_ok": (_int, [_int, _i64, _i32]),
+    "gsage_lstm_tile": (_int, [_int, _i64, _i64, _int]),
     "gsage_lstm_packed_elems": (_i64, [_i64]),
     "gsage_lstm_pack_whh": (_int, [_vp, _i64, _i64, _int, _vp, _vp]),
     "gsage_lstm_fwd": (_int, [_vp, _int, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),

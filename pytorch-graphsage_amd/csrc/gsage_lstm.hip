@@ -378,6 +378,12 @@ extern "C" int gsage_lstm_ok(int dtype, int64_t H, int32_t n)
     return H >= 1 && H <= lstm_hmax(dtype) && n >= 1 && n <= LSTM_NMAX ? 1 : 0;
 }
 
+extern "C" int gsage_lstm_tile(int dtype, int64_t M, int64_t H, int backward)
+{
+    if (!gsage_lstm_ok(dtype, H, 1) || M < 0) return 0;
+    return lstm_tile(dtype, M, lstm_hp(H), backward != 0);
+}
+
 extern "C" int64_t gsage_lstm_packed_elems(int64_t H)
 {
     const int64_t Hp = lstm_hp(H);

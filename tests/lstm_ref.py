@@ -23,62 +23,87 @@ def _sigmoid(v):
     return 1.0 / (1.0 + np.exp(-v))
 
 
+def _rounder(rounding):
+    return bf16 if rounding == "bf16" else (lambda a: np.asarray(a, dtype=np.float64))
+
+
+def recurrence(GX, w_hh, dh=None, rounding=None):
+    """The sequential part alone, as gsage_lstm_fwd / _bwd see it: GX [M, steps, 4H] = the projected rows plus both
+    biases (taken as given: the caller rounds it), w_hh [4H, H] (None for one step: no recurrent term), dh [M, H] =
+    gradient of the last h or None.  -> (gates [M, steps, 4H] activated, as saved; c [M, steps, H]; hprev [M, steps, H],
+    row t = the step's INPUT state; out [M, H]; dG [M, steps, 4H] or None)."""
+    r = _rounder(rounding)
+    GX = np.asarray(GX, dtype=np.float64)
+    M, steps, H4 = GX.shape
+    H = H4 // 4
+    Wh = r(w_hh) if w_hh is not None else np.zeros((4 * H, H))
+    assert w_hh is not None or steps == 1
+    h, c = np.zeros((M, H)), np.zeros((M, H))
+    gates, cs, hprev = np.zeros((M, steps, 4 * H)), np.zeros((M, steps, H)), np.zeros((M, steps, H))
+    for t in range(steps):
+        pre = GX[:, t] + h @ Wh.T
+        i, f, g, o = _sigmoid(pre[:, :H]), _sigmoid(pre[:, H:2 * H]), np.tanh(pre[:, 2 * H:3 * H]), _sigmoid(pre[:, 3 * H:])
+        c = f * c + i * g
+        hprev[:, t] = h
+        h = r(o * np.tanh(c))
+        gates[:, t] = r(np.concatenate([i, f, g, o], axis=1))
+        cs[:, t] = c
+    if dh is None:
+        return gates, cs, hprev, h, None
+    dh = np.asarray(dh, dtype=np.float64)
+    dc = np.zeros((M, H))
+    dG = np.zeros((M, steps, 4 * H))
+    for t in range(steps - 1, -1, -1):
+        i, f, g, o = (gates[:, t, k * H:(k + 1) * H] for k in range(4))
+        tc = np.tanh(cs[:, t])
+        cprev = cs[:, t - 1] if t > 0 else np.zeros((M, H))
+        dc = dc + dh * o * (1 - tc * tc)
+        dG[:, t] = r(np.concatenate([dc * g * i * (1 - i), dc * cprev * f * (1 - f), dc * i * (1 - g * g),
+                                     dh * tc * o * (1 - o)], axis=1))
+        dh = dG[:, t] @ Wh
+        dc = dc * f
+    return gates, cs, hprev, h, dG
+
+
 class Direction(object):
     """One LSTM direction over X [M, steps, D]; .out = h after the last step; .backward(dh) fills the gradients."""
 
-    def __init__(self, X, w_ih, w_hh, b_ih, b_hh, rounding=None):
-        r = bf16 if rounding == "bf16" else (lambda a: np.asarray(a, dtype=np.float64))
-        self.r = r
+    def __init__(self, X, w_ih, w_hh, b_ih, b_hh, rounding=None, gx_edit=None):
+        r = _rounder(rounding)
+        self.rounding = rounding
         self.X = r(X)
         self.Wi, self.Wh = r(w_ih), r(w_hh)
         M, steps, _ = self.X.shape
-        H = self.Wh.shape[1]
-        GX = r(self.X @ self.Wi.T + (np.asarray(b_ih, dtype=np.float64) + np.asarray(b_hh, dtype=np.float64)))
-        h, c = np.zeros((M, H)), np.zeros((M, H))
-        self.gates, self.c, self.hprev = [], [], []
-        for t in range(steps):
-            pre = GX[:, t] + h @ self.Wh.T
-            i, f, g, o = _sigmoid(pre[:, :H]), _sigmoid(pre[:, H:2 * H]), np.tanh(pre[:, 2 * H:3 * H]), _sigmoid(pre[:, 3 * H:])
-            c = f * c + i * g
-            self.hprev.append(h)
-            h = r(o * np.tanh(c))
-            self.gates.append(tuple(r(v) for v in (i, f, g, o)))
-            self.c.append(c)
-        self.out, self.H, self.steps = h, H, steps
+        self.GX = r(self.X @ self.Wi.T + (np.asarray(b_ih, dtype=np.float64) + np.asarray(b_hh, dtype=np.float64)))
+        if gx_edit is not None:           # (a sensitivity test's change to the projected rows)
+            self.GX = gx_edit(self.GX)
+        self.gates, self.c, self.hprev, self.out, _ = recurrence(self.GX, self.Wh, None, rounding)
+        self.H, self.steps = self.Wh.shape[1], steps
 
     def backward(self, dh):
         H, M = self.H, self.X.shape[0]
-        dh = np.asarray(dh, dtype=np.float64)
-        dc = np.zeros((M, H))
-        dG = np.zeros((M, self.steps, 4 * H))
-        for t in range(self.steps - 1, -1, -1):
-            i, f, g, o = self.gates[t]
-            tc = np.tanh(self.c[t])
-            cprev = self.c[t - 1] if t > 0 else np.zeros((M, H))
-            dc = dc + dh * o * (1 - tc * tc)
-            dG[:, t] = self.r(np.concatenate([dc * g * i * (1 - i), dc * cprev * f * (1 - f), dc * i * (1 - g * g),
-                                              dh * tc * o * (1 - o)], axis=1))
-            dh = dG[:, t] @ self.Wh
-            dc = dc * f
+        dG = recurrence(self.GX, self.Wh, dh, self.rounding)[4]
+        self.dG = dG
         flat = dG.reshape(M * self.steps, 4 * H)
         self.d_w_ih = flat.T @ self.X.reshape(M * self.steps, -1)
-        self.d_w_hh = flat.T @ np.stack(self.hprev, axis=1).reshape(M * self.steps, H)
+        self.d_w_hh = flat.T @ self.hprev.reshape(M * self.steps, H)
         self.d_b = flat.sum(axis=0)
         self.d_X = dG @ self.Wi
         return self
 
 
-def lstm_last(neibs, M, fwd, rev=None, G=None, rounding=None):
+def lstm_last(neibs, M, fwd, rev=None, G=None, rounding=None, gx_edit=None):
     """neibs [M n, D]; fwd / rev: (w_ih, w_hh, b_ih, b_hh) of a direction (rev None: unidirectional); G: gradient of
-    the result or None.  -> dict(out [M, hidden], and with G: dneibs, grads = [d w_ih, d w_hh, d b_ih, d b_hh] per
-    direction, forward first)."""
+    the result or None; gx_edit(GX [M, n, 4H]) -> GX: a change to the forward direction's projected rows.
+    -> dict(out [M, hidden], dirs = the Direction objects, and with G: dneibs, grads = [d w_ih, d w_hh, d b_ih, d b_hh]
+    per direction, forward first)."""
     neibs = np.asarray(neibs, dtype=np.float64)
     X = neibs.reshape(M, -1, neibs.shape[1])
     n = X.shape[1]
-    dirs = [Direction(X, *fwd, rounding=rounding)]
+    dirs = [Direction(X, *fwd, rounding=rounding, gx_edit=gx_edit)]
     if rev is not None:
         dirs.append(Direction(X[:, n - 1:n], *rev, rounding=rounding))
-    res = {"out": np.concatenate([d.out for d in dirs], axis=1)}
+    res = {"out": np.concatenate([d.out for d in dirs], axis=1), "dirs": dirs}
     if G is None:
         return res
     G = np.asarray(G, dtype=np.float64)

@@ -8,18 +8,16 @@ import torch
 from scipy import sparse
 from torch.nn import functional as F
 
+import lstm_harness
 import lstm_ref
 from conftest import load_golden, pkg
-from util import ACTS, SelReplay, close, close_fro, note_parity, weights
+from util import ACTS, SelReplay, close, weights
 
 pytestmark = pytest.mark.gpu
 gs = pkg()
 ops = gs.ops
 nat = gs._native
 DEV = "cuda"
-
-TOL_BF16 = (4e-2, 4e-2)         # TOL["bf16"] of test_gpu_model.py
-GRAD_BOUND_BF16 = 3e-2          # GRAD_BOUND["bf16"] of test_gpu_engine_shapes.py (relative Frobenius)
 
 
 @pytest.fixture(autouse=True)
@@ -72,44 +70,8 @@ SWEEP = [(1, 1, 7, 2, True), (17, 3, 602, 40, False), (33, 2, 100, 40, True), (6
 def test_shape_sweep_against_the_float64_oracle(case, mode, no_stock_lstm):
     """ops.lstm_last, output and every gradient.  fp32 mode: close(2e-4, 2e-5).  bf16 mode against the rounding-aware
     oracle: output at TOL["bf16"], gradients at 3e-2 relative Frobenius (no ReLU in the recurrence: no mask flips)."""
-    M, n, D, hid, bidir = SWEEP[case]
-    ops.set_compute_dtype(mode)
-    torch.manual_seed(100 + case)
-    lstm = torch.nn.LSTM(D, hid // (1 + bidir), bidirectional=bidir, batch_first=True)
-    rng = np.random.RandomState(case)
-    nb_np = rng.normal(size=(M * n, D)).astype(np.float32)
-    G = lstm_ref.bf16(rng.normal(size=(M, hid))).astype(np.float32)     # bf16-representable: both modes see the same G
-    names = list(lstm_ref.PARAMS) + ([k + "_reverse" for k in lstm_ref.PARAMS] if bidir else [])
-    w_np = [getattr(lstm, k).detach().numpy().copy() for k in names]
-    ref = lstm_ref.lstm_last(nb_np, M, w_np[:4], w_np[4:] if bidir else None, G=G,
-                             rounding="bf16" if mode == "bf16" else None)
-    lstm = lstm.to(DEV)
-    params = [getattr(lstm, k) for k in names]
-    nb = torch.from_numpy(nb_np).to(DEV).requires_grad_(True)
-    out = ops.lstm_last(nb, M, *params[:4], reverse=params[4:] if bidir else None)
-    assert out.shape == (M, hid) and out.dtype == ops.torch_dtype()
-    (out.float() * torch.from_numpy(G).to(DEV)).sum().backward()
-    got = {"out": out.detach().float().cpu().numpy(), "dneibs": nb.grad.cpu().numpy()}
-    want = {"out": ref["out"], "dneibs": ref["dneibs"]}
-    for k, p, r in zip(names, params, ref["grads"]):
-        assert p.grad is not None, k
-        got[k], want[k] = p.grad.cpu().numpy(), r
-    errs = {}
-    for k in got:
-        a, b = np.asarray(got[k], dtype=np.float64), np.asarray(want[k], dtype=np.float64)
-        errs[k + "_maxabs"] = float(np.abs(a - b).max())
-        errs[k + "_fro"] = float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-12))
-    print("lstm sweep case %d %s: %s" % (case + 1, mode, {k: "%.3g" % v for k, v in sorted(errs.items())}))
-    note_parity("lstm_sweep_case%d_%s" % (case + 1, mode), **errs)
-    if bidir:
-        assert not got["weight_hh_l0_reverse"].any()
-    for k in got:
-        if mode == "fp32":
-            close(got[k], want[k], (case, mode, k), 2e-4, 2e-5)
-        elif k == "out":
-            close(got[k], want[k], (case, mode, k), *TOL_BF16)
-        elif np.linalg.norm(want[k]) > 0:
-            close_fro(got[k], want[k], (case, mode, k), GRAD_BOUND_BF16)
+    r = lstm_harness.run(SWEEP[case], mode, case, "lstm_sweep_case%d_%s" % (case + 1, mode))
+    lstm_harness.compare(r, mode, case)
 
 
 def _agg(D, h, hid, bidir):

@@ -46,7 +46,8 @@ def test_bf16_rounding_helper_is_round_to_nearest_even():
 def test_lstm_entry_points_exported_and_bound():
     nat = gs._native
     lib = ctypes.CDLL(nat.LIB_PATH)
-    for name in ("gsage_lstm_fwd", "gsage_lstm_bwd", "gsage_lstm_ok", "gsage_lstm_pack_whh", "gsage_lstm_packed_elems"):
+    for name in ("gsage_lstm_fwd", "gsage_lstm_bwd", "gsage_lstm_ok", "gsage_lstm_pack_whh", "gsage_lstm_packed_elems",
+                 "gsage_lstm_tile"):
         assert hasattr(lib, name), name
         assert name in nat.SIGNATURES, name
     assert hasattr(gs.ops, "lstm_last")
@@ -63,6 +64,9 @@ def test_lstm_ok_says_which_shapes_the_kernels_take():
     assert L.gsage_lstm_ok(nat.BF16, 1024, 4) == 1 and L.gsage_lstm_ok(nat.BF16, 1025, 4) == 0
     assert L.gsage_lstm_ok(nat.F32, 513, 4) == 0
     assert L.gsage_lstm_packed_elems(20) == 8 * 32 * 32 and L.gsage_lstm_packed_elems(512) == 8 * 512 * 512
+    # gsage_lstm_tile: where the LDS image of 32 rows does not fit, 16 whatever M (elsewhere it depends on the CU count)
+    assert L.gsage_lstm_tile(nat.BF16, 1 << 20, 640, 1) == 16 and L.gsage_lstm_tile(nat.F32, 1 << 20, 320, 1) == 16
+    assert L.gsage_lstm_tile(nat.BF16, 49, 40, 0) == 16 and L.gsage_lstm_tile(nat.F32, 49, 513, 0) == 0
 
 
 def test_lstm_bad_arguments_return_einval_without_gpu():
