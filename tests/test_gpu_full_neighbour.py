@@ -37,12 +37,15 @@ def _graph(seed, n=1500, D=602):
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 @pytest.mark.parametrize("agg", AGGS)
-@pytest.mark.parametrize("depth,D", [(2, 602), (3, 50)])
-def test_gpu_matches_float64_reference(agg, depth, D, precision):
+@pytest.mark.parametrize("depth,D,dims", [
+    pytest.param(2, 602, None, id="2-602"), pytest.param(3, 50, None, id="3-50"),
+    # widths 18 and 10: no multiple of the 16-byte chunk in either precision, so infer._table's padding copy runs
+    pytest.param(2, 50, (18, 10), id="2-50-dims18x10")])
+def test_gpu_matches_float64_reference(agg, depth, D, dims, precision):
     gs = pkg()
     gs.ops.set_compute_dtype(precision)
     rng, adj, indptr, data, feats = _graph(depth, D=D)
-    model = make_model(agg, "identity", adj, D, dims=(16,) * (depth - 1) + (24,)).to(DEV)
+    model = make_model(agg, "identity", adj, D, dims=dims or (16,) * (depth - 1) + (24,)).to(DEV)
     store = gs.FeatureStore.from_array(feats, torch.device(DEV), dtype=precision)
     logits, emb = gs.full_neighbour(model, store, embeddings=True)
     ref_logits, ref_emb = reference(model, store.dense().cpu().numpy(), neighbours_sparse(indptr, data))
