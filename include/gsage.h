@@ -1023,6 +1023,52 @@ int gsage_segment_reduce(int mode, const void *table, int dtype, int64_t ld, int
                          int64_t ldp, void *out, int out_dtype, int64_t out_ld, int act, int32_t *err_flag,
                          void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Unsupervised GraphSAGE (csrc/gsage_unsup.hip): random-walk positives, degree^0.75 negatives, skip-gram head
+ *
+ * gsage_unsup_batch -- one launch.  From B seed ids it writes the encoder's id batch
+ *     ids    int64 [2B + Q] = [seeds (B) | positives (B) | negatives (Q)]        pair_w  fp32 [B]
+ * Every draw is a word of Philox4x32-10 (the sampler's generator) under a ROLE TAG xored into the key's high word:
+ *     call       = call_base + (call_ctr ? *call_ctr : 0)           (call_ctr: device word, may be NULL)
+ *     P(c, tag)  = philox4x32_10({lo(c), hi(c), lo(call), hi(call)}, {lo(seed), hi(seed) ^ tag})     (four words)
+ *   Positive of seed i (global index g = g0 + i; a shard [g0, g0 + B) of a larger batch draws what the whole draws):
+ *     t_i  = 1 + ((P(g, 0x4C000000)[0] * walk_len) >> 32)                        (64-bit product; 1 <= walk_len <= 16)
+ *     v    = seeds[i];  for j = 0 .. t_i - 1:
+ *              beg = rowptr[v], deg = rowptr[v + 1] - beg;   deg <= 0: the walk ends at v
+ *              word = P(g, 0x53000000 | (j >> 2))[j & 3]
+ *              off  = deg <= 2^32 - 1 ? (word * deg) >> 32 : word                (64-bit product)
+ *              v    = col[beg + off]
+ *     ids[B + i] = v;  pair_w[i] = (v == seeds[i]) ? 0 : 1;  ids[i] = seeds[i]
+ *     An id outside [0, n_rows) -- a seed, or a node the walk reaches -- raises *err_flag (int32, may be NULL) and
+ *     ends the walk at node 0: ids[B + i] = 0; such a seed is also written as ids[i] = 0 with pair_w[i] = 0.
+ *   Negative q (the same Q ids for every seed and every shard: g0 does not enter):
+ *     r = P(q, 0x4E000000);  u = ((uint64)r[0] << 21 | r[1] >> 11) * 2^-53      (53 bits, exact in a double)
+ *     x = u * cdf_total                                                           (one double multiplication)
+ *     ids[2B + q] = min(first i with cdf[i] > x, n_rows - 1)                      (binary search)
+ *   cdf: DOUBLE [n_rows], the inclusive running sum of non-negative row weights (the model: degree^0.75), so a row of
+ *   weight 0 is never drawn; cdf_total: the HOST's copy of cdf[n_rows - 1], read once when the table is built --
+ *   cdf_total <= 0 (or not finite) is GSAGE_EINVAL before anything is launched.  Q >= 1, 1 <= B < 2^31.
+ * ---------------------------------------------------------------------------------------- */
+int gsage_unsup_batch(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const int64_t *seeds, int64_t B,
+                      int32_t walk_len, int64_t Q, const double *cdf, double cdf_total, uint64_t seed,
+                      const uint64_t *call_ctr, uint64_t call_base, uint64_t g0, int64_t *ids, float *pair_w,
+                      int32_t *err_flag, void *stream);
+
+/* gsage_head_skipgram -- forward + backward in two launches.  E: fp32 [2B + Q, lde], the encoder's un-normalised rows
+ * in the order of gsage_unsup_batch;  z = E / max(||E||_2, 1e-12) row-wise (F.normalize, inside the head):
+ *     a_i  = <z_i, z_{B+i}>          n_iq = <z_i, z_{2B+q}>          softplus(x) = max(x, 0) + log1p(exp(-|x|))
+ *     loss = (1/B) sum_i [ pair_w[i] softplus(-a_i) + neg_weight sum_q softplus(n_iq) ]
+ *   loss: one float.  aff (may be NULL): fp32 [B, 1 + Q] = [a_i | n_i0 .. n_i,Q-1].  dE: [2B + Q, ldd], bf16 or fp32
+ *   (dE_dtype) = d loss / d E, i.e. through the normalisation.  1 <= Q <= 64, 1 <= D <= 1024, lde >= D, ldd >= D.
+ *   Launch 1: a workgroup per 16 seeds writes their rows and their positives' rows of dE, aff, and its partial of
+ *   d z of the negatives and of the loss into scratch (fp32, gsage_head_skipgram_scratch(B, Q, D) elements =
+ *   [ceil(B / 16)][Q * D + 1]).  Launch 2: a workgroup per negative sums the partials in workgroup order and applies
+ *   that row's normalisation backward; it also sums the loss.  No floating-point atomics: same inputs, same bits. */
+int gsage_head_skipgram(const float *E, int64_t lde, int32_t B, int32_t Q, int32_t D, const float *pair_w,
+                        float neg_weight, void *dE, int dE_dtype, int64_t ldd, float *loss, float *aff, float *scratch,
+                        void *stream);
+int64_t gsage_head_skipgram_scratch(int32_t B, int32_t Q, int32_t D);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,451 @@
+// gsage_unsup.hip -- unsupervised GraphSAGE: the batch builder (random-walk positives, degree^0.75 negatives) in one
+// launch and the skip-gram head, forward AND backward, in two.  Definitions: include/gsage.h, "Unsupervised GraphSAGE".
+//
+// The builder is latency, not bandwidth: a lane per seed walks a chain of at most 16 dependent (rowptr -> col) loads,
+// a lane per negative walks a binary search of log2(n_rows) dependent loads; both roles share the launch.
+//
+// The head is k_head_ce (gsage_head.hip) with the normalised negatives in the role of fc.weight and the loss
+// exchanged: B x Q x D = 512 x 20 x 256 is 2.6 MFLOP, so the cost is launches and dependent phases, not flops.  A
+// workgroup keeps its 16 normalised seed rows in LDS, streams the negatives' rows from L2 (64 x 1024 floats do not fit
+// beside them), and leaves one partial of d z_neg per workgroup for the second launch to sum in a fixed order.
+#include "gsage_common.h"
+
+namespace gsage {
+
+constexpr uint32_t UNSUP_TAG_LEN = 0x4C000000u;     // walk length
+constexpr uint32_t UNSUP_TAG_STEP = 0x53000000u;    // | (step >> 2): walk steps, four to a Philox block
+constexpr uint32_t UNSUP_TAG_NEG = 0x4E000000u;     // negatives
+constexpr int UNSUP_WALK_MAX = 16;
+
+struct UnsupParams {
+    const int64_t *rowptr;
+    const int32_t *col;
+    const int64_t *seeds;
+    const double *cdf;
+    const uint64_t *call_ctr;
+    int64_t *ids;
+    float *pair_w;
+    int32_t *err_flag;
+    int64_t n_rows, B, Q;
+    uint64_t call_base, g0;
+    double cdf_total;
+    uint32_t seed_lo, seed_hi;
+    int32_t walk_len, walk_blocks;
+};
+
+__device__ __forceinline__ philox4 unsup_philox(const UnsupParams &p, uint64_t c, uint64_t call, uint32_t tag)
+{
+    return philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), (uint32_t)call, (uint32_t)(call >> 32), p.seed_lo,
+                         p.seed_hi ^ tag);
+}
+
+// blocks [0, walk_blocks): a lane per seed;  the rest: a lane per negative
+__global__ void __launch_bounds__(256)
+k_unsup_batch(const UnsupParams p)
+{
+    const uint64_t call = p.call_base + (p.call_ctr ? *p.call_ctr : 0ull);
+    if ((int)blockIdx.x < p.walk_blocks) {
+        const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+        if (i >= p.B) return;
+        const int64_t s = p.seeds[i];
+        const uint64_t g = p.g0 + (uint64_t)i;
+        if ((uint64_t)s >= (uint64_t)p.n_rows) {
+            if (p.err_flag) *p.err_flag = 1;
+            p.ids[i] = 0;
+            p.ids[p.B + i] = 0;
+            p.pair_w[i] = 0.f;
+            return;
+        }
+        const uint32_t wl = unsup_philox(p, g, call, UNSUP_TAG_LEN).v[0];
+        const int t = 1 + (int)(((uint64_t)wl * (uint64_t)(uint32_t)p.walk_len) >> 32);
+        int64_t v = s;
+        philox4 r = {};
+        for (int j = 0; j < t; ++j) {
+            const int64_t beg = p.rowptr[v];
+            const int64_t deg = p.rowptr[v + 1] - beg;
+            if (deg <= 0) break;
+            if ((j & 3) == 0) r = unsup_philox(p, g, call, UNSUP_TAG_STEP | (uint32_t)(j >> 2));
+            const int w4 = j & 3;                               // selects, not r.v[j & 3]: no scratch
+            const uint32_t word = w4 == 0 ? r.v[0] : w4 == 1 ? r.v[1] : w4 == 2 ? r.v[2] : r.v[3];
+            const uint64_t off = (deg <= 0xffffffffLL) ? ((uint64_t)word * (uint64_t)deg) >> 32 : (uint64_t)word;
+            v = (int64_t)p.col[beg + (int64_t)off];
+            if ((uint64_t)v >= (uint64_t)p.n_rows) {
+                if (p.err_flag) *p.err_flag = 1;
+                v = 0;
+                break;
+            }
+        }
+        p.ids[i] = s;
+        p.ids[p.B + i] = v;
+        p.pair_w[i] = v == s ? 0.f : 1.f;
+        return;
+    }
+    const int64_t q = (int64_t)((int)blockIdx.x - p.walk_blocks) * 256 + threadIdx.x;
+    if (q >= p.Q) return;
+    const philox4 r = unsup_philox(p, (uint64_t)q, call, UNSUP_TAG_NEG);
+    const uint64_t u53 = ((uint64_t)r.v[0] << 21) | (uint64_t)(r.v[1] >> 11);
+    const double x = ((double)u53 * 0x1p-53) * p.cdf_total;
+    int64_t lo = 0, hi = p.n_rows - 1;                          // first i with cdf[i] > x, clamped to the last row
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (p.cdf[mid] > x) hi = mid; else lo = mid + 1;
+    }
+    p.ids[2 * p.B + q] = lo;
+}
+
+
+// ---- skip-gram head ------------------------------------------------------------------------------------------------
+constexpr int SG_QMAX = 64;        // negatives
+constexpr int SG_DMAX = 1024;      // embedding width
+constexpr int SG_ROWS = 16;        // seeds per workgroup
+
+struct SkipgramParams {
+    const float *E;          // [2B + Q, lde]
+    const float *pair_w;     // [B]
+    void *dE;                // [2B + Q, ldd]
+    float *aff;              // [B, 1 + Q] or NULL
+    float *partial;          // [n_wg][Q * D + 1]: d z_neg | loss
+    float *loss;
+    int64_t lde, ldd;
+    int32_t B, Q, D, dE_dtype, n_wg;
+    float neg_weight;
+};
+
+__device__ __forceinline__ float sg_wave_sum(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float sg_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float sg_sigmoid(float x)
+{
+    const float e = expf(-fabsf(x));
+    return (x >= 0.f ? 1.f : e) / (1.f + e);
+}
+
+__device__ __forceinline__ void sg_store(const SkipgramParams &p, int64_t row, int k, float g)
+{
+    if (p.dE_dtype == GSAGE_BF16)
+        ((uint16_t *)p.dE)[row * p.ldd + k] = f32_to_bf16(g);
+    else
+        ((float *)p.dE)[row * p.ldd + k] = g;
+}
+
+// 16 per-lane partial sums -> 16 wave sums with 17 shuffles instead of 96: every exchange step halves the values a
+// lane carries.  Afterwards v[0] of lane l is the whole wave's sum of value (l >> 2) & 15.
+__device__ __forceinline__ float sg_reduce16(float (&v)[SG_ROWS], int lane)
+{
+#pragma unroll
+    for (int half = 8, o = 32; half >= 1; half >>= 1, o >>= 1) {
+        const bool up = (lane & o) != 0;
+#pragma unroll
+        for (int j = 0; j < half; ++j) {
+            const float send = up ? v[j] : v[j + half];
+            const float keep = up ? v[j + half] : v[j];
+            v[j] = keep + __shfl_xor(send, o, 64);
+        }
+    }
+    float s = v[0];
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 1, 64);
+    return s;
+}
+
+// NJ = ceil(D / 64): columns a lane holds of one row (4, 8 or 16).  Thread t of the column phase owns columns t + 256 j.
+template <int NJ>
+__global__ void __launch_bounds__(256)
+k_head_skipgram(const SkipgramParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int D = p.D, Q = p.Q, B = p.B;
+    float *nT = lds;                                  // [SG_QMAX][16] n_iq           (16-byte rows: ds_read_b128)
+    float *dT = nT + SG_QMAX * SG_ROWS;               // [SG_QMAX][16] d n_iq
+    float *sinv = dT + SG_QMAX * SG_ROWS;             // [16] 1 / norm of the seed rows
+    float *pinv = sinv + SG_ROWS;                     // [16] ... of the positives' rows
+    float *av = pinv + SG_ROWS;                       // [16] a_i
+    float *dav = av + SG_ROWS;                        // [16] d a_i
+    float *zdz = dav + SG_ROWS;                       // [16] <z_i, d z_i>
+    float *ninv = zdz + SG_ROWS;                      // [SG_QMAX] 1 / norm of the negatives' rows
+    float *red = ninv + SG_QMAX;                      // [4] (+ 12 of padding)
+    float *zs = red + 16;                             // [16][D] normalised seed rows (zero rows past B)
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row0 = blockIdx.x * SG_ROWS;
+    const float *__restrict__ E = p.E;
+    const float *__restrict__ En = E + (int64_t)2 * B * p.lde;     // the negatives' rows
+
+    // 1. norms of the 16 seed rows and of their positives, a_i, the normalised seed rows -> LDS (wave w: rows w + 4 m)
+#pragma unroll
+    for (int m = 0; m < SG_ROWS / 4; ++m) {
+        const int r = wave + 4 * m, i = row0 + r;
+        float es[NJ], ep[NJ], ss = 0.f, sp = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = lane + 64 * j;
+            const bool ok = k < D && i < B;
+            es[j] = ok ? E[(int64_t)i * p.lde + k] : 0.f;
+            ep[j] = ok ? E[((int64_t)B + i) * p.lde + k] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { ss += es[j] * es[j]; sp += ep[j] * ep[j]; }
+        const float ns = fmaxf(sqrtf(sg_wave_sum(ss)), 1e-12f), np = fmaxf(sqrtf(sg_wave_sum(sp)), 1e-12f);
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = lane + 64 * j;
+            const float z = es[j] / ns;
+            a += z * (ep[j] / np);
+            if (k < D) zs[r * D + k] = z;
+        }
+        a = sg_wave_sum(a);
+        if (lane == 0) { sinv[r] = 1.f / ns; pinv[r] = 1.f / np; av[r] = a; }
+    }
+    __syncthreads();
+
+    // 2. n_iq for the 16 rows: wave w takes negatives w, w + 4, ...; the next negative's row is in flight meanwhile
+    {
+        float cur[NJ], nxt[NJ];
+        auto fetch = [&](int q, float (&buf)[NJ]) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int k = lane + 64 * j;
+                buf[j] = (k < D && q < Q) ? En[(int64_t)q * p.lde + k] : 0.f;
+            }
+        };
+        fetch(wave, cur);
+        for (int q = wave; q < Q; q += 4) {
+            fetch(q + 4, nxt);
+            float acc[SG_ROWS], ss = 0.f;
+#pragma unroll
+            for (int r = 0; r < SG_ROWS; ++r) acc[r] = 0.f;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int k = lane + 64 * j;
+                if (k < D) {                                   // (keeps the LDS reads inside zs)
+                    const float e = cur[j];
+                    ss += e * e;
+#pragma unroll
+                    for (int r = 0; r < SG_ROWS; ++r) acc[r] += zs[r * D + k] * e;
+                }
+            }
+            const float inv = 1.f / fmaxf(sqrtf(sg_wave_sum(ss)), 1e-12f);
+            const float dot = sg_reduce16(acc, lane);
+            if ((lane & 3) == 0) nT[q * SG_ROWS + ((lane >> 2) & 15)] = dot * inv;
+            if (lane == 0) ninv[q] = inv;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) cur[j] = nxt[j];
+        }
+    }
+    __syncthreads();
+
+    // 3. loss, aff, d n_iq; then (a lane per row) d a_i and <z_i, d z_i> = d a_i a_i + sum_q d n_iq n_iq
+    const float invB = 1.f / (float)B;
+    float my_loss = 0.f;
+    for (int e = tid; e < Q * SG_ROWS; e += 256) {
+        const int q = e >> 4, i = row0 + (e & 15);
+        float dn = 0.f;
+        if (i < B) {
+            const float n = nT[e];
+            if (p.aff) p.aff[(int64_t)i * (1 + Q) + 1 + q] = n;
+            my_loss += p.neg_weight * sg_softplus(n);
+            dn = p.neg_weight * invB * sg_sigmoid(n);
+        }
+        dT[e] = dn;
+    }
+    __syncthreads();
+    if (tid < SG_ROWS) {
+        const int r = tid, i = row0 + r;
+        float da = 0.f, s = 0.f;
+        if (i < B) {
+            const float a = av[r], w = p.pair_w[i];
+            if (p.aff) p.aff[(int64_t)i * (1 + Q)] = a;
+            my_loss += w * sg_softplus(-a);
+            da = -w * invB * sg_sigmoid(-a);
+            s = da * a;
+            for (int q = 0; q < Q; ++q) s += dT[q * SG_ROWS + r] * nT[q * SG_ROWS + r];
+        }
+        dav[r] = da;
+        zdz[r] = s;
+    }
+    my_loss = sg_wave_sum(my_loss);
+    if (lane == 0) red[wave] = my_loss;
+    __syncthreads();
+
+    // 4. thread <-> column: d z_i = d a_i z_pos + sum_q d n_iq z_neg_q, this workgroup's partial of
+    //    d z_neg_q = sum_i d n_iq z_i, then the two gradient rows of every seed through their normalisations
+    float *__restrict__ out = p.partial + (int64_t)blockIdx.x * ((int64_t)Q * D + 1);
+    if (tid == 0) out[(int64_t)Q * D] = (red[0] + red[1]) + (red[2] + red[3]);
+    for (int k = tid; k < D; k += 256) {
+        float z[SG_ROWS], dz[SG_ROWS], zp[SG_ROWS];
+#pragma unroll
+        for (int r = 0; r < SG_ROWS; ++r) {
+            z[r] = zs[r * D + k];
+            dz[r] = 0.f;
+            zp[r] = (row0 + r < B) ? E[((int64_t)B + row0 + r) * p.lde + k] : 0.f;
+        }
+        for (int q0 = 0; q0 < Q; q0 += 4) {
+            float en[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) en[u] = (q0 + u < Q) ? En[(int64_t)(q0 + u) * p.lde + k] : 0.f;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (q0 + u < Q) {                              // block-uniform
+                    const float zn = en[u] * ninv[q0 + u];
+                    const float4 *dn4 = (const float4 *)(dT + (q0 + u) * SG_ROWS);
+                    float dzn = 0.f;
+#pragma unroll
+                    for (int h = 0; h < SG_ROWS / 4; ++h) {
+                        const float4 d = dn4[h];
+                        dz[4 * h + 0] += d.x * zn; dzn += d.x * z[4 * h + 0];
+                        dz[4 * h + 1] += d.y * zn; dzn += d.y * z[4 * h + 1];
+                        dz[4 * h + 2] += d.z * zn; dzn += d.z * z[4 * h + 2];
+                        dz[4 * h + 3] += d.w * zn; dzn += d.w * z[4 * h + 3];
+                    }
+                    out[(int64_t)(q0 + u) * D + k] = dzn;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < SG_ROWS; ++r) {
+            const int i = row0 + r;
+            if (i < B) {                                       // block-uniform
+                const float da = dav[r], zpos = zp[r] * pinv[r];
+                sg_store(p, i, k, (da * zpos + dz[r] - z[r] * zdz[r]) * sinv[r]);
+                sg_store(p, (int64_t)B + i, k, da * (z[r] - zpos * av[r]) * pinv[r]);     // <z_pos, d z_pos> = d a_i a_i
+            }
+        }
+    }
+}
+
+// A workgroup per negative q: d z_neg_q = the partials summed in workgroup order, then that row's normalisation
+// backward.  Workgroup 0 also sums the loss.  Thread t owns columns t + 256 j.
+__global__ void __launch_bounds__(256)
+k_head_skipgram_neg(const SkipgramParams p)
+{
+    __shared__ float red[4];
+    const int D = p.D, q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t width = (int64_t)p.Q * D + 1;
+    const int64_t row = (int64_t)2 * p.B + q;
+    auto block_sum = [&](float v) {
+        v = sg_wave_sum(v);
+        __syncthreads();
+        if (lane == 0) red[wave] = v;
+        __syncthreads();
+        return (red[0] + red[1]) + (red[2] + red[3]);
+    };
+    float e[SG_DMAX / 256], dz[SG_DMAX / 256], ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < SG_DMAX / 256; ++j) {
+        const int k = tid + 256 * j;
+        e[j] = k < D ? p.E[row * p.lde + k] : 0.f;
+        float s = 0.f;
+        if (k < D) {
+            const float *col = p.partial + (int64_t)q * D + k;
+            int g = 0;
+            for (; g + 8 <= p.n_wg; g += 8) {                  // 8 loads in flight, summed in order
+                float v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = col[(int64_t)(g + u) * width];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) s += v[u];
+            }
+            for (; g < p.n_wg; ++g) s += col[(int64_t)g * width];
+        }
+        dz[j] = s;
+        ss += e[j] * e[j];
+    }
+    const float nrm = fmaxf(sqrtf(block_sum(ss)), 1e-12f);
+    float zd = 0.f;
+#pragma unroll
+    for (int j = 0; j < SG_DMAX / 256; ++j) { e[j] = e[j] / nrm; zd += e[j] * dz[j]; }
+    zd = block_sum(zd);
+#pragma unroll
+    for (int j = 0; j < SG_DMAX / 256; ++j) {
+        const int k = tid + 256 * j;
+        if (k < D) sg_store(p, row, k, (dz[j] - e[j] * zd) / nrm);
+    }
+    if (q == 0 && wave == 0) {                                 // the loss: lanes over the workgroups, a fixed tree
+        float l = 0.f;
+        for (int g = lane; g < p.n_wg; g += 64) l += p.partial[(int64_t)g * width + width - 1];
+        l = sg_wave_sum(l);
+        if (lane == 0) *p.loss = l / (float)p.B;
+    }
+}
+
+template <typename K>
+static int sg_raise_lds(K kernel, size_t lds, bool &done)
+{
+    if (done || lds <= 64 * 1024) return GSAGE_OK;
+    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("head_skipgram: cannot raise the dynamic LDS limit");
+        return GSAGE_ELAUNCH;
+    }
+    done = true;
+    return GSAGE_OK;
+}
+
+}  // namespace gsage
+
+using namespace gsage;
+
+extern "C" {
+
+int gsage_unsup_batch(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const int64_t *seeds, int64_t B,
+                      int32_t walk_len, int64_t Q, const double *cdf, double cdf_total, uint64_t seed,
+                      const uint64_t *call_ctr, uint64_t call_base, uint64_t g0, int64_t *ids, float *pair_w,
+                      int32_t *err_flag, void *stream)
+{
+    GSAGE_REQUIRE(rowptr && col && seeds && cdf && ids && pair_w, "unsup_batch: null pointer");
+    GSAGE_REQUIRE(n_rows > 0 && B > 0 && B < (1LL << 31) && Q > 0 && Q < (1LL << 31), "unsup_batch: bad sizes");
+    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= UNSUP_WALK_MAX, "unsup_batch: needs 1 <= walk_len <= %d", UNSUP_WALK_MAX);
+    GSAGE_REQUIRE(cdf_total > 0.0 && cdf_total <= 1.7976931348623157e308,
+                  "unsup_batch: the negatives' weights sum to %g (every row has weight 0?)", cdf_total);
+    UnsupParams p;
+    p.rowptr = rowptr; p.col = col; p.seeds = seeds; p.cdf = cdf; p.call_ctr = call_ctr; p.ids = ids; p.pair_w = pair_w;
+    p.err_flag = err_flag; p.n_rows = n_rows; p.B = B; p.Q = Q; p.call_base = call_base; p.g0 = g0;
+    p.cdf_total = cdf_total; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
+    p.walk_len = walk_len; p.walk_blocks = (int32_t)ceil_div(B, 256);
+    launch(k_unsup_batch, dim3((unsigned)(p.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream, p);
+    return check_launch("unsup_batch");
+}
+
+int64_t gsage_head_skipgram_scratch(int32_t B, int32_t Q, int32_t D)
+{
+    if (B <= 0 || Q <= 0 || D <= 0) return -1;
+    return ceil_div(B, SG_ROWS) * ((int64_t)Q * D + 1);
+}
+
+int gsage_head_skipgram(const float *E, int64_t lde, int32_t B, int32_t Q, int32_t D, const float *pair_w,
+                        float neg_weight, void *dE, int dE_dtype, int64_t ldd, float *loss, float *aff, float *scratch,
+                        void *stream)
+{
+    GSAGE_REQUIRE(E && pair_w && dE && loss && scratch, "head_skipgram: null pointer");
+    GSAGE_REQUIRE(B > 0 && Q > 0 && Q <= SG_QMAX && D > 0 && D <= SG_DMAX,
+                  "head_skipgram: needs 1 <= n_negatives <= %d and 1 <= width <= %d", SG_QMAX, SG_DMAX);
+    GSAGE_REQUIRE(lde >= D && ldd >= D, "head_skipgram: leading dimensions smaller than the width");
+    GSAGE_REQUIRE(dE_dtype == GSAGE_BF16 || dE_dtype == GSAGE_F32, "head_skipgram: bad dE dtype");
+    SkipgramParams p;
+    p.E = E; p.pair_w = pair_w; p.dE = dE; p.aff = aff; p.partial = scratch; p.loss = loss; p.lde = lde; p.ldd = ldd;
+    p.B = B; p.Q = Q; p.D = D; p.dE_dtype = dE_dtype; p.n_wg = (int32_t)ceil_div(B, SG_ROWS); p.neg_weight = neg_weight;
+    const size_t lds = sizeof(float) * (2 * SG_QMAX * SG_ROWS + 5 * SG_ROWS + SG_QMAX + 16 + (size_t)SG_ROWS * D);
+    hipStream_t s = (hipStream_t)stream;
+    if (D <= 256) {
+        launch(k_head_skipgram<4>, dim3(p.n_wg), dim3(256), lds, s, p);
+    } else if (D <= 512) {
+        launch(k_head_skipgram<8>, dim3(p.n_wg), dim3(256), lds, s, p);
+    } else {
+        static bool raised = false;
+        const int rc = sg_raise_lds(k_head_skipgram<16>, lds, raised);
+        if (rc != GSAGE_OK) return rc;
+        launch(k_head_skipgram<16>, dim3(p.n_wg), dim3(256), lds, s, p);
+    }
+    int rc = check_launch("head_skipgram");
+    if (rc != GSAGE_OK) return rc;
+    launch(k_head_skipgram_neg, dim3(Q), dim3(256), 0, s, p);
+    return check_launch("head_skipgram_neg");
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 """
-infer.py -- layer-wise full-neighbourhood inference and node-embedding export for a trained GSSupervised.
+infer.py -- layer-wise full-neighbourhood inference and node-embedding export for a trained GSSupervised or
+GSUnsupervised.
 
 The sampled forward (`model(ids, feats, train=False)`) draws new neighbour samples on every call and pays, per seed,
 the product of the fan-outs.  Here every layer is computed ONCE for every row of the adjacency, over each row's
@@ -221,9 +222,9 @@ def _feature_rows(feats, n):
     return feats[:n]
 
 
-def full_neighbour(model, feats, nodes=None, adj=None, embeddings=False):
-    """Logits of `model` for `nodes` (default: every row of the adjacency) by layer-wise full-neighbourhood inference,
-    and, with embeddings=True, also F.normalize(H^L) for every row: returns (logits, emb).
+def embeddings(model, feats, adj=None):
+    """F.normalize(H^L) of every row of the adjacency, [n_rows, width], by layer-wise full-neighbourhood inference --
+    for a GSSupervised (the rows its `fc` classifies) and for a GSUnsupervised (its output).
 
     feats: a FeatureStore or a tensor; its device decides the route (CUDA: the library's kernels, CPU: host mode).
     adj: a store.DeviceCSR / store.DenseAdj; default: the adjacency evaluation samples from (model.val_sampler).
@@ -250,10 +251,22 @@ def full_neighbour(model, feats, nodes=None, adj=None, embeddings=False):
             edges = _edges(adj)
             for layer in model.agg_layers.children():
                 H = _layer_host(layer, H, edges)
-        emb = F.normalize(H.float(), dim=1)
+        return F.normalize(H.float(), dim=1)
+
+
+def full_neighbour(model, feats, nodes=None, adj=None, embeddings=False):
+    """Logits of `model` for `nodes` (default: every row of the adjacency) by layer-wise full-neighbourhood inference,
+    and, with embeddings=True, also F.normalize(H^L) for every row: returns (logits, emb).  Arguments as for
+    embeddings() above, which computes emb; this applies the model's `fc` to it."""
+    emb = _embeddings(model, feats, adj=adj)
+    dev = feats.device
+    with torch.no_grad():
         sel = emb if nodes is None else emb[torch.as_tensor(nodes, device=dev).long().view(-1)]
         if dev.type == "cuda":
             logits = ops.linear(sel, model.fc.weight, model.fc.bias, compute_dtype="fp32")
         else:
             logits = model.fc(sel)
     return (logits, emb) if embeddings else logits
+
+
+_embeddings = embeddings          # (full_neighbour's keyword of the same name shadows the function inside it)

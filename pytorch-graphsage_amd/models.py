@@ -1,5 +1,6 @@
 """
-models.py -- GSSupervised, the layer-stacking loop and train_step (reference models.py:21-104),
+models.py -- GSSupervised, the layer-stacking loop and train_step (reference models.py:21-104), and
+GSUnsupervised, the same encoder under a skip-gram loss (no reference counterpart).  GSSupervised is
 kept drop-in: same constructor keywords (as passed at train.py:94-123), same methods
 (`forward(ids, feats, train)`, `set_progress`, `train_step`), same parameter names.
 
@@ -19,15 +20,16 @@ import os
 from . import ops
 from .lr import LRSchedule
 from .optim import FlatAdam
-from .store import FeatureStore
+from .store import DenseAdj, DeviceCSR, FeatureStore
 
 
-class GSSupervised(nn.Module):
-    def __init__(self, input_dim, n_nodes, n_classes, layer_specs, aggregator_class, prep_class,
-                 sampler_class, adj, train_adj, lr_init=0.01, weight_decay=0.0,
-                 lr_schedule='constant', epochs=10):
-        super(GSSupervised, self).__init__()
+class _SageModel(nn.Module):
+    """What GSSupervised and GSUnsupervised share: samplers, prep, the aggregator stack (_build_encoder), the frontier
+    and layer-stacking loop (_encode), the learning-rate schedule and the optimizer route."""
 
+    def _build_encoder(self, input_dim, n_nodes, layer_specs, aggregator_class, prep_class, sampler_class, adj,
+                       train_adj):
+        """-> the width of the top-level rows"""
         # samplers: training walks train_adj, evaluation the full graph (models.py:41-44)
         self.train_sampler = sampler_class(adj=train_adj)
         self.val_sampler = sampler_class(adj=adj)
@@ -46,8 +48,9 @@ class GSSupervised(nn.Module):
             stack.append(layer)
             width = layer.output_dim          # 2 * output_dim for the concat (models.py:59)
         self.agg_layers = nn.Sequential(*stack)
-        self.fc = nn.Linear(width, n_classes, bias=True)
+        return width
 
+    def _build_optimizer(self, lr_init, weight_decay, lr_schedule):
         # schedule is a function of progress only: `epochs` is not forwarded (models.py:67)
         self.lr_scheduler = partial(getattr(LRSchedule, lr_schedule), lr_init=lr_init)
         self.lr = self.lr_scheduler(0.0)
@@ -68,7 +71,8 @@ class GSSupervised(nn.Module):
             self._wrapped = {key: FeatureStore.wrap(feats)}
         return self._wrapped[key]
 
-    def forward(self, ids, feats, train=True):
+    def _encode(self, ids, feats, train=True):
+        """The un-normalised top-level rows [len(ids), width] (fp32) of `ids`: frontier, prep, layer stack."""
         # a fused engine that defers the embedding table's zero-gradient Adam updates (engine.sync_rows)
         # settles them HERE: the prep reads `embedding.weight` directly, not through the nn.Embedding
         # module, so a hook on that module would never fire
@@ -89,13 +93,7 @@ class GSSupervised(nn.Module):
         for layer in self.agg_layers.children():
             hops = [layer(hops[k], hops[k + 1]) for k in range(len(hops) - 1)]
         assert len(hops) == 1, "len(all_feats) != 1"
-
-        out = F.normalize(hops[0].float(), dim=1)
-        if out.is_cuda:
-            # the head's projection on K5 in exact fp32 (models.py:91 is an nn.Linear: a library GEMM on the GPU
-            # otherwise -- the last one of the module path, forward and backward)
-            return ops.linear(out, self.fc.weight, self.fc.bias, compute_dtype="fp32")
-        return self.fc(out)
+        return hops[0].float()
 
     def __getstate__(self):
         # per-process handles of a fused engine (a weakref and a bound method) do not pickle / deep-copy
@@ -107,6 +105,15 @@ class GSSupervised(nn.Module):
     def set_progress(self, progress):
         self.lr = self.lr_scheduler(progress)
         LRSchedule.set_lr(self.optimizer, self.lr)
+
+    def _clip_and_step(self, flat):
+        if self.grad_sync is not None:
+            self.grad_sync(self)
+        if flat is not None:
+            flat.clip_and_step(5.0)               # models.py:101-102 in two launches
+        else:
+            torch.nn.utils.clip_grad_norm_(self.parameters(), 5)
+            self.optimizer.step()
 
     def _flat_optimizer(self):
         """On the GPU the optimizer built in __init__ (torch.optim.Adam, never stepped yet) is replaced,
@@ -162,17 +169,111 @@ class GSSupervised(nn.Module):
             return eng.optimizer_state_dict()
         return self.optimizer.state_dict()
 
+
+class GSSupervised(_SageModel):
+    def __init__(self, input_dim, n_nodes, n_classes, layer_specs, aggregator_class, prep_class,
+                 sampler_class, adj, train_adj, lr_init=0.01, weight_decay=0.0,
+                 lr_schedule='constant', epochs=10):
+        super(GSSupervised, self).__init__()
+        width = self._build_encoder(input_dim, n_nodes, layer_specs, aggregator_class, prep_class, sampler_class,
+                                    adj, train_adj)
+        self.fc = nn.Linear(width, n_classes, bias=True)
+        self._build_optimizer(lr_init, weight_decay, lr_schedule)
+
+    def forward(self, ids, feats, train=True):
+        out = F.normalize(self._encode(ids, feats, train), dim=1)
+        if out.is_cuda:
+            # the head's projection on K5 in exact fp32 (models.py:91 is an nn.Linear: a library GEMM on the GPU
+            # otherwise -- the last one of the module path, forward and backward)
+            return ops.linear(out, self.fc.weight, self.fc.bias, compute_dtype="fp32")
+        return self.fc(out)
+
     def train_step(self, ids, feats, targets, loss_fn):
         flat = self._flat_optimizer()
         self.optimizer.zero_grad()
         preds = self(ids, feats, train=True)
         loss = loss_fn(preds, targets.squeeze())
         loss.backward()
-        if self.grad_sync is not None:
-            self.grad_sync(self)
-        if flat is not None:
-            flat.clip_and_step(5.0)               # models.py:101-102 in two launches
-        else:
-            torch.nn.utils.clip_grad_norm_(self.parameters(), 5)
-            self.optimizer.step()
+        self._clip_and_step(flat)
         return preds
+
+
+class GSUnsupervised(_SageModel):
+    """The same encoder trained without labels: random-walk co-occurrence positives, degree^0.75 negatives and a
+    skip-gram loss on the cosines of the embeddings (include/gsage.h, "Unsupervised GraphSAGE").  Constructor keywords
+    of GSSupervised minus n_classes; no `fc`: the model's output IS the embedding, F.normalize of the top-level rows
+    (what infer.embeddings / train.py --save-embeddings export for every node).
+
+    A step encodes [seeds (B) | positives (B) | negatives (Q)] in ONE pass of the module path.  The walks run on the
+    adjacency the step's sampler walks (train_adj for training, adj for evaluation) and draw from Philox under the
+    neighbour sampler's seed with role tags of their own, whatever --rng the neighbour sampler uses."""
+
+    def __init__(self, input_dim, n_nodes, layer_specs, aggregator_class, prep_class, sampler_class, adj, train_adj,
+                 lr_init=0.01, weight_decay=0.0, lr_schedule='constant', epochs=10, walk_len=5, n_negatives=20,
+                 neg_weight=1.0):
+        super(GSUnsupervised, self).__init__()
+        assert 1 <= walk_len <= 16 and 1 <= n_negatives <= 64, "GSUnsupervised: walk_len in 1..16, n_negatives in 1..64"
+        self.output_dim = self._build_encoder(input_dim, n_nodes, layer_specs, aggregator_class, prep_class,
+                                              sampler_class, adj, train_adj)
+        self.walk_len, self.n_negatives, self.neg_weight = int(walk_len), int(n_negatives), float(neg_weight)
+        self._build_optimizer(lr_init, weight_decay, lr_schedule)
+        self._walk = {}                       # (train, device) -> (DeviceCSR, negatives' table)
+        self._batch_calls = [0, 0]            # Philox call index of the next batch: evaluation, training
+
+    def extra_repr(self):
+        return "walk_len=%d, n_negatives=%d, neg_weight=%g" % (self.walk_len, self.n_negatives, self.neg_weight)
+
+    def forward(self, ids, feats, train=True):
+        return F.normalize(self._encode(ids, feats, train), dim=1)
+
+    def _walk_graph(self, train, device):
+        key = (bool(train), str(device))
+        if key not in self._walk:
+            sampler = self.train_sampler if train else self.val_sampler
+            csr = sampler.csr(device)
+            if isinstance(csr, DenseAdj):     # the dense sampler's [n, K] table read as K edges per row
+                rowptr = torch.arange(csr.n_rows + 1, dtype=torch.int64, device=csr.device) * csr.K
+                csr = DeviceCSR(rowptr, csr.adj.reshape(-1).to(torch.int32), csr.n_rows, csr.K)
+            self._walk[key] = (csr, ops.neg_cdf(csr))
+        return self._walk[key]
+
+    def build_batch(self, ids, train=True):
+        """-> (ids [2B + Q] = [seeds | positives | negatives], pair_w [B]) for the seeds `ids` (ops.unsup_batch)."""
+        ids = ids.contiguous().view(-1)
+        csr, cdf = self._walk_graph(train, ids.device)
+        sampler = self.train_sampler if train else self.val_sampler
+        rank, _ = getattr(sampler, "shard", (0, 1))
+        ph = {"seed": int(getattr(sampler, "seed", 0)), "call_base": self._batch_calls[int(train)],
+              "g0": rank * int(ids.shape[0])}
+        self._batch_calls[int(train)] += 1
+        return ops.unsup_batch(csr, ids, self.walk_len, self.n_negatives, cdf, ph)
+
+    def _loss_inputs(self, ids, feats, batch, train):
+        all_ids, pair_w = batch if batch is not None else self.build_batch(ids, train=train)
+        B = int(pair_w.shape[0])
+        Q = int(all_ids.shape[0]) - 2 * B
+        assert Q >= 1, "GSUnsupervised: a batch is [seeds (B) | positives (B) | negatives (Q >= 1)]"
+        return self._encode(all_ids, feats, train=train), B, Q, pair_w
+
+    def train_step(self, ids, feats, batch=None):
+        """One optimisation step on the seeds `ids` (or on an explicit batch = (ids [2B + Q], pair_w [B])): the loss."""
+        flat = self._flat_optimizer()
+        self.optimizer.zero_grad()
+        E, B, Q, pair_w = self._loss_inputs(ids, feats, batch, True)
+        loss = ops.skipgram_loss(E, B, Q, pair_w, self.neg_weight)
+        loss.backward()
+        self._clip_and_step(flat)
+        return loss.detach()
+
+    def evaluate(self, ids, feats, batch=None):
+        """{"loss", "mrr"} of the seeds `ids` on the evaluation graph: mrr = mean of 1 / rank of a_i among
+        [a_i, n_i1 .. n_iQ] (rank 1: the positive is closer than every negative)."""
+        with torch.no_grad():
+            E, B, Q, pair_w = self._loss_inputs(ids, feats, batch, False)
+            if E.is_cuda:
+                loss, aff, _ = ops.skipgram_head(E, B, Q, pair_w, self.neg_weight)
+            else:
+                loss, aff = ops._skipgram_host(E, B, Q, pair_w, self.neg_weight)
+            rank = 1 + (aff[:, 1:] > aff[:, :1]).sum(dim=1)
+            mrr = (1.0 / rank.double()).mean()
+        return {"loss": float(loss), "mrr": float(mrr)}

@@ -304,6 +304,91 @@ def sample_csr(csr, ids, n, sel=None, philox=None, out=None):
 
 
 # =============================================================================================
+# Unsupervised batches: random-walk positives + degree^0.75 negatives (csrc/gsage_unsup.hip)
+# =============================================================================================
+UNSUP_TAG_LEN, UNSUP_TAG_STEP, UNSUP_TAG_NEG = 0x4C000000, 0x53000000, 0x4E000000     # include/gsage.h
+
+
+def _philox4(ctr, key):
+    """Philox4x32-10 on Python integers: four counter words, two key words -> four words (host mode)."""
+    c0, c1, c2, c3 = ctr
+    k0, k1 = key
+    m = 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & m, p1 & m, ((p0 >> 32) ^ c3 ^ k1) & m, p0 & m
+        k0, k1 = (k0 + 0x9E3779B9) & m, (k1 + 0xBB67AE85) & m
+    return c0, c1, c2, c3
+
+
+def neg_cdf(csr):
+    """The negatives' table of gsage_unsup_batch for `csr`: float64 inclusive running sum of degree^0.75, on the
+    adjacency's device (set-up, once per adjacency).  Its last element is read to the host here, once."""
+    deg = (csr.rowptr[1:] - csr.rowptr[:-1]).to(torch.float64)
+    cdf = torch.cumsum(deg.clamp(min=0).pow(0.75), 0).contiguous()
+    cdf._gsage_total = float(cdf[-1].item())
+    return cdf
+
+
+def unsup_batch(csr, seeds, walk_len, Q, cdf, philox):
+    """The id batch of one unsupervised step (include/gsage.h, gsage_unsup_batch): -> (ids int64 [2B + Q] =
+    [seeds | random-walk positives | negatives], pair_w fp32 [B]: 0 where a walk ended on its own seed).
+    cdf: neg_cdf(csr) (any float64 inclusive running sum of row weights will do); philox: dict(seed, call_base,
+    g0, call_ctr) as for sample_csr.  CPU tensors: the same definition in numpy / Python integers (host mode)."""
+    seeds = seeds.contiguous().view(-1)
+    B, Q, walk_len = int(seeds.shape[0]), int(Q), int(walk_len)
+    total = getattr(cdf, "_gsage_total", None)
+    if total is None:
+        total = float(cdf[-1].item())
+    seed, base, g0 = int(philox["seed"]), int(philox.get("call_base", 0)), int(philox.get("g0", 0))
+    ctr = philox.get("call_ctr")
+    if seeds.is_cuda:
+        assert cdf.dtype == torch.float64 and cdf.is_cuda and cdf.is_contiguous() and cdf.numel() == csr.n_rows
+        ids = torch.empty(2 * B + Q, dtype=torch.int64, device=seeds.device)
+        pair_w = torch.empty(B, dtype=torch.float32, device=seeds.device)
+        nat.check(nat.lib().gsage_unsup_batch(_ptr(csr.rowptr), _ptr(csr.col), csr.n_rows, _ptr(seeds), B, walk_len, Q,
+                                              _ptr(cdf), total, seed, _ptr(ctr), base, g0, _ptr(ids), _ptr(pair_w),
+                                              _ptr(csr.err_flag), _stream()), "unsup_batch")
+        return ids, pair_w
+    # ---- host mode
+    if not (B > 0 and Q > 0 and 1 <= walk_len <= 16):
+        raise ValueError("unsup_batch: needs B > 0, Q > 0 and 1 <= walk_len <= 16")
+    if not (total > 0.0 and total < float("inf")):
+        raise ValueError("unsup_batch: the negatives' weights sum to %g" % total)
+    call = (base + (int(ctr.item()) if ctr is not None else 0)) & 0xFFFFFFFFFFFFFFFF
+    clo, chi = call & 0xFFFFFFFF, call >> 32
+    klo, khi = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    rp, col, sd, n_rows = csr.rowptr.numpy(), csr.col.numpy(), seeds.numpy(), csr.n_rows
+    if sd.min() < 0 or sd.max() >= n_rows:
+        raise IndexError("unsup_batch: node id out of range of the adjacency")
+    ids = np.zeros(2 * B + Q, dtype=np.int64)
+    pair_w = np.zeros(B, dtype=np.float32)
+    for i in range(B):
+        g = (g0 + i) & 0xFFFFFFFFFFFFFFFF
+        c = (g & 0xFFFFFFFF, g >> 32, clo, chi)
+        t = 1 + ((_philox4(c, (klo, khi ^ UNSUP_TAG_LEN))[0] * walk_len) >> 32)
+        v, r = int(sd[i]), None
+        for j in range(t):
+            beg = int(rp[v])
+            deg = int(rp[v + 1]) - beg
+            if deg <= 0:
+                break
+            if j & 3 == 0:
+                r = _philox4(c, (klo, khi ^ (UNSUP_TAG_STEP | (j >> 2))))
+            word = r[j & 3]
+            v = int(col[beg + ((word * deg) >> 32 if deg <= 0xFFFFFFFF else word)])
+            if v < 0 or v >= n_rows:
+                raise IndexError("unsup_batch: node id out of range of the adjacency")
+        ids[i], ids[B + i], pair_w[i] = sd[i], v, 0.0 if v == sd[i] else 1.0
+    cn = cdf.numpy()
+    for q in range(Q):
+        r = _philox4((q & 0xFFFFFFFF, q >> 32, clo, chi), (klo, khi ^ UNSUP_TAG_NEG))
+        x = np.float64((r[0] << 21) | (r[1] >> 11)) * np.float64(2.0 ** -53) * np.float64(total)
+        ids[2 * B + q] = min(int(np.searchsorted(cn, x, side="right")), n_rows - 1)
+    return torch.from_numpy(ids), torch.from_numpy(pair_w)
+
+
+# =============================================================================================
 # K2 / K6  gather + mean, segment mean, scatter-add
 # =============================================================================================
 def _gather_mean_raw(table, D, ids, M, n, out_dtype, out_ld=None, out=None):
@@ -1100,3 +1185,61 @@ def lstm_last(neibs, M, w_ih, w_hh, b_ih, b_hh, reverse=None, compute_dtype=None
     if isinstance(neibs, RowRef):
         return _LSTMLast.apply(None, neibs.store.data, neibs.ids, neibs.store.dim, M, n, cd, w_ih, w_hh, b_ih, b_hh, *rev)
     return _LSTMLast.apply(neibs, None, None, 0, M, n, cd, w_ih, w_hh, b_ih, b_hh, *rev)
+
+
+# =============================================================================================
+# Skip-gram head of the unsupervised model (csrc/gsage_unsup.hip)
+# =============================================================================================
+def _skipgram_host(E, B, Q, pair_w, neg_weight):
+    """The head's definition in torch ops (host mode): -> (loss, aff [B, 1 + Q])."""
+    z = F.normalize(E.float(), dim=1)
+    a = (z[:B] * z[B:2 * B]).sum(1)
+    n = z[:B] @ z[2 * B:2 * B + Q].t()
+    loss = ((pair_w * F.softplus(-a)).sum() + neg_weight * F.softplus(n).sum()) / B
+    return loss, torch.cat([a.unsqueeze(1), n], dim=1)
+
+
+def skipgram_head(E, B, Q, pair_w, neg_weight=1.0, grad_dtype=torch.float32, grad_ld=None):
+    """gsage_head_skipgram on the un-normalised rows E [2B + Q, D] = [seeds | positives | negatives] (CUDA, fp32, unit
+    column stride): -> (loss [1], aff [B, 1 + Q] = [a_i | n_iq], dE [2B + Q, D] = d loss / d E in `grad_dtype`).
+        loss = (1/B) sum_i [pair_w_i softplus(-a_i) + neg_weight sum_q softplus(n_iq)],  a, n = cosines of the rows"""
+    assert E.is_cuda and E.dtype == torch.float32 and E.dim() == 2 and int(E.shape[0]) == 2 * B + Q
+    if E.stride(1) != 1:
+        E = E.contiguous()
+    D = int(E.shape[1])
+    pair_w = pair_w.to(torch.float32).contiguous()
+    assert pair_w.is_cuda and pair_w.numel() == B
+    L = nat.lib()
+    ldd = D if grad_ld is None else int(grad_ld)
+    dE = torch.empty(2 * B + Q, ldd, dtype=grad_dtype, device=E.device) if ldd == D else \
+        torch.zeros(2 * B + Q, ldd, dtype=grad_dtype, device=E.device)
+    loss = torch.empty(1, dtype=torch.float32, device=E.device)
+    aff = torch.empty(B, 1 + Q, dtype=torch.float32, device=E.device)
+    scratch = torch.empty(max(int(L.gsage_head_skipgram_scratch(B, Q, D)), 1), dtype=torch.float32, device=E.device)
+    nat.check(L.gsage_head_skipgram(_ptr(E), E.stride(0), B, Q, D, _ptr(pair_w), float(neg_weight), _ptr(dE),
+                                    _code(grad_dtype), ldd, _ptr(loss), _ptr(aff), _ptr(scratch), _stream()),
+              "head_skipgram")
+    return loss, aff, dE[:, :D]
+
+
+class _SkipgramLoss(torch.autograd.Function):
+    """forward and backward are the head's two launches, run in forward; backward scales the saved dE."""
+
+    @staticmethod
+    def forward(ctx, E, B, Q, pair_w, neg_weight):
+        loss, _, dE = skipgram_head(E, B, Q, pair_w, neg_weight)
+        ctx.save_for_backward(dE)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dE, = ctx.saved_tensors
+        return dE * g, None, None, None, None
+
+
+def skipgram_loss(E, B, Q, pair_w, neg_weight=1.0):
+    """Skip-gram loss of an unsupervised batch (GSUnsupervised.train_step): E [2B + Q, D] un-normalised encoder rows in
+    the order of unsup_batch; differentiable in E.  CUDA: gsage_head_skipgram; CPU: the torch expression (host mode)."""
+    if E.is_cuda:
+        return _SkipgramLoss.apply(E.float(), int(B), int(Q), pair_w, float(neg_weight))
+    return _skipgram_host(E, int(B), int(Q), pair_w, float(neg_weight))[0]

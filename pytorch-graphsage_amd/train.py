@@ -33,6 +33,11 @@ Layer-wise full-neighbourhood inference (infer.py, opt-in; the default output is
                           every neighbour of every node, no sampling) instead of the sampled forward
   --save-embeddings PATH  after training, F.normalize(H^L) of every row of the adjacency, in node-id order, as one
                           .npy (rank 0)
+
+--unsupervised (with --walk-len, --n-negatives, --neg-weight): train the encoder without labels (models.GSUnsupervised:
+random-walk positives, degree^0.75 negatives, skip-gram loss on the HIP head).  Targets are ignored; every batch
+prints one JSON line with its loss, every epoch the validation fold's loss and mean reciprocal rank ("mrr").  The
+module path runs it (said on stderr); data-parallel launches are refused.
 """
 from __future__ import division, print_function
 
@@ -114,9 +119,7 @@ def full_neighbour_evaluate(model, problem, mode='val'):
 
 def save_embeddings(model, problem, path):
     """F.normalize(H^L) of every row, node-id order, one .npy."""
-    _, emb = gs.full_neighbour(model, problem.feats, nodes=torch.zeros(1, dtype=torch.int64,
-                                                                       device=problem.feats.device), embeddings=True)
-    np.save(path, emb.cpu().numpy())
+    np.save(path, gs.embeddings(model, problem.feats).cpu().numpy())
 
 
 class FusedEvaluator(object):
@@ -213,6 +216,10 @@ def parse_args(argv=None):
     parser.add_argument('--feature-dtype', type=str, default='native', choices=['native', 'fp8'])
     parser.add_argument('--full-neighbour-eval', action="store_true")
     parser.add_argument('--save-embeddings', type=str, default=None)
+    parser.add_argument('--unsupervised', action="store_true")
+    parser.add_argument('--walk-len', type=int, default=5)
+    parser.add_argument('--n-negatives', type=int, default=20)
+    parser.add_argument('--neg-weight', type=float, default=1.0)
 
     args = parser.parse_args(argv)
     args.cuda = not args.no_cuda
@@ -220,6 +227,8 @@ def parse_args(argv=None):
     assert args.aggregator_class in aggregator_lookup.keys(), \
         'parse_args: aggregator_class not in %s' % str(aggregator_lookup.keys())
     assert args.batch_size > 1, 'parse_args: batch_size must be > 1'
+    assert 1 <= args.walk_len <= 16 and 1 <= args.n_negatives <= 64, \
+        'parse_args: --walk-len must be in 1..16 and --n-negatives in 1..64'
     return args
 
 
@@ -237,12 +246,16 @@ def build_model(args, problem):
             "output_dim": dims[li],
             "activation": (lambda x: x) if last else F.relu,     # train.py:105-118
         })
-    return GSSupervised(
+    common = dict(
         sampler_class=sampler_lookup[args.sampler_class], adj=problem.adj, train_adj=problem.train_adj,
         prep_class=prep_lookup[args.prep_class], aggregator_class=aggregator_lookup[args.aggregator_class],
-        input_dim=problem.feats_dim, n_nodes=problem.n_nodes, n_classes=problem.n_classes,
+        input_dim=problem.feats_dim, n_nodes=problem.n_nodes,
         layer_specs=specs, lr_init=args.lr_init, lr_schedule=args.lr_schedule,
         weight_decay=args.weight_decay)
+    if args.unsupervised:
+        return gs.GSUnsupervised(walk_len=args.walk_len, n_negatives=args.n_negatives, neg_weight=args.neg_weight,
+                                 **common)
+    return GSSupervised(n_classes=problem.n_classes, **common)
 
 
 def main(argv=None, problem=None):
@@ -256,6 +269,8 @@ def main(argv=None, problem=None):
     gs.helpers.legacy_stream.enabled = bool(args.cuda and args.rng == 'compat' and
                                             os.environ.get("GSAGE_HOST_SEL", "0") != "1")
 
+    if args.unsupervised and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("GSAGE_FORCE_DDP", "0") == "1"):
+        raise SystemExit('gsage: --unsupervised: data-parallel training is not supported (run a single process)')
     ddp = gs.dist.init_from_env(args.cuda)            # no-op outside torch.distributed.run
     if problem is None:
         problem = NodeProblem(problem_path=args.problem_path, cuda=args.cuda)
@@ -272,6 +287,16 @@ def main(argv=None, problem=None):
     if ddp is not None:
         gs.dist.attach(model, ddp, seed=args.seed)
     print(model, file=sys.stderr)
+    if args.unsupervised:
+        if args.full_neighbour_eval:
+            raise SystemExit('gsage: --unsupervised: --full-neighbour-eval scores logits; there are none')
+        if args.save_embeddings:
+            try:
+                gs.infer.check_supported(model)
+            except ValueError as e:
+                raise SystemExit('gsage: --save-embeddings: %s' % e)
+        set_seeds(args.seed ** 2)
+        return train_unsupervised(args, problem, model)
     if args.full_neighbour_eval or args.save_embeddings:
         try:
             gs.infer.check_supported(model)
@@ -321,6 +346,49 @@ def main(argv=None, problem=None):
         ddp.close()
 
 
+def evaluate_unsupervised(model, problem, mode='val'):
+    """{"loss", "mrr"} of a fold under GSUnsupervised.evaluate, seed-weighted over the fold's batches."""
+    tot = {"loss": 0.0, "mrr": 0.0}
+    count = 0
+    for (ids, _, _) in problem.iterate(mode=mode, shuffle=False):
+        res = model.evaluate(ids, problem.feats)
+        n = int(ids.shape[0])
+        count += n
+        for k in tot:
+            tot[k] += res[k] * n
+    check_samplers(model)
+    return {k: v / max(count, 1) for k, v in tot.items()}
+
+
+def train_unsupervised(args, problem, model):
+    """The --unsupervised run: GSUnsupervised.train_step on the module path, one JSON line per batch."""
+    choose_engine(args, problem, model, None)          # (says on stderr that the module path runs)
+    start_time = time()
+    val = {"loss": None, "mrr": None}
+    loss = None
+    epoch = 0
+    for epoch in range(args.epochs):
+        model.train()
+        for ids, _, epoch_progress in problem.iterate(mode='train', shuffle=True, batch_size=args.batch_size):
+            model.set_progress((epoch + epoch_progress) / args.epochs)
+            loss = float(model.train_step(ids=ids, feats=problem.feats))
+            print(dumps({"epoch": epoch, "epoch_progress": epoch_progress, "loss": loss, "val_loss": val["loss"],
+                         "val_mrr": val["mrr"], "time": time() - start_time}))
+            sys.stdout.flush()
+        model.eval()
+        val = evaluate_unsupervised(model, problem, 'val')
+        print(dumps({"epoch": epoch, "val_loss": val["loss"], "mrr": val["mrr"], "time": time() - start_time}))
+        sys.stdout.flush()
+    gs.helpers.legacy_stream.release()                 # hand numpy's stream back to the host
+    print('-- done --', file=sys.stderr)
+    print(dumps({"epoch": epoch, "loss": loss, "val_loss": val["loss"], "mrr": val["mrr"], "time": time() - start_time}))
+    if args.show_test:
+        print(dumps({"test": evaluate_unsupervised(model, problem, 'test')}))
+    sys.stdout.flush()
+    if args.save_embeddings:
+        save_embeddings(model, problem, args.save_embeddings)
+
+
 def choose_engine(args, problem, model, ddp):
     """The fused engine this run gets, or None for the module path.  Everything that could stop an engine AFTER it
     has re-pointed the model's Parameters into its buckets is decided here: the model / feature store / process
@@ -328,10 +396,15 @@ def choose_engine(args, problem, model, ddp):
     reference's unequal chunks) and the batch geometry.  --engine auto: one stderr line says why the module path
     runs; --engine fused: the same sentence is an error."""
     def give_up(why):
+        if args.unsupervised:
+            print('gsage: unsupervised model: module path', file=sys.stderr)
+            return None
         if args.engine == 'fused':
             raise SystemExit('gsage: --engine fused: %s (use --engine auto / eager)' % why)
         print('gsage: %s; using the module path' % why, file=sys.stderr)
         return None
+    if args.unsupervised:                           # no fused engine is attempted
+        return give_up('unsupervised model')
     cls = gs.engine.fused_engine_for(model, problem.feats, explain=True, ddp=ddp)
     if cls is None:
         return give_up('no fused engine covers this model')

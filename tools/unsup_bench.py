@@ -1,0 +1,112 @@
+#!/usr/bin/env python
+"""unsup_bench.py -- what an unsupervised step costs on the GPU, at the Reddit shape (232 965 nodes, 602 features,
+fan-out 25/10, dims 128/128, B = 512 seeds, Q = 20 negatives, walk_len = 5, bf16 compute), on a synthetic graph.
+
+One JSON line per measurement, appended to --out (default profiles/unsup_bench.jsonl), all in one process:
+  unsup_train_step   ms / step of GSUnsupervised.train_step (builder + one encoder pass over 2B + Q ids + head + Adam)
+  sup_train_step     ms / step of GSSupervised.train_step on the module path with 2B + Q = 1044 seeds: the comparison
+                     (same encoder work, cross-entropy head through torch ops instead of the skip-gram head)
+  unsup_batch        us / call of the builder's one launch
+  head_skipgram      us / call of the head's two launches (D = 256)
+Times are device events around `--steps` back-to-back calls after `--warmup` calls; the two train steps alternate
+`--rounds` times so that a drift of the machine shows in the spread.  Needs a GPU: there is no CPU fallback."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+from torch.nn import functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+gs = importlib.import_module("pytorch-graphsage_amd")
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nodes", type=int, default=232965)
+    ap.add_argument("--feats", type=int, default=602)
+    ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--negatives", type=int, default=20)
+    ap.add_argument("--walk-len", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "unsup_bench.jsonl"))
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "unsup_bench needs a GPU"
+    dev = torch.device("cuda")
+    gs.ops.set_compute_dtype("bf16")
+    gs.ops.warmup(dev)
+
+    from scipy import sparse
+    rng = np.random.RandomState(0)
+    n, B, Q = args.nodes, args.batch, args.negatives
+    deg = rng.randint(1, 100, size=n)
+    deg[0] = 0
+    indptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+    data = rng.randint(1, n, size=int(indptr[-1])).astype(np.int32)
+    adj = sparse.csr_matrix((data, gs.store.row_positions(indptr), indptr), shape=(n, int(deg.max())))
+    store = gs.FeatureStore.from_array(rng.standard_normal((n, args.feats)).astype(np.float32), dev, dtype="bf16")
+    specs = [{"n_train_samples": 25, "n_val_samples": 25, "output_dim": 128, "activation": F.relu},
+             {"n_train_samples": 10, "n_val_samples": 10, "output_dim": 128, "activation": lambda x: x}]
+    common = dict(sampler_class=lambda adj: gs.nn_modules.SparseUniformNeighborSampler(adj, rng="philox"), adj=adj,
+                  train_adj=adj, prep_class=gs.prep_lookup["identity"], aggregator_class=gs.aggregator_lookup["mean"],
+                  input_dim=args.feats, n_nodes=n, layer_specs=specs)
+    torch.manual_seed(0)
+    unsup = gs.GSUnsupervised(walk_len=args.walk_len, n_negatives=Q, **common).to(dev)
+    sup = gs.GSSupervised(n_classes=41, **common).to(dev)
+    seeds = torch.from_numpy(rng.randint(1, n, size=B)).to(dev)
+    seeds_sup = torch.from_numpy(rng.randint(1, n, size=2 * B + Q)).to(dev)
+    targets = torch.from_numpy(rng.randint(0, 41, size=(2 * B + Q, 1))).to(dev)
+
+    info = gs._native.device_info()
+    base = {"arch": info["arch"] if info else None, "nodes": n, "feats": args.feats, "fan": [25, 10], "dims": [128, 128],
+            "B": B, "Q": Q, "walk_len": args.walk_len, "precision": "bf16", "steps": args.steps, "warmup": args.warmup,
+            "stamp": time.strftime("%Y-%m-%d")}
+    rows = []
+    un, su = [], []
+    for _ in range(args.rounds):
+        un.append(timed(lambda: unsup.train_step(seeds, store), args.steps, args.warmup))
+        su.append(timed(lambda: sup.train_step(seeds_sup, store, targets, gs.ProblemLosses.classification), args.steps,
+                        args.warmup))
+    rows.append(dict(base, what="unsup_train_step", ms_per_step=float(np.median(un)), rounds_ms=un))
+    rows.append(dict(base, what="sup_train_step", seeds=2 * B + Q, ms_per_step=float(np.median(su)), rounds_ms=su))
+
+    csr, cdf = unsup._walk_graph(True, dev)
+    ph = {"seed": 0, "call_base": 0}
+    t = [timed(lambda: gs.ops.unsup_batch(csr, seeds, args.walk_len, Q, cdf, ph), 200, 20) for _ in range(args.rounds)]
+    rows.append(dict(base, what="unsup_batch", launches=1, us_per_call=1e3 * float(np.median(t)),
+                     rounds_us=[1e3 * v for v in t]))
+    E = torch.randn(2 * B + Q, unsup.output_dim, device=dev)
+    pw = torch.ones(B, device=dev)
+    t = [timed(lambda: gs.ops.skipgram_head(E, B, Q, pw), 200, 20) for _ in range(args.rounds)]
+    rows.append(dict(base, what="head_skipgram", launches=2, D=unsup.output_dim, us_per_call=1e3 * float(np.median(t)),
+                     rounds_us=[1e3 * v for v in t],
+                     note="includes the four output allocations of ops.skipgram_head"))
+    with open(args.out, "a") as f:
+        for r in rows:
+            line = json.dumps(r)
+            print(line)
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
