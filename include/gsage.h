@@ -1013,7 +1013,7 @@ int gsage_metric_mae(const float *y_true, const float *y_pred, int64_t n, double
  *   inputs give the same bits.  err_flag (int32, may be NULL) is set to 1 when a neighbour id is outside
  *   [0, n_rows); such an id reads row 0.
  * ---------------------------------------------------------------------------------------- */
-enum { GSAGE_SEG_MEAN = 0, GSAGE_SEG_MAX = 1, GSAGE_SEG_SOFTMAX_WEIGHTED = 2 };
+enum { GSAGE_SEG_MEAN = 0, GSAGE_SEG_MAX = 1, GSAGE_SEG_SOFTMAX_WEIGHTED = 2, GSAGE_SEG_WEIGHTED_MEAN = 3 };
 /* HOST: the smallest row length of the partials buffer for width D (-1 when D <= 0) */
 int64_t gsage_segment_reduce_ldp(int64_t D);
 int gsage_segment_reduce(int mode, const void *table, int dtype, int64_t ld, int64_t D, const float *keys,
@@ -1068,6 +1068,51 @@ int gsage_head_skipgram(const float *E, int64_t lde, int32_t B, int32_t Q, int32
                         float neg_weight, void *dE, int dE_dtype, int64_t ldd, float *loss, float *aff, float *scratch,
                         void *stream);
 int64_t gsage_head_skipgram_scratch(int32_t B, int32_t Q, int32_t D);
+
+/* ------------------------------------------------------------------------------------------
+ * Weighted adjacency (csrc/gsage_weighted.hip, csrc/gsage_fullgraph.hip): edge-weight neighbour sampling and the
+ * weight-normalised mean of layer-wise inference.  Additive; the ABI version is unchanged.  No reference counterpart.
+ *
+ * A weighted adjacency is the device CSR plus `cdf`, one uint64 per stored edge (aligned with col): the inclusive
+ * running sum, inside each row, of the edge weights in integer quanta.
+ *
+ * gsage_edge_cdf_build -- set-up, once per adjacency (two launches: a wave per row of degree <= 256, a workgroup per
+ * longer row).  weight: fp32 [nnz], finite and >= 0 (the CALLER checks: the kernels do not).  For row v with largest
+ * weight m_v:
+ *     degree 0 or m_v == 0     no drawable edge: every entry of the row is 0; the row behaves everywhere as a row of
+ *                              degree 0 does (the dummy node 0)
+ *     otherwise                (f, E) = frexp(m_v), f in [0.5, 1);   q_e = floor(w_e * 2^(24 - E))   in [0, 2^24)
+ *                              cdf[e] = sum of q over the row's edges up to and including e        (<= deg * 2^24)
+ * The scaling and the floor are done on the bits of w_e: q_e is the mathematical value for denormal weights and for a
+ * maximum of 3.4e38 alike, and integer sums are exact, so every scan order gives the same table.  An edge lighter than
+ * m_v * 2^-24 has q_e = 0 and is never drawn.
+ *
+ * gsage_sample_csr_weighted -- one launch per hop, Philox4x32-10 (the uniform sampler's generator, own key):
+ *     g    = g0 + i*n + j,    call = call_base + (call_ctr ? *call_ctr : 0)        (as gsage_sample_csr_philox)
+ *     w    = philox4x32_10({lo(g>>1), hi(g>>1), lo(call), hi(call)}, {lo(seed), hi(seed) ^ 0x57000000})
+ *     r64  = (w[2*(g&1)] << 32) | w[2*(g&1) + 1]                                    (a block holds two draws)
+ *     T    = the last cdf entry of row ids[i];   x = (r64 * T) >> 64               (128-bit product, x < T)
+ *     out[i*n+j] = col[first e in the row with cdf[e] > x]                          (binary search)
+ * T == 0 or degree 0 yields the dummy 0; an id outside [0, n_rows) yields 0 and raises *err_flag (may be NULL).
+ *
+ * gsage_segment_reduce_weighted -- gsage_segment_reduce's arguments for a mean (no keys) plus cdf:
+ *     out[v, c] = sum_e p_e table[col[e], c],   p_e = (cdf[e] - cdf[e-1]) / T_v    (the row's first edge subtracts 0)
+ * -- what the sampled mean estimates under gsage_sample_csr_weighted, from the same quanta (mode
+ * GSAGE_SEG_WEIGHTED_MEAN).  q_e < 2^24 is exact as a float and p_e = float(q_e) / float(T_v) is one IEEE division, so
+ * a row with a single drawable edge (p_e == 1) returns that neighbour's row bit for bit; short rows and slices
+ * accumulate fma(p_e, x, acc) in edge order, the merge adds a long row's partials in slice order.  A row with
+ * T_v == 0 reads row 0.  Same plan, partials, alignment rules, activation and err_flag as
+ * gsage_segment_reduce; no floating-point atomics.
+ * ---------------------------------------------------------------------------------------- */
+int gsage_edge_cdf_build(const int64_t *rowptr, const float *weight, int64_t n_rows, uint64_t *cdf, void *stream);
+int gsage_sample_csr_weighted(const int64_t *rowptr, const int32_t *col, const uint64_t *cdf, int64_t n_rows,
+                              const int64_t *ids, int64_t M, int32_t n, uint64_t seed, const uint64_t *call_ctr,
+                              uint64_t call_base, uint64_t g0, int64_t *out, int32_t *err_flag, void *stream);
+int gsage_segment_reduce_weighted(const void *table, int dtype, int64_t ld, int64_t D, const int64_t *rowptr,
+                                  const int32_t *col, const uint64_t *cdf, int64_t n_rows, const int32_t *order,
+                                  int64_t n_short, const int64_t *slices, int64_t n_slices, const int64_t *long_rows,
+                                  int64_t n_long, int32_t slice_len, float *partials, int64_t ldp, void *out,
+                                  int out_dtype, int64_t out_ld, int act, int32_t *err_flag, void *stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
                               same names and interfaces as the reference's files
     dist.py                   RCCL data-parallel gradient sync
     infer.py                  layer-wise full-neighbourhood inference, node-embedding export
+    store.WeightedAdj         edge weights: sparse_weighted_neighbor_sampler, weight-normalised full-neighbourhood mean
     models.GSUnsupervised     label-free training: random-walk positives, degree^0.75 negatives, skip-gram head
     engine/                   the whole train_step as recorded launches (captured autograd path; fused mean /
                               pool / attention engines on a shared base)
@@ -19,10 +20,10 @@ from .helpers import set_seeds, to_numpy                            # noqa: F401
 from .infer import embeddings, full_neighbour                                   # noqa: F401
 from .lr import LRSchedule                                          # noqa: F401
 from .models import GSSupervised, GSUnsupervised                                # noqa: F401
-from .nn_modules import aggregator_lookup, prep_lookup, sampler_lookup   # noqa: F401
+from .nn_modules import aggregator_lookup, find_sampler, prep_lookup, sampler_extensions, sampler_lookup   # noqa: F401
 from .problem import DeviceMetrics, NodeProblem, ProblemLosses, ProblemMetrics, batch_metric   # noqa: F401
-from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef                  # noqa: F401
+from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef, WeightedAdj                  # noqa: F401
 
 __all__ = ["GSSupervised", "GSUnsupervised", "NodeProblem", "aggregator_lookup", "prep_lookup", "sampler_lookup",
            "set_seeds", "to_numpy", "LRSchedule", "FeatureStore", "DeviceCSR", "RowRef", "ops", "full_neighbour",
-           "embeddings"]
+           "embeddings", "WeightedAdj", "find_sampler", "sampler_extensions"]

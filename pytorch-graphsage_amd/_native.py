@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libgsage_hip.so")
 F32, BF16, FP8 = 0, 1, 2
 POOL_MAX, POOL_MEAN = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
-SEG_MEAN, SEG_MAX, SEG_SOFTMAX_WEIGHTED = 0, 1, 2
+SEG_MEAN, SEG_MAX, SEG_SOFTMAX_WEIGHTED, SEG_WEIGHTED_MEAN = 0, 1, 2, 3
 ABI_VERSION = 6
 
 _vp = ctypes.c_void_p
@@ -182,6 +182,10 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _vp]),
     "gsage_head_skipgram": (_int, [_vp, _i64, _i32, _i32, _i32, _vp, _f32, _vp, _int, _i64, _vp, _vp, _vp, _vp]),
     "gsage_head_skipgram_scratch": (_i64, [_i32, _i32, _i32]),
+    "gsage_edge_cdf_build": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "gsage_sample_csr_weighted": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _u64, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "gsage_segment_reduce_weighted": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                             _i32, _vp, _i64, _vp, _int, _i64, _int, _vp, _vp]),
 }
 
 

@@ -2,11 +2,18 @@
 //
 // out[v, c] = reduce_{u in N(v)} table[u, c] over the WHOLE neighbourhood of every row v (infer.py), with
 // N(v) = col[rowptr[v] .. rowptr[v+1]) and the single neighbour 0 (the dummy) for a row of degree 0 -- what the
-// sampler draws for such a row (gsage_sample_dev.h).  Three modes:
+// sampler draws for such a row (gsage_sample_dev.h).  Four modes:
 //   MEAN              (1/deg) sum_u table[u]
 //   MAX               max_u table[u]
 //   SOFTMAX_WEIGHTED  sum_u softmax_u(keys[u] . keys[v]) table[u]; keys are 32-wide fp32 rows, the score of a
 //                     neighbour is its key dotted with the row's own key (the attention aggregator's query).
+//   WEIGHTED_MEAN     sum_e (q_e / T_v) table[u_e] over a weighted adjacency's integer quanta (gsage_weighted.hip):
+//                     q_e = cdf[e] - cdf[e - 1] < 2^24 is exact as a float and p_e = q_e / float(T_v) is one IEEE
+//                     division per edge, so a row with a single drawable edge (p = 1) returns that neighbour's row
+//                     bit for bit -- sum q_e x_u divided once at the end does not (round(q x) / q need not be x).  Short
+//                     rows and slices accumulate fma(p_e, x_u, acc); the merge adds the slices' partials.  A row
+//                     without a drawable edge (T_v == 0) reads the dummy like a row of degree 0
+//                     (gsage_segment_reduce_weighted).
 //
 // Degree skew (Reddit-shaped graphs run from degree 0 to > 20,000): the caller's plan (infer.py, built once per
 // adjacency) lists the rows of degree <= slice_len in DEGREE-DESCENDING order -- a wave holds 64 / team rows of
@@ -66,6 +73,7 @@ struct FgArgs {
     int32_t act;
     int32_t team;                   // lanes per row: 8, 16, 32 or 64
     int32_t *err;                   // set to 1 when a neighbour id is outside [0, n_rows)
+    const uint64_t *cdf;            // WEIGHTED_MEAN: the adjacency's inclusive per-row running sums of quanta [nnz]
 };
 
 // state of one lane's column chunk
@@ -95,7 +103,7 @@ __device__ __forceinline__ float team8_sum(float s)
 // own a chunk inside Dp.
 template <typename TI, int MODE>
 __device__ __forceinline__ void fg_walk(const FgArgs &a, int64_t beg, int64_t cnt, int32_t c0, bool live,
-                                        const float4 &q, int klane, FgAcc<MODE, fg_io<TI>::VEC> &s)
+                                        const float4 &q, int klane, FgAcc<MODE, fg_io<TI>::VEC> &s, int64_t row_beg, float Tf)
 {
     constexpr int VEC = fg_io<TI>::VEC;
     const TI *table = (const TI *)a.table;
@@ -151,6 +159,23 @@ __device__ __forceinline__ void fg_walk(const FgArgs &a, int64_t beg, int64_t cn
                 }
             }
             s.m = mn;
+        } else if (MODE == GSAGE_SEG_WEIGHTED_MEAN) {
+            // the edge's quantum: the difference of two neighbouring table entries (the row's first edge subtracts 0),
+            // over the row's total; the dummy neighbour of a row without a drawable edge (cnt == 0) has weight 1
+            float w[FG_BATCH];
+#pragma unroll
+            for (int u = 0; u < FG_BATCH; ++u) {
+                const int64_t e = beg + min(j + u, cnt - 1);
+                w[u] = 1.f;
+                if (cnt > 0) w[u] = (float)(uint32_t)(a.cdf[e] - (e > row_beg ? a.cdf[e - 1] : 0ull)) / Tf;
+            }
+#pragma unroll
+            for (int u = 0; u < FG_BATCH; ++u) {
+                if (u < m) {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) s.a[e] = fmaf(w[u], fg_io<TI>::elem(v[u], e), s.a[e]);
+                }
+            }
         } else {
 #pragma unroll
             for (int u = 0; u < FG_BATCH; ++u) {
@@ -191,16 +216,24 @@ __global__ __launch_bounds__(FG_THREADS) void k_segment_reduce(FgArgs a)
     const int64_t item = (int64_t)blockIdx.x * (FG_THREADS / team) + threadIdx.x / team;
     if (item >= a.n_short + a.n_slices) return;
     int64_t row, beg, cnt;
+    float Tf = 1.f;                 // WEIGHTED_MEAN: the row's total
     const bool is_slice = item >= a.n_short;
     if (!is_slice) {
         row = a.order[item];
         beg = a.rowptr[row];
         cnt = a.rowptr[row + 1] - beg;
+        if (MODE == GSAGE_SEG_WEIGHTED_MEAN) {
+            const uint64_t T = cnt > 0 ? a.cdf[beg + cnt - 1] : 0ull;
+            if (T == 0) cnt = 0;    // no drawable edge: the dummy, as a row of degree 0
+            else Tf = (float)T;
+        }
     } else {
         const int64_t s = item - a.n_short;
         row = a.slices[2 * s];
         beg = a.slices[2 * s + 1];
         cnt = min((int64_t)a.slice_len, a.rowptr[row + 1] - beg);
+        // (a long row of zero weights: every quantum is 0, the partials are +-0 whatever Tf is; the merge reads the dummy)
+        if (MODE == GSAGE_SEG_WEIGHTED_MEAN) Tf = fmaxf((float)a.cdf[a.rowptr[row + 1] - 1], 1.f);
     }
     const int klane = lane & 7;
     float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -211,7 +244,7 @@ __global__ __launch_bounds__(FG_THREADS) void k_segment_reduce(FgArgs a)
         const bool live = g + lane < chunks;
         FgAcc<MODE, VEC> s;
         s.init();
-        fg_walk<TI, MODE>(a, beg, cnt, c0, live, q, klane, s);
+        fg_walk<TI, MODE>(a, beg, cnt, c0, live, q, klane, s, a.rowptr[row], Tf);
         if (!live) continue;
         if (is_slice) {
             float *p = a.partials + (item - a.n_short) * a.ldp;
@@ -231,7 +264,8 @@ __global__ __launch_bounds__(FG_THREADS) void k_segment_reduce(FgArgs a)
             const float inv = MODE == GSAGE_SEG_MEAN ? (float)(cnt > 0 ? cnt : 1)
                               : MODE == GSAGE_SEG_SOFTMAX_WEIGHTED ? s.l : 1.f;
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) r[e] = MODE == GSAGE_SEG_MAX ? s.a[e] : s.a[e] / inv;
+            for (int e = 0; e < VEC; ++e)
+                r[e] = MODE == GSAGE_SEG_MAX || MODE == GSAGE_SEG_WEIGHTED_MEAN ? s.a[e] : s.a[e] / inv;
             fg_store<TO, VEC>(a, row, c0, r);
         }
     }
@@ -249,6 +283,7 @@ __global__ __launch_bounds__(FG_THREADS) void k_segment_merge(FgArgs a)
     const int64_t row = a.long_rows[2 * lr], s0 = a.long_rows[2 * lr + 1];
     const int64_t deg = a.rowptr[row + 1] - a.rowptr[row];
     const int64_t ns = (deg + a.slice_len - 1) / a.slice_len;
+    const uint64_t T = MODE == GSAGE_SEG_WEIGHTED_MEAN ? a.cdf[a.rowptr[row + 1] - 1] : 1ull;
     float M = -INFINITY;
     if (MODE == GSAGE_SEG_SOFTMAX_WEIGHTED)
         for (int64_t s = 0; s < ns; ++s) M = fmaxf(M, a.partials[(s0 + s) * a.ldp + a.Dp]);
@@ -268,11 +303,17 @@ __global__ __launch_bounds__(FG_THREADS) void k_segment_merge(FgArgs a)
 #pragma unroll
             for (int e = 0; e < VEC; ++e)
                 r[e] = MODE == GSAGE_SEG_MAX ? fmaxf(r[e], p[c0 + e])
-                       : MODE == GSAGE_SEG_MEAN ? r[e] + p[c0 + e] : r[e] + w * p[c0 + e];
+                       : MODE == GSAGE_SEG_SOFTMAX_WEIGHTED ? r[e] + w * p[c0 + e] : r[e] + p[c0 + e];
         }
         const float inv = MODE == GSAGE_SEG_MEAN ? (float)deg : MODE == GSAGE_SEG_SOFTMAX_WEIGHTED ? l : 1.f;
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) r[e] = MODE == GSAGE_SEG_MAX ? r[e] : r[e] / inv;
+        for (int e = 0; e < VEC; ++e)
+            r[e] = MODE == GSAGE_SEG_MAX || MODE == GSAGE_SEG_WEIGHTED_MEAN ? r[e] : r[e] / inv;
+        if (MODE == GSAGE_SEG_WEIGHTED_MEAN && T == 0) {            // a long row of zero weights: the dummy's row
+            const vec16 v0 = *reinterpret_cast<const vec16 *>((const TI *)a.table + c0);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) r[e] = fg_io<TI>::elem(v0, e);
+        }
         fg_store<TO, VEC>(a, row, c0, r);
     }
 }
@@ -298,6 +339,7 @@ int dispatch_mode(int mode, const FgArgs &a, hipStream_t s)
     switch (mode) {
     case GSAGE_SEG_MEAN: return launch_segment_reduce<TI, TO, GSAGE_SEG_MEAN>(a, s);
     case GSAGE_SEG_MAX: return launch_segment_reduce<TI, TO, GSAGE_SEG_MAX>(a, s);
+    case GSAGE_SEG_WEIGHTED_MEAN: return launch_segment_reduce<TI, TO, GSAGE_SEG_WEIGHTED_MEAN>(a, s);
     default: return launch_segment_reduce<TI, TO, GSAGE_SEG_SOFTMAX_WEIGHTED>(a, s);
     }
 }
@@ -318,15 +360,13 @@ int64_t gsage_segment_reduce_ldp(int64_t D)
     return ceil_div(D, 8) * 8 + 4;
 }
 
-int gsage_segment_reduce(int mode, const void *table, int dtype, int64_t ld, int64_t D, const float *keys,
-                         int64_t ldk, const int64_t *rowptr, const int32_t *col, int64_t n_rows,
-                         const int32_t *order, int64_t n_short, const int64_t *slices, int64_t n_slices,
-                         const int64_t *long_rows, int64_t n_long, int32_t slice_len, float *partials,
-                         int64_t ldp, void *out, int out_dtype, int64_t out_ld, int act, int32_t *err_flag,
-                         void *stream)
+static int segment_reduce_any(int mode, const void *table, int dtype, int64_t ld, int64_t D, const float *keys,
+                              int64_t ldk, const int64_t *rowptr, const int32_t *col, const uint64_t *cdf,
+                              int64_t n_rows, const int32_t *order, int64_t n_short, const int64_t *slices,
+                              int64_t n_slices, const int64_t *long_rows, int64_t n_long, int32_t slice_len,
+                              float *partials, int64_t ldp, void *out, int out_dtype, int64_t out_ld, int act,
+                              int32_t *err_flag, void *stream)
 {
-    GSAGE_REQUIRE(mode == GSAGE_SEG_MEAN || mode == GSAGE_SEG_MAX || mode == GSAGE_SEG_SOFTMAX_WEIGHTED,
-                  "segment_reduce: unknown mode %d", mode);
     GSAGE_REQUIRE(dtype == GSAGE_BF16 || dtype == GSAGE_F32, "segment_reduce: table dtype must be bf16 or fp32");
     GSAGE_REQUIRE(out_dtype == GSAGE_BF16 || out_dtype == GSAGE_F32, "segment_reduce: out dtype must be bf16 or fp32");
     GSAGE_REQUIRE(act == GSAGE_ACT_NONE || act == GSAGE_ACT_RELU, "segment_reduce: act must be none or relu");
@@ -347,6 +387,7 @@ int gsage_segment_reduce(int mode, const void *table, int dtype, int64_t ld, int
                       "segment_reduce: softmax mode needs 32-wide fp32 keys (ldk >= 32, 16-byte rows)");
     if (n_short + n_slices == 0) return GSAGE_OK;
     GSAGE_REQUIRE(table && rowptr && col && out && aligned16(table), "segment_reduce: null or misaligned pointer");
+    GSAGE_REQUIRE(mode != GSAGE_SEG_WEIGHTED_MEAN || cdf, "segment_reduce_weighted: null cdf");
     GSAGE_REQUIRE(n_short == 0 || order, "segment_reduce: null order");
     GSAGE_REQUIRE(n_slices == 0 || (slices && long_rows), "segment_reduce: null slice plan");
 
@@ -357,7 +398,7 @@ int gsage_segment_reduce(int mode, const void *table, int dtype, int64_t ld, int
     a.order = order; a.n_short = n_short;
     a.slices = slices; a.n_slices = n_slices; a.long_rows = long_rows; a.n_long = n_long;
     a.slice_len = slice_len; a.partials = partials; a.ldp = ldp;
-    a.out = out; a.out_ld = out_ld; a.act = act; a.err = err_flag;
+    a.out = out; a.out_ld = out_ld; a.act = act; a.err = err_flag; a.cdf = cdf;
     int team = 8;
     while (team < 64 && team * vec < Dp) team *= 2;
     a.team = team;
@@ -366,6 +407,31 @@ int gsage_segment_reduce(int mode, const void *table, int dtype, int64_t ld, int
         return out_dtype == GSAGE_F32 ? dispatch_mode<uint16_t, float>(mode, a, s)
                                       : dispatch_mode<uint16_t, uint16_t>(mode, a, s);
     return out_dtype == GSAGE_F32 ? dispatch_mode<float, float>(mode, a, s) : dispatch_mode<float, uint16_t>(mode, a, s);
+}
+
+int gsage_segment_reduce(int mode, const void *table, int dtype, int64_t ld, int64_t D, const float *keys,
+                         int64_t ldk, const int64_t *rowptr, const int32_t *col, int64_t n_rows,
+                         const int32_t *order, int64_t n_short, const int64_t *slices, int64_t n_slices,
+                         const int64_t *long_rows, int64_t n_long, int32_t slice_len, float *partials,
+                         int64_t ldp, void *out, int out_dtype, int64_t out_ld, int act, int32_t *err_flag,
+                         void *stream)
+{
+    GSAGE_REQUIRE(mode == GSAGE_SEG_MEAN || mode == GSAGE_SEG_MAX || mode == GSAGE_SEG_SOFTMAX_WEIGHTED,
+                  "segment_reduce: unknown mode %d", mode);
+    return segment_reduce_any(mode, table, dtype, ld, D, keys, ldk, rowptr, col, nullptr, n_rows, order, n_short, slices,
+                              n_slices, long_rows, n_long, slice_len, partials, ldp, out, out_dtype, out_ld, act,
+                              err_flag, stream);
+}
+
+int gsage_segment_reduce_weighted(const void *table, int dtype, int64_t ld, int64_t D, const int64_t *rowptr,
+                                  const int32_t *col, const uint64_t *cdf, int64_t n_rows, const int32_t *order,
+                                  int64_t n_short, const int64_t *slices, int64_t n_slices, const int64_t *long_rows,
+                                  int64_t n_long, int32_t slice_len, float *partials, int64_t ldp, void *out,
+                                  int out_dtype, int64_t out_ld, int act, int32_t *err_flag, void *stream)
+{
+    return segment_reduce_any(GSAGE_SEG_WEIGHTED_MEAN, table, dtype, ld, D, nullptr, 0, rowptr, col, cdf, n_rows, order,
+                              n_short, slices, n_slices, long_rows, n_long, slice_len, partials, ldp, out, out_dtype,
+                              out_ld, act, err_flag, stream);
 }
 
 }  // extern "C"

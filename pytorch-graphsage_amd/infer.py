@@ -13,7 +13,9 @@ WHOLE neighbourhood:
 agg is the aggregator's own reduction: mean; max / mean of relu(W_m h + b_m) (pool aggregators); the softmax over
 N(v) of att(H[u]) . att(H[v]) weighting the raw rows (attention).  N(v) is row v of the sparse adjacency (a row of
 degree 0 has the single neighbour 0, the dummy, as the sampler draws it) or all K columns of row v of the dense one
-(duplicates count).  With the dense sampler and n_val_samples == K the sampled forward takes every column of every
+(duplicates count).  On a WEIGHTED adjacency (store.DeviceCSR.edge_cdf) the mean is the weight-normalised mean
+sum_e (q_e / T_v) H[u_e] over the table's integer quanta -- what the sampled mean estimates under the weighted sampler;
+a row without a drawable edge reads the dummy.  Max-pool and attention have no weighted form here.  With the dense sampler and n_val_samples == K the sampled forward takes every column of every
 row, i.e. computes this same thing up to summation order.
 
 On the GPU, fc_neib is applied BEFORE the reduction where that is exact (mean, mean-pool, attention: the reduction
@@ -37,8 +39,13 @@ SLICE_LEN = 256          # rows of higher degree are cut into slices of this man
 # --------------------------------------------------------------------------------------------
 # what is supported
 # --------------------------------------------------------------------------------------------
-def check_supported(model):
-    """Raise ValueError naming why `model` has no layer-wise full-neighbourhood form; else return None."""
+def _weighted(adj):
+    return getattr(adj, "edge_cdf", None) is not None
+
+
+def check_supported(model, adj=None):
+    """Raise ValueError naming why `model` has no layer-wise full-neighbourhood form (over `adj`, when given: a
+    weighted adjacency takes mean and mean-pool aggregators only); else return None."""
     if isinstance(model.prep, NodeEmbeddingPrep):
         raise ValueError("full-neighbour inference does not support NodeEmbeddingPrep: its seed hop reads the spare "
                          "row n_nodes, so every layer would need two tables")
@@ -58,6 +65,10 @@ def check_supported(model):
                              "not a callable")
         if isinstance(layer, AttentionAggregator) and layer.att[2].weight.shape[0] > 32:
             raise ValueError("full-neighbour inference needs an attention hidden_dim of at most 32")
+        if adj is not None and _weighted(adj) and (isinstance(layer, AttentionAggregator) or
+                                                   (isinstance(layer, PoolAggregator) and layer.pool_fn == "max")):
+            raise ValueError("full-neighbour inference on a weighted adjacency supports the mean and mean-pool "
+                             "aggregators; max-pool and attention have no weighted form")
 
 
 # --------------------------------------------------------------------------------------------
@@ -107,13 +118,22 @@ def plan(adj, slice_len=SLICE_LEN):
 def segment_reduce(adj, table, mode, out, act=nat.ACT_NONE, keys=None):
     """out[v, :D] = reduce over N(v) of table[u, :D] for every row v of `adj` (gsage_segment_reduce: two launches).
     table: [n_rows, D] bf16 / fp32 CUDA tensor whose row stride is a multiple of 16 bytes; out: a (possibly
-    strided) fp32 / bf16 [n_rows, D] view; keys (SOFTMAX_WEIGHTED): fp32 [n_rows, 32]."""
+    strided) fp32 / bf16 [n_rows, D] view; keys (SOFTMAX_WEIGHTED): fp32 [n_rows, 32].  mode SEG_WEIGHTED_MEAN
+    (gsage_segment_reduce_weighted) reads the adjacency's edge_cdf."""
     rowptr, col, n = _csr(adj)
     p = plan(adj)
     D = int(table.shape[1])
     assert table.stride(1) == 1 and out.stride(1) == 1 and int(table.shape[0]) >= n and int(out.shape[0]) >= n
     ldp = int(nat.lib().gsage_segment_reduce_ldp(D))
     partials = torch.empty(max(p["n_slices"], 1), ldp, dtype=torch.float32, device=table.device)
+    if mode == nat.SEG_WEIGHTED_MEAN:
+        assert _weighted(adj) and int(adj.edge_cdf.shape[0]) == int(col.shape[0])
+        nat.check(nat.lib().gsage_segment_reduce_weighted(
+            ops._ptr(table), ops._code(table.dtype), table.stride(0), D, ops._ptr(rowptr), ops._ptr(col),
+            ops._ptr(adj.edge_cdf), n, ops._ptr(p["order"]), p["n_short"], ops._ptr(p["slices"]), p["n_slices"],
+            ops._ptr(p["long_rows"]), p["n_long"], p["slice_len"], ops._ptr(partials), ldp, ops._ptr(out),
+            ops._code(out.dtype), out.stride(0), act, ops._ptr(adj.err_flag), ops._stream()), "segment_reduce_weighted")
+        return out
     kp, ldk = (None, 0) if keys is None else (ops._ptr(keys), keys.stride(0))
     nat.check(nat.lib().gsage_segment_reduce(
         mode, ops._ptr(table), ops._code(table.dtype), table.stride(0), D, kp, ldk, ops._ptr(rowptr), ops._ptr(col), n,
@@ -145,6 +165,7 @@ def _layer_device(layer, H, adj):
     out = torch.empty(N, 2 * h, dtype=torch.float32, device=H.device)
     out[:, :h] = ops.linear(H, layer.fc_x.weight, None, code)
     right = out[:, h:]
+    mean = nat.SEG_WEIGHTED_MEAN if _weighted(adj) else nat.SEG_MEAN
     if isinstance(layer, PoolAggregator) and layer.pool_fn == "max":
         lin = layer.mlp[0]
         Q = _table(ops.linear(H, lin.weight, lin.bias, nat.ACT_RELU, out_dtype=cdt))
@@ -155,7 +176,7 @@ def _layer_device(layer, H, adj):
         lin = layer.mlp[0]
         Q = ops.linear(H, lin.weight, lin.bias, nat.ACT_RELU, out_dtype=cdt)
         P = _table(ops.linear(Q, layer.fc_neib.weight, None, nat.ACT_NONE, out_dtype=cdt))
-        segment_reduce(adj, P[:, :h], nat.SEG_MEAN, right, code)
+        segment_reduce(adj, P[:, :h], mean, right, code)
     elif isinstance(layer, AttentionAggregator):
         P = _table(ops.linear(H, layer.fc_neib.weight, None, nat.ACT_NONE, out_dtype=cdt))
         A = layer._att(H)
@@ -164,12 +185,36 @@ def _layer_device(layer, H, adj):
         segment_reduce(adj, P[:, :h], nat.SEG_SOFTMAX_WEIGHTED, right, code, keys=keys)
     else:
         P = _table(ops.linear(H, layer.fc_neib.weight, None, nat.ACT_NONE, out_dtype=cdt))
-        segment_reduce(adj, P[:, :h], nat.SEG_MEAN, right, code)
+        segment_reduce(adj, P[:, :h], mean, right, code)
     return post(out) if post is not None else out
+
+
+def _edges_weighted(adj):
+    """_edges for a weighted adjacency, plus each edge's share p_e = q_e / T_v (float32: q_e < 2^24 is exact, one
+    division).  Edges of quantum 0 are kept with p_e = 0; a row with T_v == 0 reads the dummy with p = 1."""
+    rowptr, col, n = _csr(adj)
+    deg = rowptr[1:] - rowptr[:-1]
+    cdf = adj.edge_cdf                                   # (< 2^63: the int64 view orders and subtracts like the uint64)
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64), deg)
+    first = torch.zeros(cdf.numel(), dtype=torch.bool)
+    first[rowptr[:-1][deg > 0]] = True
+    prev = torch.cat([torch.zeros(1, dtype=torch.int64), cdf[:-1]])
+    q = cdf - torch.where(first, torch.zeros_like(prev), prev)
+    T = torch.zeros(n, dtype=torch.int64)
+    T[deg > 0] = cdf[rowptr[1:][deg > 0] - 1]
+    keep = T[rows] > 0
+    empty = torch.nonzero(T == 0).view(-1)
+    dst = torch.cat([rows[keep], empty])
+    src = torch.cat([col.long()[keep], torch.zeros_like(empty)])
+    p = torch.cat([q[keep].float() / T[rows[keep]].float(), torch.ones(empty.numel())])
+    order = torch.argsort(dst, stable=True)              # row-major, a row's edges in their stored order
+    return src[order], dst[order], p[order], n
 
 
 def _edges(adj):
     """(src, dst) of every edge of N(v), v = 0..n_rows-1, degree-0 rows reading the dummy 0 (host mode)."""
+    if _weighted(adj):
+        return _edges_weighted(adj)
     rowptr, col, n = _csr(adj)
     deg = rowptr[1:] - rowptr[:-1]
     dst = torch.repeat_interleave(torch.arange(n, dtype=torch.int64), deg.clamp(min=1))
@@ -182,7 +227,10 @@ def _edges(adj):
 def _layer_host(layer, H, edges):
     src, dst, cnt, n = edges
     code, post = _split_activation(layer.activation)
-    if isinstance(layer, PoolAggregator):
+    if cnt.dtype.is_floating_point:                      # a weighted adjacency: cnt holds the edges' shares p_e
+        X = torch.relu(F.linear(H, layer.mlp[0].weight, layer.mlp[0].bias)) if isinstance(layer, PoolAggregator) else H
+        agg = torch.zeros(n, X.shape[1]).index_add_(0, dst, X[src] * cnt.unsqueeze(1))
+    elif isinstance(layer, PoolAggregator):
         lin = layer.mlp[0]
         Q = torch.relu(F.linear(H, lin.weight, lin.bias))
         if layer.pool_fn == "max":
@@ -234,6 +282,8 @@ def embeddings(model, feats, adj=None):
     dev = feats.device
     if adj is None:
         adj = model.val_sampler.csr(dev)
+    if _weighted(adj):
+        check_supported(model, adj)
     with torch.no_grad():
         settle = getattr(model, "_settle_rows", None)
         if settle is not None:

@@ -21,7 +21,7 @@ from torch.nn import functional as F
 
 from . import _native as nat
 from . import ops
-from .store import DenseAdj, DeviceCSR, RowRef
+from .store import DenseAdj, DeviceCSR, RowRef, WeightedAdj
 
 
 # --------------------------------------------------------------------------------------------
@@ -79,6 +79,8 @@ class SparseUniformNeighborSampler(object):
     rng_default = "compat"
 
     def __init__(self, adj, rng=None, seed=0):
+        if isinstance(adj, WeightedAdj):          # a weighted problem under the uniform sampler: the weights are ignored
+            adj = adj.adj
         self.adj = adj
         self._host = DeviceCSR.from_scipy(adj, torch.device("cpu"))
         self._dev = {}
@@ -157,10 +159,102 @@ class SparseUniformNeighborSampler(object):
         return self._static_calls
 
 
+class SparseWeightedNeighborSampler(object):
+    """CSR neighbour sampling with replacement in proportion to the edge weights (no reference counterpart;
+    include/gsage.h, "Weighted adjacency"): out[i*n+j] = a neighbour of ids[i] drawn with probability q_e / T, the
+    integer quanta of the adjacency's edge_cdf, or the dummy node 0 for a row without a drawable edge.  adj: a
+    store.WeightedAdj (a bare scipy matrix carries no weights: ValueError).  Same call signature, `shard`,
+    begin_capture / calls_in_capture, csr(device) and use_device_csr as SparseUniformNeighborSampler.  It always
+    draws from Philox -- there is no legacy stream to be compatible with -- and says so once when the class-wide
+    default asks for "compat"."""
+
+    _said_philox = False
+
+    def __init__(self, adj, rng=None, seed=0):
+        if not isinstance(adj, WeightedAdj):
+            raise ValueError("SparseWeightedNeighborSampler: the adjacency carries no edge weights "
+                             "(wrap it in store.WeightedAdj, or add adj_weight / train_adj_weight to the problem)")
+        if (rng or SparseUniformNeighborSampler.rng_default) != "philox" and not SparseWeightedNeighborSampler._said_philox:
+            SparseWeightedNeighborSampler._said_philox = True
+            print("gsage: the weighted sampler always draws from Philox (--rng compat has no meaning for it)",
+                  file=sys.stderr)
+        self.adj = adj
+        self._weight = torch.from_numpy(adj.weight)
+        self._host = DeviceCSR.from_scipy(adj.adj, torch.device("cpu")).with_weights(self._weight)
+        self._dev = {}
+        self.rng = "philox"
+        self.seed = int(seed)
+        self.calls = 0                # host-side call index (eager)
+        self.call_ctr = None          # device counter tensor (inside a captured graph)
+        self.shard = (0, 1)           # (rank, world): offsets the global sample index
+
+    @property
+    def degrees(self):
+        return np.diff(self._host.rowptr.numpy())
+
+    def csr(self, device):
+        device = torch.device(device)
+        if device.type == "cpu":
+            return self._host
+        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        if key not in self._dev:
+            # (the table is built where it lives: gsage_edge_cdf_build; the same bits as the host's)
+            self._dev[key] = DeviceCSR(self._host.rowptr.to(device), self._host.col.to(device), self._host.n_rows,
+                                       self._host.max_deg).with_weights(self._weight.to(device))
+        return self._dev[key]
+
+    def use_device_csr(self, csr):
+        """Walk `csr` (a weighted store.DeviceCSR already in HBM) on its device, as the uniform sampler's."""
+        if csr.edge_cdf is None:
+            raise ValueError("SparseWeightedNeighborSampler: the adjacency carries no edge weights")
+        dev = csr.device
+        self._dev[(dev.type, dev.index if dev.index is not None else torch.cuda.current_device())] = csr
+        return csr
+
+    def __call__(self, ids, n_samples=128):
+        assert n_samples > 0, 'SparseWeightedNeighborSampler: n_samples must be set explicitly'
+        ids = ids.contiguous().view(-1)
+        csr = self.csr(ids.device)
+        rank, _ = self.shard
+        ph = {"seed": self.seed, "g0": rank * int(ids.shape[0]) * n_samples}
+        if self.call_ctr is not None:
+            ph["call_ctr"] = self.call_ctr
+            ph["call_base"] = self._static_calls
+            self._static_calls += 1
+        else:
+            ph["call_base"] = self.calls
+            self.calls += 1
+        return ops.sample_csr_weighted(csr, ids, n_samples, ph)
+
+    _static_calls = 0
+
+    def begin_capture(self, counter):
+        self.call_ctr = counter
+        self._static_calls = 0
+
+    def calls_in_capture(self):
+        return self._static_calls
+
+
 sampler_lookup = {
     "uniform_neighbor_sampler": UniformNeighborSampler,
     "sparse_uniform_neighbor_sampler": SparseUniformNeighborSampler,
 }
+
+# samplers the reference does not have.  sampler_lookup stays the reference's table, name for name (the drop-in
+# surface: tests/test_host_mode.py pins it); find_sampler() resolves a --sampler-class name over both
+sampler_extensions = {
+    "sparse_weighted_neighbor_sampler": SparseWeightedNeighborSampler,
+}
+
+
+def find_sampler(name):
+    """The sampler class registered as `name`: the reference's table first, then this library's extensions."""
+    if name in sampler_lookup:
+        return sampler_lookup[name]
+    if name in sampler_extensions:
+        return sampler_extensions[name]
+    raise KeyError("unknown sampler class %r (known: %s)" % (name, ", ".join(list(sampler_lookup) + list(sampler_extensions))))
 
 
 # --------------------------------------------------------------------------------------------

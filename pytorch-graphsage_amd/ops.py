@@ -304,6 +304,107 @@ def sample_csr(csr, ids, n, sel=None, philox=None, out=None):
 
 
 # =============================================================================================
+# Weighted adjacencies: the per-edge integer CDF and the edge-weight sampler (csrc/gsage_weighted.hip)
+# =============================================================================================
+WEIGHTED_TAG = 0x57000000                                                             # include/gsage.h
+
+
+def edge_cdf(rowptr, weight, n_rows):
+    """The table of a weighted adjacency (include/gsage.h, gsage_edge_cdf_build): weight fp32 [nnz] (already
+    validated: finite, >= 0) -> int64 [nnz] holding the uint64 bits of each row's inclusive running sum of quanta
+    q_e = floor(w_e * 2^(24 - E)), (f, E) = frexp(the row's largest weight); an all-zero row stays 0.  Set-up, once per
+    adjacency.  CPU tensors: the same integers in numpy (float64 holds every scaled weight exactly)."""
+    n_rows, nnz = int(n_rows), int(weight.shape[0])
+    assert weight.dtype == torch.float32 and weight.is_contiguous() and rowptr.dtype == torch.int64
+    if weight.is_cuda:
+        cdf = torch.zeros(nnz, dtype=torch.int64, device=weight.device)
+        if nnz:
+            nat.check(nat.lib().gsage_edge_cdf_build(_ptr(rowptr), _ptr(weight), n_rows, _ptr(cdf), _stream()),
+                      "edge_cdf_build")
+        return cdf
+    rp, w = rowptr.numpy(), weight.numpy().astype(np.float64)
+    if nnz == 0:
+        return torch.zeros(0, dtype=torch.int64)
+    deg = np.diff(rp)
+    rows = np.flatnonzero(deg > 0)
+    m = np.zeros(n_rows, dtype=np.float64)
+    m[rows] = np.maximum.reduceat(w, rp[rows])
+    _, E = np.frexp(m)
+    shift = np.repeat(24 - E.astype(np.int64), deg)
+    q = np.where(np.repeat(m, deg) > 0, np.floor(np.ldexp(w, shift)), 0.0).astype(np.uint64)
+    run = np.cumsum(q, dtype=np.uint64)
+    before = np.concatenate([[0], run]).astype(np.uint64)[rp[:-1]]         # the running sum in front of each row
+    return torch.from_numpy((run - np.repeat(before, deg)).view(np.int64))
+
+
+def _mulhi64(a, b):
+    """high 64 bits of the 128-bit product of two uint64 arrays (numpy has no such product: four 32-bit pieces)"""
+    m, s = np.uint64(0xFFFFFFFF), np.uint64(32)
+    a0, a1, b0, b1 = a & m, a >> s, b & m, b >> s
+    mid = (a1 * b0 & m) + (a0 * b1 & m) + (a0 * b0 >> s)
+    return a1 * b1 + (a1 * b0 >> s) + (a0 * b1 >> s) + (mid >> s)
+
+
+def sample_csr_weighted(csr, ids, n, philox, out=None):
+    """SparseWeightedNeighborSampler.__call__ (include/gsage.h, gsage_sample_csr_weighted): n neighbours of every id,
+    each drawn in proportion to its edge's quantum; a row without a drawable edge yields the dummy 0.
+    csr: a store.DeviceCSR with an edge_cdf; philox: dict(seed, call_base, g0, call_ctr) as for sample_csr.
+    Returns LongTensor [M*n] on the ids' device.  CPU tensors: the same definition in numpy (host mode)."""
+    assert n > 0, "SparseWeightedNeighborSampler: n_samples must be set explicitly"
+    if csr.edge_cdf is None:
+        raise ValueError("sample_csr_weighted: the adjacency carries no edge weights (DeviceCSR.with_weights)")
+    ids = ids.contiguous().view(-1)
+    M = int(ids.shape[0])
+    seed, base, g0 = int(philox["seed"]), int(philox.get("call_base", 0)), int(philox.get("g0", 0))
+    ctr = philox.get("call_ctr")
+    if ids.is_cuda:
+        if out is None:
+            out = torch.empty(M * n, dtype=torch.int64, device=ids.device)
+        assert out.dtype == torch.int64 and out.numel() == M * n and out.is_contiguous()
+        nat.check(nat.lib().gsage_sample_csr_weighted(_ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.edge_cdf), csr.n_rows,
+                                                      _ptr(ids), M, n, seed, _ptr(ctr), base, g0, _ptr(out),
+                                                      _ptr(csr.err_flag), _stream()), "sample_csr_weighted")
+        return out
+    # ---- host mode
+    idn = ids.numpy()
+    if idn.size and (idn.min() < 0 or idn.max() >= csr.n_rows):
+        raise IndexError("sampler: node id out of range of the adjacency")
+    count = M * n
+    if count == 0 or csr.nnz == 0:
+        return torch.zeros(count, dtype=torch.int64)
+    call = (base + (int(ctr.item()) if ctr is not None else 0)) & 0xFFFFFFFFFFFFFFFF
+    g = (np.arange(count, dtype=np.uint64) + np.uint64(g0 & 0xFFFFFFFFFFFFFFFF))
+    blk = g >> np.uint64(1)
+    mask, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    c = [blk & mask, blk >> s32, np.full(count, call & 0xFFFFFFFF, dtype=np.uint64),
+         np.full(count, call >> 32, dtype=np.uint64)]
+    k0, k1 = seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ WEIGHTED_TAG
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> s32) ^ c[1] ^ np.uint64(k0)) & mask, p1 & mask, ((p0 >> s32) ^ c[3] ^ np.uint64(k1)) & mask, p0 & mask]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    odd = (g & np.uint64(1)).astype(bool)
+    r64 = (np.where(odd, c[2], c[0]) << s32) | np.where(odd, c[3], c[1])
+    rp, col, cdf = csr.rowptr.numpy(), csr.col.numpy(), csr.edge_cdf.numpy().view(np.uint64)
+    beg, end = np.repeat(rp[idn], n), np.repeat(rp[idn + 1], n)
+    T = np.where(end > beg, cdf[np.maximum(end, 1) - 1], np.uint64(0)).astype(np.uint64)
+    live = T > 0
+    x = _mulhi64(r64, T)
+    lo, hi = np.where(live, beg, 0), np.where(live, end - 1, 0)          # cdf[end - 1] = T > x: the answer is in [lo, hi]
+    while True:
+        act = lo < hi
+        if not act.any():
+            break
+        mid = (lo + hi) >> 1
+        gt = cdf[mid] > x
+        hi = np.where(act & gt, mid, hi)
+        lo = np.where(act & ~gt, mid + 1, lo)
+    vals = col[lo].astype(np.int64) if col.shape[0] else np.zeros(count, dtype=np.int64)
+    return torch.from_numpy(np.where(live, vals, 0).astype(np.int64))
+
+
+# =============================================================================================
 # Unsupervised batches: random-walk positives + degree^0.75 negatives (csrc/gsage_unsup.hip)
 # =============================================================================================
 UNSUP_TAG_LEN, UNSUP_TAG_STEP, UNSUP_TAG_NEG = 0x4C000000, 0x53000000, 0x4E000000     # include/gsage.h

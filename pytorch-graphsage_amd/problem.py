@@ -8,6 +8,9 @@ chunking rule (n_chunks = len // batch_size + 1, np.array_split) and its draw fr
 global stream for the shuffle.  Differences:
   * the file may be the reference's HDF5 (needs h5py) or an .npz twin with the same keys
     (SURVEY section 8(f) row 1: h5py is absent from the build image);
+  * a sparse problem may carry edge weights: optional keys `adj_weight` / `train_adj_weight`, in the encoding of `adj`
+    ((v, r, c) with v the weights); `adj` / `train_adj` then become store.WeightedAdj (what
+    sparse_weighted_neighbor_sampler needs; the uniform samplers ignore the weights).  Files without them load as before;
   * with cuda=True the feature matrix becomes a store.FeatureStore resident in HBM
     (bf16 rows padded to 128 B; fp32 when ops.config.compute_dtype == "fp32") instead of a
     FloatTensor, so per-batch gathers are fused into the aggregator kernels.
@@ -21,7 +24,7 @@ from scipy.sparse import csr_matrix
 from torch.nn import functional as F
 
 from . import ops
-from .store import FeatureStore
+from .store import FeatureStore, WeightedAdj
 
 
 class ProblemLosses:
@@ -184,6 +187,22 @@ def parse_csr_matrix(x):
     return csr_matrix((v, (r, c)))
 
 
+def _weighted(adj, w):
+    """adj with the weights of the problem file's (v, r, c) triple `w` (v: the weights), or adj itself without one"""
+    if w is None:
+        return adj
+    if not sparse.issparse(adj):
+        raise ValueError("edge weights need a sparse adjacency")
+    if not sparse.issparse(w):
+        v, r, c = np.asarray(w)
+        w = csr_matrix((v.astype(np.float32), (r.astype(np.int64), c.astype(np.int64))), shape=adj.shape)
+    return WeightedAdj(adj, w)
+
+
+def _is_sparse(adj):
+    return sparse.issparse(adj) or isinstance(adj, WeightedAdj)
+
+
 def _scalar(v):
     v = np.asarray(v)
     v = v.item() if v.shape == () else v
@@ -211,6 +230,8 @@ def save_problem_npz(path, problem):
     for k, v in problem.items():
         if v is None:
             continue
+        if isinstance(v, WeightedAdj):              # (its weights travel under their own key: `adj_weight`)
+            v = v.adj
         if sparse.issparse(v):
             coo = v.tocoo()
             v = np.vstack([coo.data, coo.row, coo.col])
@@ -228,8 +249,8 @@ class NodeProblem(object):
         self.folds = np.array([s.decode() if isinstance(s, bytes) else str(s) for s in f['folds']])
         self.targets = f['targets']
         if 'sparse' in f and bool(_scalar(f['sparse'])):
-            self.adj = parse_csr_matrix(f['adj'])
-            self.train_adj = parse_csr_matrix(f['train_adj'])
+            self.adj = _weighted(parse_csr_matrix(f['adj']), f.get('adj_weight'))
+            self.train_adj = _weighted(parse_csr_matrix(f['train_adj']), f.get('train_adj_weight'))
         else:
             self.adj = f['adj']
             self.train_adj = f['train_adj']
@@ -245,15 +266,18 @@ class NodeProblem(object):
         print('NodeProblem: loading finished')
 
     @classmethod
-    def from_arrays(cls, task, n_classes, adj, train_adj, feats, folds, targets, cuda=True):
+    def from_arrays(cls, task, n_classes, adj, train_adj, feats, folds, targets, cuda=True, adj_weight=None,
+                    train_adj_weight=None):
         """The same object from arrays already in memory (the keys of utils/convert.py:192-202): adj / train_adj a
         scipy csr_matrix in the (v, r, c) convention (sparse problems) or an int array [n + 1, K] (dense), feats a
         float array / FeatureStore / None.  What bench.py's CLI measurements and the tests use instead of writing a
-        multi-GB problem file first; everything downstream of the loader is the code path of `NodeProblem(path)`."""
+        multi-GB problem file first; everything downstream of the loader is the code path of `NodeProblem(path)`.
+        adj_weight / train_adj_weight (sparse problems): edge weights as store.WeightedAdj takes them."""
         self = object.__new__(cls)
         self.task, self.n_classes = str(task), int(n_classes) if n_classes is not None else 1
         self.feats, self.folds, self.targets = feats, np.asarray(folds), targets
-        self.adj, self.train_adj = adj, train_adj
+        self.adj = adj if adj_weight is None else WeightedAdj(adj, adj_weight)
+        self.train_adj = train_adj if train_adj_weight is None else WeightedAdj(train_adj, train_adj_weight)
         self.feats_dim = feats.shape[1] if feats is not None else None
         self.n_nodes = self.adj.shape[0]
         self.cuda = cuda
@@ -269,7 +293,7 @@ class NodeProblem(object):
         return self
 
     def _to_device(self):
-        if not sparse.issparse(self.adj):
+        if not _is_sparse(self.adj):
             self.adj = torch.LongTensor(np.asarray(self.adj))
             self.train_adj = torch.LongTensor(np.asarray(self.train_adj))
             if self.cuda:

@@ -4,7 +4,10 @@ store.py -- HBM-resident data layouts of the hot path.
   DeviceCSR     the adjacency the sampler walks: (rowptr int64 [n_rows+1], col int32 [nnz]) built
                 once from the reference's scipy csr_matrix (problem.py:70-72: csr_matrix((v,(r,c)))
                 in the convention of utils/convert.py:100-126 -- ids 1-based, row 0 the dummy,
-                row i's neighbours in columns 0..deg_i-1).
+                row i's neighbours in columns 0..deg_i-1).  Optionally weighted: `edge_cdf`, one
+                uint64 per stored edge (include/gsage.h, "Weighted adjacency"), built by with_weights().
+  WeightedAdj   the reference-convention scipy matrix plus one fp32 weight per stored edge: what a
+                weighted problem hands to the samplers in place of the bare matrix.
   FeatureStore  the node-feature table feats[N+1, D] (problem.py:118-121) kept in HBM as a
                 row-major [n_rows, ld] matrix, bf16 (default on GPU) or fp32, rows padded with zeros
                 to a multiple of 128 bytes so every row is a whole number of cache lines and
@@ -63,12 +66,48 @@ def row_positions(indptr):
     return np.cumsum(step, dtype=np.int32)
 
 
+def _canonical_csr(adj):
+    """adj as a scipy CSR with sorted indices (the order DeviceCSR.from_scipy stores the edges in)"""
+    adj = adj.tocsr()
+    return adj if adj.has_sorted_indices else adj.sorted_indices()
+
+
+class WeightedAdj(object):
+    """A sparse adjacency in the reference's convention with one fp32 weight per stored edge.  `weight`: a scipy
+    matrix with the structure of `adj` (same indptr / indices once both are in canonical order) whose data are the
+    weights, or a flat array aligned with the data of `adj` in canonical (row-major, sorted-column) order; anything
+    else is a ValueError.  Forwards `.shape`, so whatever only asks an adjacency for its size takes it as is; the
+    weighted sampler reads `.adj` and `.weight`, the uniform samplers `.adj` alone.  The values are validated where
+    the table is built (DeviceCSR.with_weights)."""
+
+    def __init__(self, adj, weight):
+        from scipy import sparse
+        if not sparse.issparse(adj):
+            raise ValueError("WeightedAdj: the adjacency must be a scipy sparse matrix")
+        self.adj = _canonical_csr(adj)
+        if sparse.issparse(weight):
+            w = _canonical_csr(weight)
+            if w.shape[0] != self.adj.shape[0] or not np.array_equal(w.indptr, self.adj.indptr) or \
+                    not np.array_equal(w.indices, self.adj.indices):
+                raise ValueError("WeightedAdj: the weight matrix does not have the adjacency's structure")
+            weight = w.data
+        weight = np.asarray(weight)
+        if weight.ndim != 1 or weight.shape[0] != self.adj.nnz:
+            raise ValueError("WeightedAdj: %s weights for %d stored edges" % (weight.shape, self.adj.nnz))
+        self.weight = np.ascontiguousarray(weight, dtype=np.float32)
+
+    @property
+    def shape(self):
+        return self.adj.shape
+
+
 class DeviceCSR(object):
-    def __init__(self, rowptr, col, n_rows, max_deg):
+    def __init__(self, rowptr, col, n_rows, max_deg, edge_cdf=None):
         self.rowptr = rowptr          # int64 [n_rows + 1]
         self.col = col                # int32 [nnz]
         self.n_rows = int(n_rows)     # adj.shape[0]  (counts the dummy row)
         self.max_deg = int(max_deg)   # adj.shape[1]: the population `sel` is drawn from
+        self.edge_cdf = edge_cdf      # weighted: int64 [nnz] holding the uint64 bits of the per-row running sums
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=rowptr.device)
 
     @property
@@ -79,12 +118,32 @@ class DeviceCSR(object):
     def nnz(self):
         return int(self.col.shape[0])
 
+    def with_weights(self, weight):
+        """Make this adjacency weighted: weight = one fp32 per stored edge, aligned with `col`, finite and >= 0
+        (ValueError otherwise -- checked here, once, by reductions on the adjacency's device).  Builds `edge_cdf`
+        (gsage_edge_cdf_build on the GPU, the same integers in numpy on the CPU) and returns self.  An edge lighter
+        than 2^-24 of its row's heaviest gets the quantum 0 and is never drawn."""
+        from . import ops
+        w = torch.as_tensor(weight).to(device=self.device, dtype=torch.float32).contiguous().view(-1)
+        if int(w.shape[0]) != self.nnz:
+            raise ValueError("with_weights: %d weights for %d stored edges" % (int(w.shape[0]), self.nnz))
+        if w.numel() and not bool((torch.isfinite(w) & (w >= 0)).all()):
+            raise ValueError("with_weights: edge weights must be finite and >= 0")
+        self.edge_cdf = ops.edge_cdf(self.rowptr, w, self.n_rows)
+        return self
+
     @staticmethod
-    def from_scipy(adj, device):
+    def from_scipy(adj, device, weight=None):
         """adj: scipy.sparse matrix in the reference convention.  Checks the convention instead
         of silently re-interpreting it: the reference indexes a row by COLUMN (nn_modules.py:90-93),
-        which equals the position inside the row only when columns are 0..deg-1."""
+        which equals the position inside the row only when columns are 0..deg-1.  weight (optional): as
+        for WeightedAdj; the result then carries its edge_cdf (with_weights)."""
         from scipy import sparse
+        if isinstance(adj, WeightedAdj):
+            adj = adj.adj
+        if weight is not None:
+            wadj = WeightedAdj(adj, weight)
+            return DeviceCSR.from_scipy(wadj.adj, device).with_weights(wadj.weight)
         assert sparse.issparse(adj), "SparseUniformNeighborSampler: not sparse.issparse(adj)"
         adj = adj.tocsr()
         if not adj.has_sorted_indices:

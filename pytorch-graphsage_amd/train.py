@@ -38,6 +38,11 @@ Layer-wise full-neighbourhood inference (infer.py, opt-in; the default output is
 random-walk positives, degree^0.75 negatives, skip-gram loss on the HIP head).  Targets are ignored; every batch
 prints one JSON line with its loss, every epoch the validation fold's loss and mean reciprocal rank ("mrr").  The
 module path runs it (said on stderr); data-parallel launches are refused.
+
+--sampler-class sparse_weighted_neighbor_sampler: neighbours drawn in proportion to edge weights (a problem file with
+`adj_weight` / `train_adj_weight`; include/gsage.h, "Weighted adjacency").  Always Philox; the module path runs it (said
+on stderr); --full-neighbour-eval / --save-embeddings compute the weight-normalised mean (mean and mean-pool models);
+--unsupervised is refused: its walks are unweighted.
 """
 from __future__ import division, print_function
 
@@ -247,7 +252,7 @@ def build_model(args, problem):
             "activation": (lambda x: x) if last else F.relu,     # train.py:105-118
         })
     common = dict(
-        sampler_class=sampler_lookup[args.sampler_class], adj=problem.adj, train_adj=problem.train_adj,
+        sampler_class=gs.find_sampler(args.sampler_class), adj=problem.adj, train_adj=problem.train_adj,
         prep_class=prep_lookup[args.prep_class], aggregator_class=aggregator_lookup[args.aggregator_class],
         input_dim=problem.feats_dim, n_nodes=problem.n_nodes,
         layer_specs=specs, lr_init=args.lr_init, lr_schedule=args.lr_schedule,
@@ -274,6 +279,13 @@ def main(argv=None, problem=None):
     ddp = gs.dist.init_from_env(args.cuda)            # no-op outside torch.distributed.run
     if problem is None:
         problem = NodeProblem(problem_path=args.problem_path, cuda=args.cuda)
+    weighted = args.sampler_class == 'sparse_weighted_neighbor_sampler'
+    if weighted:
+        if not (isinstance(problem.adj, gs.store.WeightedAdj) and isinstance(problem.train_adj, gs.store.WeightedAdj)):
+            raise SystemExit('gsage: --sampler-class sparse_weighted_neighbor_sampler: this problem has no edge weights '
+                             '(adj_weight / train_adj_weight)')
+        if args.unsupervised:
+            raise SystemExit('gsage: --unsupervised: the weighted sampler is not supported (random walks are unweighted)')
     if args.feature_dtype == 'fp8':
         if problem.feats is None:
             raise SystemExit('gsage: --feature-dtype fp8: this problem has no feature table')
@@ -299,7 +311,7 @@ def main(argv=None, problem=None):
         return train_unsupervised(args, problem, model)
     if args.full_neighbour_eval or args.save_embeddings:
         try:
-            gs.infer.check_supported(model)
+            gs.infer.check_supported(model, model.val_sampler.csr('cpu') if weighted else None)
         except ValueError as e:
             raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings: %s' % e)
     evaluate_fn = (lambda mode: full_neighbour_evaluate(model, problem, mode=mode)) if args.full_neighbour_eval else \
@@ -405,6 +417,8 @@ def choose_engine(args, problem, model, ddp):
         return None
     if args.unsupervised:                           # no fused engine is attempted
         return give_up('unsupervised model')
+    if isinstance(model.train_sampler, gs.nn_modules.SparseWeightedNeighborSampler):
+        return give_up('no fused engine covers the weighted sampler (SparseWeightedNeighborSampler)')
     cls = gs.engine.fused_engine_for(model, problem.feats, explain=True, ddp=ddp)
     if cls is None:
         return give_up('no fused engine covers this model')
