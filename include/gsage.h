@@ -1114,6 +1114,63 @@ int gsage_segment_reduce_weighted(const void *table, int dtype, int64_t ld, int6
                                   int64_t n_long, int32_t slice_len, float *partials, int64_t ldp, void *out,
                                   int out_dtype, int64_t out_ld, int act, int32_t *err_flag, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * k-hop closure blocks (csrc/gsage_block.hip, csrc/gsage_fullgraph.hip): full-neighbourhood inference for a query
+ * set (infer.closure / infer.query).  Additive; the ABI version is unchanged.  No reference counterpart.
+ *
+ * Node sets S_L c ... c S_0 of a query vector over a CSR (rowptr int64, col int32, optional cdf):
+ *     S_L     = the queries, duplicates removed, in order of first appearance
+ *     S_{l-1} = S_l unchanged as a prefix, then the nodes of N(S_l) u {0} not yet present, in ascending id
+ * Row 0 (the dummy) is a member of every source set.  A node's position in its set is its local index, the same in
+ * every larger set.  Block l (destinations S_l, sources S_{l-1}): rowptr int64 [n_dst + 1]; col int32 = the stored
+ * rows of S_l, whole, in stored order, duplicates kept, each id replaced by its local index; cdf = the rows' segments
+ * verbatim.  An id outside [0, n_rows) raises *err_flag (int32, may be NULL) and is dropped from the sets; in a block's
+ * col it is the dummy's local index.
+ *
+ * State the caller keeps per adjacency and hands to every call:
+ *     local   int32 [n_rows]               -1 everywhere between queries
+ *     bitmap  uint32 [ceil(n_rows / 32)]   0 everywhere between queries
+ * Scratch: sums int64 [ceil(n / gsage_closure_span()) + 1] per scan over n items; the scans are three-phase (per-
+ * workgroup sums over spans of gsage_closure_span() items, scan of the sums, apply): no workgroup waits for another.
+ *
+ * gsage_closure_seed_count (3 launches)   counts[0] = |S_L|.  The caller reads it back and allocates set.
+ * gsage_closure_seed_write (3 launches)   set[0 .. n_set) = S_L, local[] of its members, pos[i] = the local index of
+ *                                         queries[i] (-1 for an id outside the graph).  1 <= nq < 2^31.
+ * gsage_closure_expand_count (4 launches) marks N(set[lo .. hi)) -- the members the previous hop added -- and the
+ *                                         dummy; counts[0] = new members, counts[1] = edges of block (rows set[0 .. hi)),
+ *                                         counts[2] = the dummy's local index in the grown set.  One readback.
+ * gsage_closure_expand_write (3 launches) set[n_dst .. n_dst + counts[0]) = the new members, ascending (the caller has
+ *                                         copied the prefix), their local[], the bitmap cleared; blk_rowptr [n_dst + 1],
+ *                                         blk_col / blk_cdf [counts[1]] (blk_cdf NULL when cdf is).
+ * gsage_closure_restore (1 launch)        local[set[i]] = -1, i < n: over S_0 it puts the state back.
+ *
+ * gsage_segment_reduce_block -- gsage_segment_reduce / _weighted over a block: n_dst output rows; table (and keys) of
+ * n_src >= n_dst rows, a neighbour id is bounded by n_src; a row of degree 0, a weighted row without a drawable edge
+ * and an id outside the table read row `dummy`.  cdf non-NULL exactly for GSAGE_SEG_WEIGHTED_MEAN.  The plan is built
+ * over the block's rowptr with the same slice_len, so a block's row has the whole graph's edges, order and slices:
+ * its output equals the whole-graph call's row bit for bit.  The whole-graph entry points are n_src = n_rows, dummy = 0.
+ * ---------------------------------------------------------------------------------------- */
+/* HOST: items per workgroup of the closure's scans (bitmap words, set members, queries) */
+int64_t gsage_closure_span(void);
+int gsage_closure_seed_count(const int64_t *queries, int64_t nq, int64_t n_rows, int32_t *local, int64_t *sums,
+                             int64_t *counts, int32_t *err_flag, void *stream);
+int gsage_closure_seed_write(const int64_t *queries, int64_t nq, int64_t n_rows, int32_t *local, const int64_t *sums,
+                             int64_t *set, int64_t n_set, int64_t *pos, void *stream);
+int gsage_closure_expand_count(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const int64_t *set, int64_t lo,
+                               int64_t hi, const int32_t *local, uint32_t *bitmap, int64_t *sums_words,
+                               int64_t *sums_rows, int64_t *counts, int32_t *err_flag, void *stream);
+int gsage_closure_expand_write(const int64_t *rowptr, const int32_t *col, const uint64_t *cdf, int64_t n_rows,
+                               int64_t *set, int64_t n_dst, int32_t *local, uint32_t *bitmap, const int64_t *sums_words,
+                               const int64_t *sums_rows, int64_t *blk_rowptr, int32_t *blk_col, uint64_t *blk_cdf,
+                               int32_t *err_flag, void *stream);
+int gsage_closure_restore(const int64_t *set, int64_t n, int32_t *local, void *stream);
+int gsage_segment_reduce_block(int mode, const void *table, int dtype, int64_t ld, int64_t D, const float *keys,
+                               int64_t ldk, const int64_t *rowptr, const int32_t *col, const uint64_t *cdf,
+                               int64_t n_dst, int64_t n_src, int64_t dummy, const int32_t *order, int64_t n_short,
+                               const int64_t *slices, int64_t n_slices, const int64_t *long_rows, int64_t n_long,
+                               int32_t slice_len, float *partials, int64_t ldp, void *out, int out_dtype,
+                               int64_t out_ld, int act, int32_t *err_flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

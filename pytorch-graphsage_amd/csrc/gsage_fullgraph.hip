@@ -25,6 +25,10 @@
 //
 // Loads: 16 bytes per lane, 8 neighbour rows in flight per lane, the ids of the next batch requested before the
 // rows of the current one (the idiom of gather_mean_chunk, gsage_gather.hip).  Columns >= D are never stored.
+//
+// Blocks (gsage_segment_reduce_block, infer.query): the same kernels over a block of a k-hop closure
+// (csrc/gsage_block.hip) -- n_dst output rows reading a table and keys of n_src >= n_dst rows, ids bounded by n_src, and
+// the dummy at a local index the caller names.  The whole-graph entry points are the case n_src = n_rows, dummy = 0.
 #include "gsage_common.h"
 
 namespace gsage {
@@ -58,7 +62,9 @@ struct FgArgs {
     int64_t ldk;
     const int64_t *rowptr;
     const int32_t *col;
-    int64_t n_rows;
+    int64_t n_rows;                 // output rows
+    int64_t n_src;                  // rows of the table and keys: the bound of a neighbour id (a block: > n_rows)
+    int32_t dummy;                  // the row a row without a (drawable) edge, or an id outside the table, reads
     const int32_t *order;           // short rows, degree-descending
     int64_t n_short;
     const int64_t *slices;          // [n_slices, 2]: (row, first edge)
@@ -72,7 +78,7 @@ struct FgArgs {
     int64_t out_ld;
     int32_t act;
     int32_t team;                   // lanes per row: 8, 16, 32 or 64
-    int32_t *err;                   // set to 1 when a neighbour id is outside [0, n_rows)
+    int32_t *err;                   // set to 1 when a neighbour id is outside [0, n_src)
     const uint64_t *cdf;            // WEIGHTED_MEAN: the adjacency's inclusive per-row running sums of quanta [nnz]
 };
 
@@ -98,7 +104,7 @@ __device__ __forceinline__ float team8_sum(float s)
     return s;
 }
 
-// Walk edges [beg, beg + cnt) of one row (cnt == 0: the dummy neighbour 0) for the column chunk at c0.  Every lane
+// Walk edges [beg, beg + cnt) of one row (cnt == 0: the dummy neighbour) for the column chunk at c0.  Every lane
 // of the team runs this with the same beg / cnt (the score of SOFTMAX_WEIGHTED is a cross-lane sum); `live` lanes
 // own a chunk inside Dp.
 template <typename TI, int MODE>
@@ -111,11 +117,11 @@ __device__ __forceinline__ void fg_walk(const FgArgs &a, int64_t beg, int64_t cn
     const int64_t n = cnt > 0 ? cnt : 1;
     const int32_t cc = live ? c0 : 0;
     auto id_at = [&](int64_t j) -> int32_t {
-        if (cnt == 0) return 0;
+        if (cnt == 0) return a.dummy;
         int32_t id = col[min(j, cnt - 1)];
-        if ((uint32_t)id >= (uint64_t)a.n_rows) {
+        if ((uint32_t)id >= (uint64_t)a.n_src) {
             if (a.err) *a.err = 1;
-            id = 0;
+            id = a.dummy;
         }
         return id;
     };
@@ -310,7 +316,7 @@ __global__ __launch_bounds__(FG_THREADS) void k_segment_merge(FgArgs a)
         for (int e = 0; e < VEC; ++e)
             r[e] = MODE == GSAGE_SEG_MAX || MODE == GSAGE_SEG_WEIGHTED_MEAN ? r[e] : r[e] / inv;
         if (MODE == GSAGE_SEG_WEIGHTED_MEAN && T == 0) {            // a long row of zero weights: the dummy's row
-            const vec16 v0 = *reinterpret_cast<const vec16 *>((const TI *)a.table + c0);
+            const vec16 v0 = *reinterpret_cast<const vec16 *>((const TI *)a.table + (int64_t)a.dummy * a.ld + c0);
 #pragma unroll
             for (int e = 0; e < VEC; ++e) r[e] = fg_io<TI>::elem(v0, e);
         }
@@ -362,10 +368,10 @@ int64_t gsage_segment_reduce_ldp(int64_t D)
 
 static int segment_reduce_any(int mode, const void *table, int dtype, int64_t ld, int64_t D, const float *keys,
                               int64_t ldk, const int64_t *rowptr, const int32_t *col, const uint64_t *cdf,
-                              int64_t n_rows, const int32_t *order, int64_t n_short, const int64_t *slices,
-                              int64_t n_slices, const int64_t *long_rows, int64_t n_long, int32_t slice_len,
-                              float *partials, int64_t ldp, void *out, int out_dtype, int64_t out_ld, int act,
-                              int32_t *err_flag, void *stream)
+                              int64_t n_rows, int64_t n_src, int64_t dummy, const int32_t *order, int64_t n_short,
+                              const int64_t *slices, int64_t n_slices, const int64_t *long_rows, int64_t n_long,
+                              int32_t slice_len, float *partials, int64_t ldp, void *out, int out_dtype, int64_t out_ld,
+                              int act, int32_t *err_flag, void *stream)
 {
     GSAGE_REQUIRE(dtype == GSAGE_BF16 || dtype == GSAGE_F32, "segment_reduce: table dtype must be bf16 or fp32");
     GSAGE_REQUIRE(out_dtype == GSAGE_BF16 || out_dtype == GSAGE_F32, "segment_reduce: out dtype must be bf16 or fp32");
@@ -376,6 +382,8 @@ static int segment_reduce_any(int mode, const void *table, int dtype, int64_t ld
     GSAGE_REQUIRE(ld % vec == 0 && Dp <= ld, "segment_reduce: ld must be a multiple of 16 bytes holding D");
     GSAGE_REQUIRE(out_ld >= D, "segment_reduce: out_ld smaller than D");
     GSAGE_REQUIRE(n_rows > 0 && n_rows < ((int64_t)1 << 31), "segment_reduce: bad n_rows");
+    GSAGE_REQUIRE(n_src >= n_rows && n_src < ((int64_t)1 << 31) && dummy >= 0 && dummy < n_src,
+                  "segment_reduce: a block needs n_dst <= n_src < 2^31 and a dummy inside the table");
     GSAGE_REQUIRE(n_short >= 0 && n_slices >= 0 && n_long >= 0 && n_short + n_long <= n_rows &&
                   n_long <= n_slices, "segment_reduce: bad plan sizes");
     GSAGE_REQUIRE(slice_len >= 8 && slice_len % 8 == 0, "segment_reduce: slice_len must be a positive multiple of 8");
@@ -394,7 +402,7 @@ static int segment_reduce_any(int mode, const void *table, int dtype, int64_t ld
     FgArgs a;
     a.table = table; a.ld = ld; a.D = (int32_t)D; a.Dp = (int32_t)Dp;
     a.keys = keys; a.ldk = ldk;
-    a.rowptr = rowptr; a.col = col; a.n_rows = n_rows;
+    a.rowptr = rowptr; a.col = col; a.n_rows = n_rows; a.n_src = n_src; a.dummy = (int32_t)dummy;
     a.order = order; a.n_short = n_short;
     a.slices = slices; a.n_slices = n_slices; a.long_rows = long_rows; a.n_long = n_long;
     a.slice_len = slice_len; a.partials = partials; a.ldp = ldp;
@@ -418,8 +426,8 @@ int gsage_segment_reduce(int mode, const void *table, int dtype, int64_t ld, int
 {
     GSAGE_REQUIRE(mode == GSAGE_SEG_MEAN || mode == GSAGE_SEG_MAX || mode == GSAGE_SEG_SOFTMAX_WEIGHTED,
                   "segment_reduce: unknown mode %d", mode);
-    return segment_reduce_any(mode, table, dtype, ld, D, keys, ldk, rowptr, col, nullptr, n_rows, order, n_short, slices,
-                              n_slices, long_rows, n_long, slice_len, partials, ldp, out, out_dtype, out_ld, act,
+    return segment_reduce_any(mode, table, dtype, ld, D, keys, ldk, rowptr, col, nullptr, n_rows, n_rows, 0, order, n_short,
+                              slices, n_slices, long_rows, n_long, slice_len, partials, ldp, out, out_dtype, out_ld, act,
                               err_flag, stream);
 }
 
@@ -429,9 +437,25 @@ int gsage_segment_reduce_weighted(const void *table, int dtype, int64_t ld, int6
                                   int64_t n_long, int32_t slice_len, float *partials, int64_t ldp, void *out,
                                   int out_dtype, int64_t out_ld, int act, int32_t *err_flag, void *stream)
 {
-    return segment_reduce_any(GSAGE_SEG_WEIGHTED_MEAN, table, dtype, ld, D, nullptr, 0, rowptr, col, cdf, n_rows, order,
-                              n_short, slices, n_slices, long_rows, n_long, slice_len, partials, ldp, out, out_dtype,
-                              out_ld, act, err_flag, stream);
+    return segment_reduce_any(GSAGE_SEG_WEIGHTED_MEAN, table, dtype, ld, D, nullptr, 0, rowptr, col, cdf, n_rows, n_rows,
+                              0, order, n_short, slices, n_slices, long_rows, n_long, slice_len, partials, ldp, out,
+                              out_dtype, out_ld, act, err_flag, stream);
+}
+
+int gsage_segment_reduce_block(int mode, const void *table, int dtype, int64_t ld, int64_t D, const float *keys,
+                               int64_t ldk, const int64_t *rowptr, const int32_t *col, const uint64_t *cdf,
+                               int64_t n_dst, int64_t n_src, int64_t dummy, const int32_t *order, int64_t n_short,
+                               const int64_t *slices, int64_t n_slices, const int64_t *long_rows, int64_t n_long,
+                               int32_t slice_len, float *partials, int64_t ldp, void *out, int out_dtype,
+                               int64_t out_ld, int act, int32_t *err_flag, void *stream)
+{
+    GSAGE_REQUIRE(mode == GSAGE_SEG_MEAN || mode == GSAGE_SEG_MAX || mode == GSAGE_SEG_SOFTMAX_WEIGHTED ||
+                  mode == GSAGE_SEG_WEIGHTED_MEAN, "segment_reduce_block: unknown mode %d", mode);
+    GSAGE_REQUIRE((mode == GSAGE_SEG_WEIGHTED_MEAN) == (cdf != nullptr),
+                  "segment_reduce_block: cdf goes with the weighted mean, and only with it");
+    return segment_reduce_any(mode, table, dtype, ld, D, keys, ldk, rowptr, col, cdf, n_dst, n_src, dummy, order, n_short,
+                              slices, n_slices, long_rows, n_long, slice_len, partials, ldp, out, out_dtype, out_ld, act,
+                              err_flag, stream);
 }
 
 }  // extern "C"

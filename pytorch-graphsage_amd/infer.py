@@ -22,7 +22,14 @@ On the GPU, fc_neib is applied BEFORE the reduction where that is exact (mean, m
 is linear in the rows), so the segment-reduce kernel (csrc/gsage_fullgraph.hip) gathers output-width rows; max-pool
 reduces the MLP output and projects afterwards.  The projections run on K5 (ops.linear).  CPU tensors take a plain
 torch restatement of the same definition (host mode).
+
+For a QUERY SET the exact answer depends only on its k-hop closure: with L layers, level L needs the queries, level
+L - 1 the queries and their neighbours, and so on down.  closure() builds the node sets S_L c ... c S_0 and one block
+per layer (csrc/gsage_block.hip: deduplicated frontier expansion and relabelling on the device), query() gathers the
+feature rows of S_0 and runs every layer over its block -- H^l has |S_l| rows -- with the same projections and the same
+segment-reduce kernels (gsage_segment_reduce_block).  The cost follows the closure, not the graph.
 """
+import numpy as np
 import torch
 from torch import nn
 from torch.nn import functional as F
@@ -117,15 +124,28 @@ def plan(adj, slice_len=SLICE_LEN):
 
 def segment_reduce(adj, table, mode, out, act=nat.ACT_NONE, keys=None):
     """out[v, :D] = reduce over N(v) of table[u, :D] for every row v of `adj` (gsage_segment_reduce: two launches).
+    `adj` may be a Block of a closure: out has its n_dst rows, table and keys the n_src rows of its source set.
     table: [n_rows, D] bf16 / fp32 CUDA tensor whose row stride is a multiple of 16 bytes; out: a (possibly
     strided) fp32 / bf16 [n_rows, D] view; keys (SOFTMAX_WEIGHTED): fp32 [n_rows, 32].  mode SEG_WEIGHTED_MEAN
     (gsage_segment_reduce_weighted) reads the adjacency's edge_cdf."""
     rowptr, col, n = _csr(adj)
     p = plan(adj)
     D = int(table.shape[1])
-    assert table.stride(1) == 1 and out.stride(1) == 1 and int(table.shape[0]) >= n and int(out.shape[0]) >= n
+    n_src = adj.n_src if isinstance(adj, Block) else n
+    assert table.stride(1) == 1 and out.stride(1) == 1 and int(table.shape[0]) >= n_src and int(out.shape[0]) >= n
     ldp = int(nat.lib().gsage_segment_reduce_ldp(D))
     partials = torch.empty(max(p["n_slices"], 1), ldp, dtype=torch.float32, device=table.device)
+    if isinstance(adj, Block):
+        # a block of a closure: n output rows over a table (and keys) of n_src rows, the dummy at adj.dummy
+        assert (mode == nat.SEG_WEIGHTED_MEAN) == _weighted(adj) and (keys is None or int(keys.shape[0]) >= n_src)
+        kp, ldk = (None, 0) if keys is None else (ops._ptr(keys), keys.stride(0))
+        nat.check(nat.lib().gsage_segment_reduce_block(
+            mode, ops._ptr(table), ops._code(table.dtype), table.stride(0), D, kp, ldk, ops._ptr(rowptr), adj.col_ptr(),
+            adj.cdf_ptr(), n, n_src, adj.dummy, ops._ptr(p["order"]), p["n_short"],
+            ops._ptr(p["slices"]), p["n_slices"], ops._ptr(p["long_rows"]), p["n_long"], p["slice_len"],
+            ops._ptr(partials), ldp, ops._ptr(out), ops._code(out.dtype), out.stride(0), act, ops._ptr(adj.err_flag),
+            ops._stream()), "segment_reduce_block")
+        return out
     if mode == nat.SEG_WEIGHTED_MEAN:
         assert _weighted(adj) and int(adj.edge_cdf.shape[0]) == int(col.shape[0])
         nat.check(nat.lib().gsage_segment_reduce_weighted(
@@ -158,12 +178,18 @@ def _table(t):
 # one layer
 # --------------------------------------------------------------------------------------------
 def _layer_device(layer, H, adj):
+    """One layer over the whole graph, or over a Block: H holds the rows of the block's source set, the result its
+    n_dst destination rows (a destination's local index is its index in H: fc_x reads H[:n_dst])."""
     code, post = _split_activation(layer.activation)
     cdt = ops.torch_dtype()
     h = layer.output_dim_
-    N = int(H.shape[0])
+    n_src = int(H.shape[0])
+    N = adj.n_dst if isinstance(adj, Block) else n_src
     out = torch.empty(N, 2 * h, dtype=torch.float32, device=H.device)
-    out[:, :h] = ops.linear(H, layer.fc_x.weight, None, code)
+    Hd = H
+    if N != n_src:                  # (a row prefix of rows this library padded keeps their tag: no padding copy)
+        Hd = ops.mark_zero_padded(H[:N]) if ops._trusted(H) else H[:N]
+    out[:, :h] = ops.linear(Hd, layer.fc_x.weight, None, code)
     right = out[:, h:]
     mean = nat.SEG_WEIGHTED_MEAN if _weighted(adj) else nat.SEG_MEAN
     if isinstance(layer, PoolAggregator) and layer.pool_fn == "max":
@@ -180,7 +206,7 @@ def _layer_device(layer, H, adj):
     elif isinstance(layer, AttentionAggregator):
         P = _table(ops.linear(H, layer.fc_neib.weight, None, nat.ACT_NONE, out_dtype=cdt))
         A = layer._att(H)
-        keys = torch.zeros(N, 32, dtype=torch.float32, device=H.device)
+        keys = torch.zeros(n_src, 32, dtype=torch.float32, device=H.device)
         keys[:, :A.shape[1]] = A
         segment_reduce(adj, P[:, :h], nat.SEG_SOFTMAX_WEIGHTED, right, code, keys=keys)
     else:
@@ -205,27 +231,28 @@ def _edges_weighted(adj):
     keep = T[rows] > 0
     empty = torch.nonzero(T == 0).view(-1)
     dst = torch.cat([rows[keep], empty])
-    src = torch.cat([col.long()[keep], torch.zeros_like(empty)])
+    src = torch.cat([col.long()[keep], torch.full_like(empty, int(getattr(adj, "dummy", 0)))])
     p = torch.cat([q[keep].float() / T[rows[keep]].float(), torch.ones(empty.numel())])
     order = torch.argsort(dst, stable=True)              # row-major, a row's edges in their stored order
     return src[order], dst[order], p[order], n
 
 
 def _edges(adj):
-    """(src, dst) of every edge of N(v), v = 0..n_rows-1, degree-0 rows reading the dummy 0 (host mode)."""
+    """(src, dst) of every edge of N(v), v = 0..n_rows-1, degree-0 rows reading the dummy (row 0; a Block: its local
+    index there) (host mode)."""
     if _weighted(adj):
         return _edges_weighted(adj)
     rowptr, col, n = _csr(adj)
     deg = rowptr[1:] - rowptr[:-1]
     dst = torch.repeat_interleave(torch.arange(n, dtype=torch.int64), deg.clamp(min=1))
-    src = torch.zeros(dst.numel(), dtype=torch.int64)
+    src = torch.full((dst.numel(),), int(getattr(adj, "dummy", 0)), dtype=torch.int64)
     has = torch.repeat_interleave(deg > 0, deg.clamp(min=1))
     src[has] = col.long()
     return src, dst, deg.clamp(min=1), n
 
 
 def _layer_host(layer, H, edges):
-    src, dst, cnt, n = edges
+    src, dst, cnt, n = edges                             # (a Block: H has the n_src source rows, n = n_dst)
     code, post = _split_activation(layer.activation)
     if cnt.dtype.is_floating_point:                      # a weighted adjacency: cnt holds the edges' shares p_e
         X = torch.relu(F.linear(H, layer.mlp[0].weight, layer.mlp[0].bias)) if isinstance(layer, PoolAggregator) else H
@@ -247,7 +274,7 @@ def _layer_host(layer, H, edges):
         agg = torch.zeros(n, H.shape[1]).index_add_(0, dst, H[src] * (e / den[dst]).unsqueeze(1))
     else:
         agg = torch.zeros(n, H.shape[1]).index_add_(0, dst, H[src]) / cnt.unsqueeze(1).float()
-    out = torch.cat([F.linear(H, layer.fc_x.weight), F.linear(agg, layer.fc_neib.weight)], dim=1)
+    out = torch.cat([F.linear(H[:n], layer.fc_x.weight), F.linear(agg, layer.fc_neib.weight)], dim=1)
     if code == nat.ACT_RELU:
         out = torch.relu(out)
     return post(out) if post is not None else out
@@ -304,10 +331,15 @@ def embeddings(model, feats, adj=None):
         return F.normalize(H.float(), dim=1)
 
 
-def full_neighbour(model, feats, nodes=None, adj=None, embeddings=False):
+def full_neighbour(model, feats, nodes=None, adj=None, embeddings=False, closure=False):
     """Logits of `model` for `nodes` (default: every row of the adjacency) by layer-wise full-neighbourhood inference,
     and, with embeddings=True, also F.normalize(H^L) for every row: returns (logits, emb).  Arguments as for
-    embeddings() above, which computes emb; this applies the model's `fc` to it."""
+    embeddings() above, which computes emb; this applies the model's `fc` to it.  closure=True (needs `nodes`): the same
+    numbers from the nodes' k-hop closure alone -- query() below, whose emb holds the rows of `nodes` only."""
+    if closure:
+        if nodes is None:
+            raise ValueError("full_neighbour(closure=True) needs the nodes to answer for")
+        return query(model, feats, nodes, adj=adj, embeddings=embeddings)
     emb = _embeddings(model, feats, adj=adj)
     dev = feats.device
     with torch.no_grad():
@@ -320,3 +352,250 @@ def full_neighbour(model, feats, nodes=None, adj=None, embeddings=False):
 
 
 _embeddings = embeddings          # (full_neighbour's keyword of the same name shadows the function inside it)
+
+
+# --------------------------------------------------------------------------------------------
+# a query set: k-hop closure blocks
+# --------------------------------------------------------------------------------------------
+class Block(object):
+    """Block l of a closure: destinations S_l (n_dst rows), sources S_{l-1} (n_src rows, S_l as a prefix).  rowptr
+    int64 [n_dst + 1]; col int32: the destinations' stored rows, whole, in stored order, as local indices into the
+    source set; edge_cdf: the rows' segments of a weighted adjacency's table, verbatim; dummy: the local index of
+    global row 0.  Quacks like an adjacency for plan() and segment_reduce() (n_rows = n_dst); err_flag is the
+    adjacency's own."""
+
+    def __init__(self, rowptr, col, n_dst, n_src, dummy, err_flag, edge_cdf=None, buffers=None):
+        self.rowptr, self.col, self.edge_cdf = rowptr, col, edge_cdf
+        self.n_rows = self.n_dst = int(n_dst)
+        self.n_src, self.dummy = int(n_src), int(dummy)
+        self.err_flag = err_flag
+        # (device blocks: the allocations col / edge_cdf are views of, at least one element each -- a block without
+        #  edges, every destination of degree 0, still hands the kernels a pointer)
+        self._buffers = buffers if buffers is not None else (col, edge_cdf)
+
+    def col_ptr(self):
+        return ops._ptr(self._buffers[0])
+
+    def cdf_ptr(self):
+        return ops._ptr(self._buffers[1])
+
+    @property
+    def device(self):
+        return self.rowptr.device
+
+
+class Closure(object):
+    """closure()'s result for depth L: sets[l] = the global ids of S_l (int64; l = 0 .. L, every S_l a prefix of
+    S_0), blocks[l] = Block l for l = 1 .. L (blocks[0] is None), index = the local index in S_L of every query, in the
+    caller's order (int64; duplicates repeat)."""
+
+    def __init__(self, sets, blocks, index):
+        self.sets, self.blocks, self.index = sets, blocks, index
+        self.depth = len(sets) - 1
+
+    def sizes(self):
+        return [int(s.shape[0]) for s in self.sets]
+
+
+def scan_span():
+    """Items per workgroup of the closure kernels' scans (bitmap words, set members, queries): 32 x this many rows."""
+    return int(nat.lib().gsage_closure_span())
+
+
+def _closure_state(adj, n, dev):
+    """The local map (int32 [n_rows], -1 = absent) and the bitmap of the closure kernels, cached on the adjacency the
+    way the plan is; both are back at rest when closure() returns."""
+    st = getattr(adj, "_closure_state", None)
+    if st is None:
+        span = scan_span()
+        n_words = (n + 31) // 32
+        st = {"local": torch.full((n,), -1, dtype=torch.int32, device=dev),
+              "bitmap": torch.zeros(n_words, dtype=torch.int32, device=dev), "span": span,
+              "sums_words": torch.empty((n_words + span - 1) // span + 1, dtype=torch.int64, device=dev),
+              "counts": torch.zeros(3, dtype=torch.int64, device=dev)}
+        adj._closure_state = st
+    return st
+
+
+def _closure_device(adj, nodes, depth):
+    rowptr, col, n = _csr(adj)
+    cdf = adj.edge_cdf if _weighted(adj) else None
+    dev = rowptr.device
+    st = _closure_state(adj, n, dev)
+    L, span = nat.lib(), st["span"]
+    local, bitmap, counts = ops._ptr(st["local"]), ops._ptr(st["bitmap"]), st["counts"]
+    err, stream = ops._ptr(adj.err_flag), ops._stream()
+    q = nodes.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+    nq = int(q.shape[0])
+
+    def i64(k):
+        return torch.empty(k, dtype=torch.int64, device=dev)
+    try:
+        sums_q = i64(nq // span + 2)
+        nat.check(L.gsage_closure_seed_count(ops._ptr(q), nq, n, local, ops._ptr(sums_q), ops._ptr(counts), err, stream),
+                  "closure_seed_count")
+        n_set = int(counts.tolist()[0])                # (the seed level's one readback)
+        S, index = i64(n_set), i64(nq)
+        nat.check(L.gsage_closure_seed_write(ops._ptr(q), nq, n, local, ops._ptr(sums_q), ops._ptr(S), n_set,
+                                             ops._ptr(index), stream), "closure_seed_write")
+        if n_set == 0:
+            adj.err_flag.zero_()
+            raise IndexError("closure: no query id lies inside the adjacency")
+        sizes, blocks, lo = [n_set], [None] * (depth + 1), 0
+        for l in range(depth, 0, -1):
+            hi = int(S.shape[0])
+            sums_rows = i64(hi // span + 2)
+            nat.check(L.gsage_closure_expand_count(ops._ptr(rowptr), ops._ptr(col), n, ops._ptr(S), lo, hi, local, bitmap,
+                                                   ops._ptr(st["sums_words"]), ops._ptr(sums_rows), ops._ptr(counts),
+                                                   err, stream), "closure_expand_count")
+            n_new, nnz, dummy = (int(v) for v in counts.tolist())          # (the hop's one readback: 24 bytes)
+            grown = i64(hi + n_new)
+            grown[:hi] = S
+            brow = i64(hi + 1)
+            colbuf = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+            cdfbuf = i64(max(nnz, 1)) if cdf is not None else None
+            nat.check(L.gsage_closure_expand_write(ops._ptr(rowptr), ops._ptr(col), ops._ptr(cdf), n, ops._ptr(grown), hi,
+                                                   local, bitmap, ops._ptr(st["sums_words"]), ops._ptr(sums_rows),
+                                                   ops._ptr(brow), ops._ptr(colbuf), ops._ptr(cdfbuf), err, stream),
+                      "closure_expand_write")
+            blocks[l] = Block(brow, colbuf[:nnz], hi, hi + n_new, dummy, adj.err_flag,
+                              None if cdfbuf is None else cdfbuf[:nnz], buffers=(colbuf, cdfbuf))
+            S, lo = grown, hi
+            sizes.append(hi + n_new)
+        nat.check(L.gsage_closure_restore(ops._ptr(S), int(S.shape[0]), local, stream), "closure_restore")
+    except BaseException:
+        adj._closure_state = None          # (left mid-way: the next call starts from a fresh map and bitmap)
+        raise
+    sizes.reverse()
+    return Closure([S[:k] for k in sizes], blocks, index)
+
+
+def _closure_host(adj, nodes, depth):
+    """closure() for CPU tensors: the same definition in numpy.  An id outside the graph raises on the spot."""
+    rowptr, col, n = _csr(adj)
+    rp, cl = rowptr.numpy(), col.numpy()
+    cdf = adj.edge_cdf.numpy() if _weighted(adj) else None
+    q = np.asarray(nodes.cpu().numpy() if torch.is_tensor(nodes) else nodes, dtype=np.int64).reshape(-1)
+    if q.size and (q.min() < 0 or q.max() >= n):
+        raise IndexError("closure: query id out of range of the adjacency")
+    if cl.size and (cl.min() < 0 or cl.max() >= n):
+        raise IndexError("closure: the adjacency holds ids outside [0, n_rows)")
+    _, first = np.unique(q, return_index=True)
+    S = q[np.sort(first)]
+    local = np.full(n, -1, dtype=np.int64)
+    local[S] = np.arange(S.size)
+    index = local[q]
+    sizes, blocks, lo = [S.size], [None] * (depth + 1), 0
+    for l in range(depth, 0, -1):
+        hi = S.size
+        deg = rp[S + 1] - rp[S]
+        brow = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+        edge = np.repeat(rp[S] - brow[:-1], deg) + np.arange(int(brow[-1]))    # the stored edges of S, row by row
+        nb = cl[edge]
+        cand = np.unique(np.concatenate([nb[brow[lo]:], [0]]))                # (older members' rows are inside S already)
+        cand = cand[local[cand] < 0]
+        local[cand] = hi + np.arange(cand.size)
+        S = np.concatenate([S, cand])
+        blocks[l] = Block(torch.from_numpy(brow), torch.from_numpy(local[nb].astype(np.int32)), hi, S.size, local[0],
+                          adj.err_flag, None if cdf is None else torch.from_numpy(cdf[edge]))
+        sizes.append(S.size)
+        lo = hi
+    sizes.reverse()
+    S = torch.from_numpy(S)
+    return Closure([S[:k] for k in sizes], blocks, torch.from_numpy(index))
+
+
+def closure(adj, nodes, depth):
+    """The k-hop closure of `nodes` over `adj` (a store.DeviceCSR / store.DenseAdj) for `depth` layers -> Closure.
+    S_depth = the nodes, duplicates removed, in order of first appearance; S_{l-1} = S_l, then the nodes of N(S_l) and
+    the dummy 0 not yet present, in ascending id; block l = the stored rows of S_l relabelled into S_{l-1}.  A CUDA
+    adjacency runs csrc/gsage_block.hip (six launches for the seed level, seven per hop plus torch's copy of the set's
+    prefix, one to restore the state, and one readback per level -- whatever the sizes; an id outside
+    the graph raises the adjacency's err_flag -- adj.check() -- and is left out), a CPU one the same definition in numpy."""
+    depth = int(depth)
+    if depth < 1:
+        raise ValueError("closure: depth must be at least 1, not %d" % depth)
+    nodes = torch.as_tensor(nodes)
+    if nodes.dtype.is_floating_point or nodes.dtype == torch.bool:
+        raise ValueError("closure: node ids must be integers, not %s" % nodes.dtype)
+    if nodes.numel() == 0:
+        raise ValueError("closure: no nodes to answer for")
+    if _csr(adj)[0].is_cuda:
+        return _closure_device(adj, nodes, depth)
+    return _closure_host(adj, nodes, depth)
+
+
+def _gathered_rows(feats, ids, n):
+    """The feature rows of `ids` (the closure's S_0) through the row gather: level 0 of a query.  An FP8 store is decoded
+    for these rows only."""
+    dev = feats.device
+    M = int(ids.shape[0])
+    rows = int(feats.data.shape[0]) if isinstance(feats, FeatureStore) else int(feats.shape[0])
+    if rows < n:
+        raise ValueError("full-neighbour inference: %d feature rows for an adjacency of %d rows" % (rows, n))
+    if dev.type != "cuda":
+        if isinstance(feats, FeatureStore):
+            return ops._store_gather(feats, feats.dim, ids, M, 1, torch.float32)
+        return feats[ids].float()
+    if isinstance(feats, FeatureStore):
+        dt = ops.torch_dtype() if feats.is_fp8 else feats.dtype
+        ld = _round_up(feats.dim, 64 if dt == torch.bfloat16 else 32)
+        return ops.mark_zero_padded(ops._store_gather(feats, feats.dim, ids, M, 1, dt, ld)[:, :feats.dim])
+    if feats.dtype not in (torch.float32, torch.bfloat16) or feats.dim() != 2:
+        return feats[ids]
+    table = feats if feats.stride(1) == 1 else feats.contiguous()
+    return ops._gather_mean_raw(table, int(table.shape[1]), ids, M, 1, table.dtype)
+
+
+def _query(model, feats, nodes, adj, cl=None):
+    """(F.normalize(H^L) of the distinct nodes, their Closure -- `cl` when the caller built it already --, the adjacency)"""
+    check_supported(model)
+    dev = feats.device
+    if adj is None:
+        adj = model.val_sampler.csr(dev)
+    if _weighted(adj):
+        check_supported(model, adj)
+    layers = list(model.agg_layers.children())
+    with torch.no_grad():
+        settle = getattr(model, "_settle_rows", None)
+        if settle is not None:
+            settle()
+        if cl is None:
+            cl = closure(adj, torch.as_tensor(nodes).to(dev), len(layers))
+        elif cl.depth != len(layers) or int(cl.index.shape[0]) != int(torch.as_tensor(nodes).numel()):
+            raise ValueError("query: the closure given was not built for these nodes and this model's depth")
+        X = _gathered_rows(feats, cl.sets[0], int(adj.n_rows))
+        if dev.type == "cuda":
+            H = ops.linear(X, model.prep.fc.weight) if isinstance(model.prep, LinearPrep) else X
+            for l, layer in enumerate(layers, 1):
+                H = _layer_device(layer, H, cl.blocks[l])
+        else:
+            H = F.linear(X, model.prep.fc.weight) if isinstance(model.prep, LinearPrep) else X
+            for l, layer in enumerate(layers, 1):
+                H = _layer_host(layer, H, _edges(cl.blocks[l]))
+        return F.normalize(H.float(), dim=1), cl, adj
+
+
+def query_embeddings(model, feats, nodes, adj=None):
+    """F.normalize(H^L) of `nodes`, [len(nodes), width], in the caller's order (duplicates repeat), computed from the
+    nodes' k-hop closure alone -- the rows embeddings() would give for them.  Arguments as for embeddings()."""
+    emb, cl, adj = _query(model, feats, nodes, adj)
+    adj.check()
+    return emb[cl.index]
+
+
+def query(model, feats, nodes, adj=None, embeddings=False, closure=None):
+    """Logits of `model` for `nodes` by full-neighbourhood inference over their k-hop closure (closure() above): what
+    full_neighbour(model, feats, nodes=nodes) returns, at a cost that follows the closure instead of the graph.  Results
+    come back in the caller's order, duplicates repeated; embeddings=True: (logits, F.normalize(H^L) of `nodes`).
+    Arguments and refusals as for embeddings(); a node id outside the adjacency is an IndexError.  closure: the Closure
+    of `nodes` over `adj` at the model's depth, when the caller has built it already (several models, one query set)."""
+    emb, cl, adj = _query(model, feats, nodes, adj, cl=closure)
+    with torch.no_grad():
+        if feats.device.type == "cuda":
+            logits = ops.linear(emb, model.fc.weight, model.fc.bias, compute_dtype="fp32")
+        else:
+            logits = model.fc(emb)
+    adj.check()
+    logits = logits[cl.index]
+    return (logits, emb[cl.index]) if embeddings else logits

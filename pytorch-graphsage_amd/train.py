@@ -33,6 +33,11 @@ Layer-wise full-neighbourhood inference (infer.py, opt-in; the default output is
                           every neighbour of every node, no sampling) instead of the sampled forward
   --save-embeddings PATH  after training, F.normalize(H^L) of every row of the adjacency, in node-id order, as one
                           .npy (rank 0)
+  --eval-closure          with --full-neighbour-eval: each fold is answered from its nodes' k-hop closure alone
+                          (infer.query: the same numbers; the cost follows the closure of the fold, about 1 % of the
+                          nodes, instead of the graph)
+  --embed-nodes IDS.npy   with --save-embeddings: only the rows of the node ids in IDS.npy, in that order (duplicates
+                          repeat), computed from their closure (infer.query_embeddings)
 
 --unsupervised (with --walk-len, --n-negatives, --neg-weight): train the encoder without labels (models.GSUnsupervised:
 random-walk positives, degree^0.75 negatives, skip-gram loss on the HIP head).  Targets are ignored; every batch
@@ -111,19 +116,23 @@ def evaluate(model, problem, mode='val'):
     return problem.metric_fn(np.vstack([to_numpy(a) for a in acts]), np.vstack([to_numpy(p) for p in preds]))
 
 
-def full_neighbour_evaluate(model, problem, mode='val'):
+def full_neighbour_evaluate(model, problem, mode='val', closure=False):
     """evaluate() by layer-wise full-neighbourhood inference (infer.full_neighbour) of the fold's nodes; every rank
-    computes the whole fold.  No random draw is consumed."""
+    computes the whole fold.  No random draw is consumed.  closure: over the fold's k-hop closure (--eval-closure)."""
     assert mode in ['test', 'val']
     nodes = problem.nodes[mode]
     _, acts = problem._batch(nodes, problem.targets[nodes])
     dev = problem.feats.device
-    preds = gs.full_neighbour(model, problem.feats, nodes=torch.from_numpy(nodes).to(dev))
+    preds = gs.full_neighbour(model, problem.feats, nodes=torch.from_numpy(nodes).to(dev), closure=closure)
     return batch_metric(problem.task, acts.reshape(acts.shape[0], -1), preds)
 
 
-def save_embeddings(model, problem, path):
-    """F.normalize(H^L) of every row, node-id order, one .npy."""
+def save_embeddings(model, problem, path, nodes=None):
+    """F.normalize(H^L) of every row, node-id order, one .npy; nodes (--embed-nodes): of these rows only, in their order."""
+    if nodes is not None:
+        ids = torch.from_numpy(np.asarray(np.load(nodes), dtype=np.int64).reshape(-1)).to(problem.feats.device)
+        np.save(path, gs.infer.query_embeddings(model, problem.feats, ids).cpu().numpy())
+        return
     np.save(path, gs.embeddings(model, problem.feats).cpu().numpy())
 
 
@@ -221,6 +230,8 @@ def parse_args(argv=None):
     parser.add_argument('--feature-dtype', type=str, default='native', choices=['native', 'fp8'])
     parser.add_argument('--full-neighbour-eval', action="store_true")
     parser.add_argument('--save-embeddings', type=str, default=None)
+    parser.add_argument('--eval-closure', action="store_true")
+    parser.add_argument('--embed-nodes', type=str, default=None)
     parser.add_argument('--unsupervised', action="store_true")
     parser.add_argument('--walk-len', type=int, default=5)
     parser.add_argument('--n-negatives', type=int, default=20)
@@ -266,6 +277,10 @@ def build_model(args, problem):
 def main(argv=None, problem=None):
     """problem: a NodeProblem already in memory (NodeProblem.from_arrays) instead of --problem-path's file."""
     args = parse_args(argv)
+    if args.eval_closure and not args.full_neighbour_eval:
+        raise SystemExit('gsage: --eval-closure goes with --full-neighbour-eval')
+    if args.embed_nodes and not args.save_embeddings:
+        raise SystemExit('gsage: --embed-nodes goes with --save-embeddings')
     set_seeds(args.seed)
     gs.ops.set_compute_dtype(args.precision)
     gs.nn_modules.SparseUniformNeighborSampler.rng_default = args.rng
@@ -314,7 +329,8 @@ def main(argv=None, problem=None):
             gs.infer.check_supported(model, model.val_sampler.csr('cpu') if weighted else None)
         except ValueError as e:
             raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings: %s' % e)
-    evaluate_fn = (lambda mode: full_neighbour_evaluate(model, problem, mode=mode)) if args.full_neighbour_eval else \
+    evaluate_fn = (lambda mode: full_neighbour_evaluate(model, problem, mode=mode, closure=args.eval_closure)) \
+        if args.full_neighbour_eval else \
         (lambda mode: evaluate(model, problem, mode=mode))
 
     set_seeds(args.seed ** 2)                          # train.py:133
@@ -353,7 +369,7 @@ def main(argv=None, problem=None):
         if args.show_test:
             print(dumps({"test_f1": evaluate_fn('test')}))
         if args.save_embeddings:
-            save_embeddings(model, problem, args.save_embeddings)
+            save_embeddings(model, problem, args.save_embeddings, args.embed_nodes)
     if ddp is not None:
         ddp.close()
 
@@ -398,7 +414,7 @@ def train_unsupervised(args, problem, model):
         print(dumps({"test": evaluate_unsupervised(model, problem, 'test')}))
     sys.stdout.flush()
     if args.save_embeddings:
-        save_embeddings(model, problem, args.save_embeddings)
+        save_embeddings(model, problem, args.save_embeddings, args.embed_nodes)
 
 
 def choose_engine(args, problem, model, ddp):
@@ -499,7 +515,8 @@ def train_fused(args, problem, model, ddp, start_time, cls):
     val_metric = train_metric = None
     epoch = 0
     if args.full_neighbour_eval:
-        fold_eval = lambda mode='val': full_neighbour_evaluate(model, problem, mode=mode)      # noqa: E731
+        fold_eval = lambda mode='val': full_neighbour_evaluate(model, problem, mode=mode,      # noqa: E731
+                                                               closure=args.eval_closure)
     elif os.environ.get("GSAGE_FUSED_EVAL", "1") == "1":
         fold_eval = FusedEvaluator(cls, model, problem).prepare('val')
     else:
@@ -586,7 +603,7 @@ def train_fused(args, problem, model, ddp, start_time, cls):
         if args.show_test:
             print(dumps({"test_f1": test_metric}))
         if args.save_embeddings:
-            save_embeddings(model, problem, args.save_embeddings)
+            save_embeddings(model, problem, args.save_embeddings, args.embed_nodes)
     if ddp is not None:
         ddp.close()
     return step
