@@ -1171,6 +1171,40 @@ int gsage_segment_reduce_block(int mode, const void *table, int dtype, int64_t l
                                int32_t slice_len, float *partials, int64_t ldp, void *out, int out_dtype,
                                int64_t out_ld, int act, int32_t *err_flag, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Retrieval over embeddings (csrc/gsage_retrieve.hip): the k nearest rows of a table by inner product
+ * (ops.topk_ip / infer.nearest).  Additive; the ABI version is unchanged.  No reference counterpart.
+ *
+ * Given a table E [N, D], queries Qm [Q, D] and k, the score of row j for query q is
+ *     s(q, j) = sum_d Qm[q, d] * E[j, d]
+ * over every ALLOWED row j, and the result is the k best under the TOTAL ORDER (score descending, row id
+ * ascending), best first: out_ids int64 [Q, k], out_scores fp32 [Q, k].
+ *     exclude = 0 (none)        every row is allowed
+ *     exclude = 1 (self)        every row except query_ids[q]
+ *     exclude = 2 (neighbours)  every row except query_ids[q] and the columns stored in row query_ids[q] of the
+ *                               CSR (rowptr int64 [N + 1], col int32; columns in any order, duplicates allowed)
+ * Fewer than k allowed rows: the tail is id -1, score -inf.  A NaN score is never selected.
+ * Compute mode = the operands' dtype, the same for both: GSAGE_BF16 operands are multiplied by
+ * mfma_f32_32x32x16_bf16 (fp32 accumulate; the caller rounds fp32 data to bf16 once), GSAGE_F32 operands by the
+ * exact mfma_f32_32x32x2f32.  A score is one accumulator chain over d in an order that does not depend on where the
+ * row falls in the grid, and the order above is total, so the result is bit-identical for every split count and run.
+ *
+ * Limits (GSAGE_EINVAL, the message names the argument): 1 <= k <= 128; 1 <= D <= 1024; ldt, ldq >= D (elements;
+ * nothing past a row's D columns is read, a D that is no multiple of the MFMA's K step is zero-filled in LDS);
+ * 1 <= N < 2^31; Q >= 1; 0 <= splits <= 1024 (0 = chosen by the library); exclude != 0 needs query_ids,
+ * exclude = 2 needs rowptr and col.  No Q x N buffer exists; the only scratch is
+ *     workspace  [Q, splits, k] pairs of (score, id), 8 bytes each, 8-byte aligned.
+ * Two launches (scan, merge); recordable in a command list.
+ *
+ * gsage_topk_ip_workspace (HOST arithmetic, no GPU): the workspace's bytes for (Q, k, splits), -1 for arguments
+ * outside the limits; *splits_used (may be NULL) = splits, or for splits = 0 the count the library chooses for (Q, N).
+ * ---------------------------------------------------------------------------------------- */
+int64_t gsage_topk_ip_workspace(int64_t Q, int64_t N, int64_t k, int64_t splits, int64_t *splits_used);
+int gsage_topk_ip(const void *table, int table_dtype, int64_t ldt, int64_t N, const void *queries, int query_dtype,
+                  int64_t ldq, int64_t Q, int64_t D, const int64_t *query_ids, const int64_t *rowptr,
+                  const int32_t *col, int exclude, int32_t k, int32_t splits, void *workspace, int64_t workspace_bytes,
+                  int64_t *out_ids, float *out_scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

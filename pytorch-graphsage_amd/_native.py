@@ -194,6 +194,9 @@ SIGNATURES = {
     "gsage_closure_restore": (_int, [_vp, _i64, _vp, _vp]),
     "gsage_segment_reduce_block": (_int, [_int, _vp, _int, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp,
                                           _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _int, _i64, _int, _vp, _vp]),
+    "gsage_topk_ip_workspace": (_i64, [_i64, _i64, _i64, _i64, ctypes.POINTER(_i64)]),
+    "gsage_topk_ip": (_int, [_vp, _int, _i64, _i64, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _i32, _i32, _vp,
+                             _i64, _vp, _vp, _vp]),
 }
 
 

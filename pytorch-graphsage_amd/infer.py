@@ -38,7 +38,7 @@ from . import _native as nat
 from . import ops
 from .nn_modules import (AttentionAggregator, IdentityPrep, LinearPrep, LSTMAggregator, MeanAggregator,
                          NodeEmbeddingPrep, PoolAggregator, concat_combine, _split_activation)
-from .store import DenseAdj, FeatureStore, _round_up
+from .store import DenseAdj, DeviceCSR, FeatureStore, WeightedAdj, _round_up
 
 SLICE_LEN = 256          # rows of higher degree are cut into slices of this many edges (one team each)
 
@@ -599,3 +599,45 @@ def query(model, feats, nodes, adj=None, embeddings=False, closure=None):
     adj.check()
     logits = logits[cl.index]
     return (logits, emb[cl.index]) if embeddings else logits
+
+
+# --------------------------------------------------------------------------------------------
+# retrieval over the exported embeddings
+# --------------------------------------------------------------------------------------------
+def nearest(emb, nodes=None, k=10, exclude="self", adj=None):
+    """The k rows of `emb` nearest to the rows of `nodes` by inner product -- on the unit rows embeddings() returns,
+    the cosine, whose order is the Euclidean one: -> (ids int64 [Q, k], scores fp32 [Q, k]), best first under the total
+    order (score descending, row id ascending); ops.topk_ip.
+
+    emb: what embeddings() / query_embeddings() return, or any [N, D] float tensor.  nodes: the node ids whose rows are
+    the queries, answered in the caller's order, duplicates repeatedly; None: every row (the k-NN graph).  exclude:
+    "none", "self" (a node is not its own neighbour) or "neighbours" (neither itself nor a node it already has an edge
+    to in `adj`, a store.DeviceCSR; a WeightedAdj is read as its CSR): link recommendation.  Fewer than k allowed rows:
+    id -1, score -inf.  A node id outside the table is an IndexError."""
+    if not torch.is_tensor(emb) or emb.dim() != 2 or not emb.is_floating_point():
+        raise ValueError("nearest: emb must be a [N, D] float tensor")
+    dev = emb.device
+    N = int(emb.shape[0])
+    if nodes is None:
+        ids = torch.arange(N, dtype=torch.int64, device=dev)
+        queries = emb
+    else:
+        ids = torch.as_tensor(nodes)
+        if ids.is_floating_point() or ids.dtype == torch.bool:
+            raise ValueError("nearest: node ids must be integers, not %s" % ids.dtype)
+        ids = ids.to(dev).long().view(-1)
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= N):
+            raise IndexError("nearest: node id out of range of the %d embedding rows" % N)
+        queries = emb[ids]
+    csr = None
+    if exclude == "neighbours":
+        if adj is None:
+            raise ValueError("nearest: exclude='neighbours' needs adj (a store.DeviceCSR)")
+        if isinstance(adj, DenseAdj):
+            raise ValueError("nearest: exclude='neighbours' reads a CSR; a DenseAdj holds samples, not the edges")
+        if isinstance(adj, WeightedAdj):
+            adj = DeviceCSR.from_scipy(adj.adj, dev)
+        if not isinstance(adj, DeviceCSR):
+            raise ValueError("nearest: adj must be a store.DeviceCSR or a store.WeightedAdj")
+        csr = adj
+    return ops.topk_ip(emb, queries, k, query_ids=ids, csr=csr, exclude=exclude)

@@ -1344,3 +1344,114 @@ def skipgram_loss(E, B, Q, pair_w, neg_weight=1.0):
     if E.is_cuda:
         return _SkipgramLoss.apply(E.float(), int(B), int(Q), pair_w, float(neg_weight))
     return _skipgram_host(E, int(B), int(Q), pair_w, float(neg_weight))[0]
+
+
+# =============================================================================================
+# Retrieval over embeddings: top-k rows by inner product (csrc/gsage_retrieve.hip)
+# =============================================================================================
+TOPK_EXCLUDE = {"none": 0, "self": 1, "neighbours": 2}
+TOPK_K_MAX, TOPK_D_MAX = 128, 1024
+
+
+def topk_ip_workspace(Q, N, k, splits=0):
+    """(bytes of gsage_topk_ip's workspace, the split count used) for Q queries over N rows -- host arithmetic."""
+    used = ctypes.c_int64(0)
+    nbytes = int(nat.lib().gsage_topk_ip_workspace(int(Q), int(N), int(k), int(splits), ctypes.byref(used)))
+    if nbytes < 0:
+        raise ValueError("topk_ip: Q = %d, N = %d, k = %d, splits = %d are outside the kernel's limits "
+                         "(1 <= k <= %d, N < 2^31, 0 <= splits <= 1024)" % (Q, N, k, splits, TOPK_K_MAX))
+    return nbytes, int(used.value)
+
+
+def _topk_ip_host(table, queries, k, query_ids, csr, exclude):
+    """The definition in numpy (host mode): operands rounded as the compute mode sees them, float64 products, a stable
+    sort on (-score, id) over the allowed rows."""
+    dt = torch_dtype()
+    E = table.detach().to(dt).double().numpy()
+    Qm = queries.detach().to(dt).double().numpy()
+    S = (Qm @ E.T).astype(np.float32)
+    Q, N = S.shape
+    ids = np.full((Q, k), -1, dtype=np.int64)
+    scores = np.full((Q, k), -np.inf, dtype=np.float32)
+    qid = None if query_ids is None else query_ids.detach().cpu().numpy().astype(np.int64)
+    if exclude == "neighbours":
+        rowptr, col = csr.rowptr.cpu().numpy(), csr.col.cpu().numpy()
+    for q in range(Q):
+        allowed = ~np.isnan(S[q])
+        if exclude != "none" and 0 <= qid[q] < N:
+            allowed[qid[q]] = False
+            if exclude == "neighbours":
+                nb = col[rowptr[qid[q]]:rowptr[qid[q] + 1]].astype(np.int64)
+                allowed[nb[(nb >= 0) & (nb < N)]] = False
+        cand = np.flatnonzero(allowed)
+        best = cand[np.argsort(-S[q, cand], kind="stable")][:k]
+        ids[q, :best.size] = best
+        scores[q, :best.size] = S[q, best]
+    return torch.from_numpy(ids), torch.from_numpy(scores)
+
+
+def topk_ip(table, queries, k, query_ids=None, csr=None, exclude="none", splits=0, workspace=None, out=None):
+    """The k rows of `table` [N, D] nearest to each row of `queries` [Q, D] by inner product, under the total order
+    (score descending, row id ascending), best first: -> (ids int64 [Q, k], scores fp32 [Q, k]); include/gsage.h,
+    "Retrieval over embeddings".  exclude: "none"; "self" (not row query_ids[q]); "neighbours" (neither that row nor
+    the columns of row query_ids[q] of `csr`, a store.DeviceCSR).  Fewer than k allowed rows: id -1, score -inf.
+    Operands are taken in ops.config.compute_dtype (fp32 data is rounded to bf16 once in the bf16 mode).
+
+    CUDA: gsage_topk_ip (two launches, recordable in a command list when the caller hands in `workspace` -- a uint8
+    tensor of topk_ip_workspace(...) bytes -- and `out` = (ids, scores)); the result does not depend on `splits`
+    (0 = chosen by the library).  CPU: the same definition in numpy."""
+    if exclude not in TOPK_EXCLUDE:
+        raise ValueError("topk_ip: exclude must be one of %s, not %r" % (sorted(TOPK_EXCLUDE), exclude))
+    if table.dim() != 2 or queries.dim() != 2 or int(table.shape[1]) != int(queries.shape[1]):
+        raise ValueError("topk_ip: table [N, D] and queries [Q, D] must share D")
+    if not (table.is_floating_point() and queries.is_floating_point()):
+        raise ValueError("topk_ip: table and queries must be floating point")
+    N, D = int(table.shape[0]), int(table.shape[1])
+    Q, k = int(queries.shape[0]), int(k)
+    if not 1 <= k <= TOPK_K_MAX:
+        raise ValueError("topk_ip: k must be in [1, %d], not %d" % (TOPK_K_MAX, k))
+    if not 1 <= D <= TOPK_D_MAX:
+        raise ValueError("topk_ip: D must be in [1, %d], not %d" % (TOPK_D_MAX, D))
+    if N < 1:
+        raise ValueError("topk_ip: the table has no rows")
+    if exclude != "none":
+        if query_ids is None:
+            raise ValueError("topk_ip: exclude=%r needs query_ids" % exclude)
+        query_ids = torch.as_tensor(query_ids).to(device=table.device, dtype=torch.int64).contiguous().view(-1)
+        if int(query_ids.shape[0]) != Q:
+            raise ValueError("topk_ip: %d query_ids for %d queries" % (int(query_ids.shape[0]), Q))
+    else:
+        query_ids = None
+    if exclude == "neighbours":
+        if csr is None:
+            raise ValueError("topk_ip: exclude='neighbours' needs csr")
+        if int(csr.n_rows) < N or csr.rowptr.device != table.device:
+            raise ValueError("topk_ip: csr must live on the table's device and have a row for each of its %d rows" % N)
+    else:
+        csr = None
+    if not table.is_cuda:
+        if Q == 0:
+            return torch.empty(0, k, dtype=torch.int64), torch.empty(0, k, dtype=torch.float32)
+        return _topk_ip_host(table, queries, k, query_ids, csr, exclude)
+    dev = table.device
+    if out is None:
+        out = (torch.empty(Q, k, dtype=torch.int64, device=dev), torch.empty(Q, k, dtype=torch.float32, device=dev))
+    ids, scores = out
+    assert ids.is_contiguous() and scores.is_contiguous() and tuple(ids.shape) == (Q, k) == tuple(scores.shape)
+    if Q == 0:
+        return ids, scores
+    cdt = torch_dtype()
+
+    def operand(t):
+        t = t.detach()
+        return t if t.dtype == cdt and t.stride(1) == 1 and t.stride(0) >= D else t.to(cdt).contiguous()
+    E, Qm = operand(table), operand(queries)
+    nbytes, _ = topk_ip_workspace(Q, N, k, splits)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nat.check(nat.lib().gsage_topk_ip(_ptr(E), _code(cdt), E.stride(0), N, _ptr(Qm), _code(cdt), Qm.stride(0), Q, D,
+                                      _ptr(query_ids), _ptr(csr.rowptr) if csr is not None else None,
+                                      _ptr(csr.col) if csr is not None else None, TOPK_EXCLUDE[exclude], k, int(splits),
+                                      _ptr(workspace), int(workspace.numel()) * workspace.element_size(), _ptr(ids),
+                                      _ptr(scores), _stream()), "topk_ip")
+    return ids, scores

@@ -39,6 +39,16 @@ Layer-wise full-neighbourhood inference (infer.py, opt-in; the default output is
   --embed-nodes IDS.npy   with --save-embeddings: only the rows of the node ids in IDS.npy, in that order (duplicates
                           repeat), computed from their closure (infer.query_embeddings)
 
+Retrieval over the embeddings (infer.nearest, opt-in):
+  --save-neighbours PATH  after training, the k nearest rows (inner product of the unit embeddings = cosine) of every
+                          row of the adjacency, as one .npz with `ids` int64 [rows, k] and `scores` fp32 [rows, k],
+                          best first, ties by ascending id (rank 0).  With --save-embeddings (and no --embed-nodes)
+                          the embeddings are computed once for both files.
+  --neighbours-k K        how many (default 10, at most 128)
+  --neighbour-nodes IDS.npy   with --save-neighbours: only for the node ids in IDS.npy, in that order
+  --neighbours-exclude none|self|neighbours   rows a node is never answered with (default self; neighbours: nor a
+                          node it already has an edge to in the evaluation adjacency -- link recommendation)
+
 --unsupervised (with --walk-len, --n-negatives, --neg-weight): train the encoder without labels (models.GSUnsupervised:
 random-walk positives, degree^0.75 negatives, skip-gram loss on the HIP head).  Targets are ignored; every batch
 prints one JSON line with its loss, every epoch the validation fold's loss and mean reciprocal rank ("mrr").  The
@@ -134,6 +144,30 @@ def save_embeddings(model, problem, path, nodes=None):
         np.save(path, gs.infer.query_embeddings(model, problem.feats, ids).cpu().numpy())
         return
     np.save(path, gs.embeddings(model, problem.feats).cpu().numpy())
+
+
+def export(model, problem, args):
+    """--save-embeddings and --save-neighbours after training: one embedding pass serves both files."""
+    emb = None
+    if args.save_embeddings:
+        if args.embed_nodes:
+            save_embeddings(model, problem, args.save_embeddings, args.embed_nodes)
+        else:
+            emb = gs.embeddings(model, problem.feats)
+            np.save(args.save_embeddings, emb.cpu().numpy())
+    if args.save_neighbours:
+        if emb is None:
+            emb = gs.embeddings(model, problem.feats)
+        nodes = None
+        if args.neighbour_nodes:
+            nodes = torch.from_numpy(np.asarray(np.load(args.neighbour_nodes), dtype=np.int64).reshape(-1))
+        adj = model.val_sampler.csr(emb.device) if args.neighbours_exclude == 'neighbours' else None
+        try:
+            ids, scores = gs.nearest(emb, nodes, k=args.neighbours_k, exclude=args.neighbours_exclude, adj=adj)
+        except ValueError as e:
+            raise SystemExit('gsage: --save-neighbours: %s' % e)
+        with open(args.save_neighbours, 'wb') as f:
+            np.savez(f, ids=ids.cpu().numpy(), scores=scores.cpu().numpy())
 
 
 class FusedEvaluator(object):
@@ -232,6 +266,10 @@ def parse_args(argv=None):
     parser.add_argument('--save-embeddings', type=str, default=None)
     parser.add_argument('--eval-closure', action="store_true")
     parser.add_argument('--embed-nodes', type=str, default=None)
+    parser.add_argument('--save-neighbours', type=str, default=None)
+    parser.add_argument('--neighbours-k', type=int, default=10)
+    parser.add_argument('--neighbour-nodes', type=str, default=None)
+    parser.add_argument('--neighbours-exclude', type=str, default='self', choices=['none', 'self', 'neighbours'])
     parser.add_argument('--unsupervised', action="store_true")
     parser.add_argument('--walk-len', type=int, default=5)
     parser.add_argument('--n-negatives', type=int, default=20)
@@ -281,6 +319,10 @@ def main(argv=None, problem=None):
         raise SystemExit('gsage: --eval-closure goes with --full-neighbour-eval')
     if args.embed_nodes and not args.save_embeddings:
         raise SystemExit('gsage: --embed-nodes goes with --save-embeddings')
+    if args.neighbour_nodes and not args.save_neighbours:
+        raise SystemExit('gsage: --neighbour-nodes goes with --save-neighbours')
+    if args.save_neighbours and not 1 <= args.neighbours_k <= gs.ops.TOPK_K_MAX:
+        raise SystemExit('gsage: --neighbours-k must be in 1..%d' % gs.ops.TOPK_K_MAX)
     set_seeds(args.seed)
     gs.ops.set_compute_dtype(args.precision)
     gs.nn_modules.SparseUniformNeighborSampler.rng_default = args.rng
@@ -317,18 +359,18 @@ def main(argv=None, problem=None):
     if args.unsupervised:
         if args.full_neighbour_eval:
             raise SystemExit('gsage: --unsupervised: --full-neighbour-eval scores logits; there are none')
-        if args.save_embeddings:
+        if args.save_embeddings or args.save_neighbours:
             try:
                 gs.infer.check_supported(model)
             except ValueError as e:
-                raise SystemExit('gsage: --save-embeddings: %s' % e)
+                raise SystemExit('gsage: --save-embeddings / --save-neighbours: %s' % e)
         set_seeds(args.seed ** 2)
         return train_unsupervised(args, problem, model)
-    if args.full_neighbour_eval or args.save_embeddings:
+    if args.full_neighbour_eval or args.save_embeddings or args.save_neighbours:
         try:
             gs.infer.check_supported(model, model.val_sampler.csr('cpu') if weighted else None)
         except ValueError as e:
-            raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings: %s' % e)
+            raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings / --save-neighbours: %s' % e)
     evaluate_fn = (lambda mode: full_neighbour_evaluate(model, problem, mode=mode, closure=args.eval_closure)) \
         if args.full_neighbour_eval else \
         (lambda mode: evaluate(model, problem, mode=mode))
@@ -368,8 +410,8 @@ def main(argv=None, problem=None):
         sys.stdout.flush()
         if args.show_test:
             print(dumps({"test_f1": evaluate_fn('test')}))
-        if args.save_embeddings:
-            save_embeddings(model, problem, args.save_embeddings, args.embed_nodes)
+        if args.save_embeddings or args.save_neighbours:
+            export(model, problem, args)
     if ddp is not None:
         ddp.close()
 
@@ -413,8 +455,8 @@ def train_unsupervised(args, problem, model):
     if args.show_test:
         print(dumps({"test": evaluate_unsupervised(model, problem, 'test')}))
     sys.stdout.flush()
-    if args.save_embeddings:
-        save_embeddings(model, problem, args.save_embeddings, args.embed_nodes)
+    if args.save_embeddings or args.save_neighbours:
+        export(model, problem, args)
 
 
 def choose_engine(args, problem, model, ddp):
@@ -602,8 +644,8 @@ def train_fused(args, problem, model, ddp, start_time, cls):
         sys.stdout.flush()
         if args.show_test:
             print(dumps({"test_f1": test_metric}))
-        if args.save_embeddings:
-            save_embeddings(model, problem, args.save_embeddings, args.embed_nodes)
+        if args.save_embeddings or args.save_neighbours:
+            export(model, problem, args)
     if ddp is not None:
         ddp.close()
     return step
