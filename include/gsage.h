@@ -1205,6 +1205,50 @@ int gsage_topk_ip(const void *table, int table_dtype, int64_t ldt, int64_t N, co
                   const int32_t *col, int exclude, int32_t k, int32_t splits, void *workspace, int64_t workspace_bytes,
                   int64_t *out_ids, float *out_scores, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exact link ranking over embeddings (csrc/gsage_rank.hip): the rank of one target row among ALL rows of a table by
+ * inner product (ops.rank_ip / infer.link_rank).  Additive; the ABI version is unchanged.  No reference counterpart.
+ *
+ * Given a table E [N, D], queries Qm [Q, D], target_ids int64 [Q] and optionally query_ids int64 [Q] and a filter
+ * CSR, with s(q, j) = sum_d Qm[q, d] * E[j, d] as in gsage_topk_ip and t = target_ids[q]:
+ *     rank(q) = 1 + |{ j allowed for q, j != t : (s(q, j), j) beats (s(q, t), t) }|
+ * "beats" is gsage_topk_ip's TOTAL ORDER (score descending, row id ascending); a row whose score is NaN beats nothing.
+ * Outputs: out_rank int64 [Q]; out_score fp32 [Q] = s(q, t).
+ *     exclude = 0 (none)        every row is allowed
+ *     exclude = 1 (self)        every row except query_ids[q]
+ *     exclude = 2 (neighbours)  every row except query_ids[q] and the columns of row query_ids[q] of the CSR: the
+ *                               "filtered" setting -- known edges of the source do not count against the target
+ * In both excluding modes the target itself is never excluded (a held-out edge's target is normally in the full
+ * adjacency, and src == dst is legal): the excluded set is ({query_ids[q]} u cols) \ {t}.
+ * Unranked: a target outside [0, N) gives rank 0 and score -inf; a target whose own score is NaN gives rank 0 and
+ * score NaN.
+ * Filter CSR (rowptr int64 [N + 1], col int32): in THIS entry point every row's columns must be STRICTLY ASCENDING
+ * (sorted, no duplicates -- stricter than gsage_topk_ip, because a subtraction must not count a duplicate twice).  A
+ * row that is read and violates it raises *err_flag (int32 device word, may be NULL; 0 = ok); the ranks of that call
+ * are then not to be used.  The check is an adjacent-column compare where the row is walked anyway.  Columns outside
+ * [0, N) are ignored.
+ *
+ * Compute mode = the operands' dtype, as in gsage_topk_ip, and every score -- the target's and the excluded rows'
+ * included -- is the SAME accumulator chain as there: its bits are a function of the two rows alone, identical in
+ * every launch of both entry points.  Counts are integers, so the result is bit-identical for every split count.
+ *
+ * Limits (GSAGE_EINVAL, the message names the argument; checked on the host before anything touches the GPU):
+ * 1 <= D <= 1024; ldt, ldq >= D (elements; nothing past a row's D columns is read); 1 <= N < 2^31; Q >= 1;
+ * 0 <= splits <= 1024 (0 = chosen by the library, gsage_topk_ip's rule); exclude != 0 needs query_ids, exclude = 2
+ * needs rowptr and col.  The only scratch is
+ *     workspace  [Q, splits] int32 split counts, then [Q] int32 filter counts: 4 * Q * (splits + 1) bytes, 4-byte aligned.
+ * Launches: 2 for exclude = 0 and 1 (scan, finish), 3 for exclude = 2 (scan, filter, finish); recordable in a command
+ * list.
+ *
+ * gsage_rank_ip_workspace (HOST arithmetic, no GPU): the workspace's bytes for (Q, splits), -1 for arguments outside
+ * the limits; *splits_used (may be NULL) = splits, or for splits = 0 the count the library chooses for (Q, N).
+ * ---------------------------------------------------------------------------------------- */
+int64_t gsage_rank_ip_workspace(int64_t Q, int64_t N, int64_t splits, int64_t *splits_used);
+int gsage_rank_ip(const void *table, int table_dtype, int64_t ldt, int64_t N, const void *queries, int query_dtype,
+                  int64_t ldq, int64_t Q, int64_t D, const int64_t *target_ids, const int64_t *query_ids,
+                  const int64_t *rowptr, const int32_t *col, int exclude, int32_t splits, void *workspace,
+                  int64_t workspace_bytes, int64_t *out_rank, float *out_score, int32_t *err_flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,9 @@ SIGNATURES = {
     "gsage_topk_ip_workspace": (_i64, [_i64, _i64, _i64, _i64, ctypes.POINTER(_i64)]),
     "gsage_topk_ip": (_int, [_vp, _int, _i64, _i64, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _int, _i32, _i32, _vp,
                              _i64, _vp, _vp, _vp]),
+    "gsage_rank_ip_workspace": (_i64, [_i64, _i64, _i64, ctypes.POINTER(_i64)]),
+    "gsage_rank_ip": (_int, [_vp, _int, _i64, _i64, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _i32, _vp, _i64,
+                             _vp, _vp, _vp, _vp]),
 }
 
 

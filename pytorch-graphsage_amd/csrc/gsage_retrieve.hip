@@ -28,19 +28,12 @@
 // what they saw under a TOTAL order, and the best k of a union is the best k of the parts' best k.  Hence the
 // result is bit-identical for every split count (tests/test_gpu_retrieve.py).  NaN compares false both ways and
 // never enters a list.
-#include "gsage_common.h"
-#include "gsage_mma_dev.h"
+#include "gsage_retrieve_dev.h"
 
 namespace gsage {
 
-constexpr int RT_QT = 32;                         // queries per workgroup (the MFMA's 32 columns)
 constexpr int RT_K_MAX = 128;
-constexpr int RT_D_MAX = 1024;
-constexpr int RT_SPLITS_MAX = 1024;               // the merge keeps one head byte per split in LDS
 constexpr int RT_SENT = 0x7fffffff;               // id of an empty slot inside the kernels (score -inf)
-constexpr uint32_t RT_NEG_INF = 0xff800000u;
-constexpr size_t RT_LDS_MAX = 160 * 1024;
-enum { RT_EXCLUDE_NONE = 0, RT_EXCLUDE_SELF = 1, RT_EXCLUDE_NEIGHBOURS = 2 };
 
 struct RetrieveParams {
     const void *table;
@@ -55,40 +48,10 @@ struct RetrieveParams {
     int32_t t_vec, q_vec;                         // rows are 16-byte aligned: whole chunks move as one load
 };
 
-// the total order: (score descending, id ascending).  false for a NaN score on either side.
-__device__ __forceinline__ bool rt_beats(float s, int id, float ts, int tid)
-{
-    return s > ts || (s == ts && id < tid);
-}
-
-// 16-byte chunk c of a row of D elements, zero past D; never reads past the row's D columns
-template <typename T>
-__device__ __forceinline__ vec16 rt_load_chunk(const T *row, int c, int D, int vec_ok)
-{
-    constexpr int EPC = 16 / (int)sizeof(T);
-    const int d0 = c * EPC;
-    if (vec_ok && d0 + EPC <= D) return *reinterpret_cast<const vec16 *>(row + d0);
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    if (d0 < D) {
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            if (d0 + e < D) {
-                if (sizeof(T) == 2)
-                    w[e >> 1] |= (uint32_t)((const uint16_t *)row)[d0 + e] << (16 * (e & 1));
-                else
-                    w[e & 3] = ((const uint32_t *)row)[d0 + e];
-            }
-        }
-    }
-    const vec16 v = {w[0], w[1], w[2], w[3]};
-    return v;
-}
-
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_topk_scan(const RetrieveParams p)
 {
-    constexpr int EPC = 16 / (int)sizeof(T);
     extern __shared__ vec16 rt_smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -97,22 +60,13 @@ k_topk_scan(const RetrieveParams p)
     const int h = lane >> 5;
     const int ql = lane & 31;
     const int k = p.k;
-    const int chunks = (p.D + EPC - 1) / EPC;
-    const int nkt = (chunks + CH - 1) / CH;
-    const int nkk = (chunks + 1) / 2;
-    const int nkk_full = p.t_vec ? (p.D / EPC) / 2 : 0;          // k steps whose two chunks are whole vector loads
+    const rt_shape<T> sh(p.D, p.t_vec);
     vec16 *sQ = rt_smem;
-    uint2 *lists = reinterpret_cast<uint2 *>(rt_smem + (size_t)nkt * RT_QT * CH);
+    uint2 *lists = reinterpret_cast<uint2 *>(rt_smem + (size_t)sh.nkt * RT_QT * CH);
     const int64_t q0 = (int64_t)blockIdx.x * RT_QT;
 
     // ---- the query tile, once ---------------------------------------------------------------------
-    for (int i = tid; i < nkt * RT_QT * CH; i += (int)blockDim.x) {
-        const int kt = i >> 8, row = (i >> 3) & 31, ch = i & 7;
-        const int64_t q = q0 + row;
-        vec16 v = {0u, 0u, 0u, 0u};
-        if (q < p.Q) v = rt_load_chunk<T>((const T *)p.queries + q * p.ldq, kt * CH + ch, p.D, p.q_vec);
-        sQ[kt * (RT_QT * CH) + lds_slot(row, ch)] = v;
-    }
+    rt_stage_queries<T>(sQ, p.queries, p.ldq, q0, p.Q, p.D, p.q_vec, sh.nkt);
     // this wave's lists: entry `pos` of query `ql` at my[pos * 32 + ql]
     uint2 *my = lists + (size_t)wave * RT_QT * k;
     for (int i = lane; i < RT_QT * k; i += 64) my[i] = make_uint2(RT_NEG_INF, (uint32_t)RT_SENT);
@@ -142,26 +96,14 @@ k_topk_scan(const RetrieveParams p)
         if (ar >= p.N) ar = p.N - 1;              // a valid address; the row is dropped below
         const T *arow = (const T *)p.table + ar * p.ldt;
         f32x16_t acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        int kk = 0;
-        for (; kk < nkk_full; ++kk) {
-            const vec16 a = *reinterpret_cast<const vec16 *>(arow + (2 * kk + h) * EPC);
-            const vec16 b = sQ[(kk >> 2) * (RT_QT * CH) + lds_slot(ql, (kk & 3) * 2 + h)];
-            mma_chunk<T>::run(a, b, acc);
-        }
-        for (; kk < nkk; ++kk) {
-            const vec16 a = rt_load_chunk<T>(arow, 2 * kk + h, p.D, p.t_vec);
-            const vec16 b = sQ[(kk >> 2) * (RT_QT * CH) + lds_slot(ql, (kk & 3) * 2 + h)];
-            mma_chunk<T>::run(a, b, acc);
-        }
+        rt_tile_scores<T>(arow, sQ, ql, h, p.D, p.t_vec, sh, acc);
 
         // ---- selection: one compare per score ----------------------------------------------------------
         const uint32_t rbase = (uint32_t)row0 + 4u * (uint32_t)h;
         uint32_t mask = 0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const uint32_t id = rbase + (uint32_t)((r & 3) + 8 * (r >> 2));
+            const uint32_t id = rbase + (uint32_t)rt_frag_row(r);
             if (id < n_u && rt_beats(acc[r], (int)id, ts, tidx)) mask |= 1u << r;
         }
         if (!q_ok) mask = 0;
@@ -172,7 +114,7 @@ k_topk_scan(const RetrieveParams p)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         if (!((mask >> r) & 1u)) continue;
-                        const int id = (int)(rbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
+                        const int id = (int)(rbase + (uint32_t)rt_frag_row(r));
                         const float s = acc[r];
                         if (!rt_beats(s, id, ts, tidx)) continue;       // the threshold moved meanwhile
                         bool allowed = true;
@@ -278,21 +220,9 @@ k_topk_merge(const uint2 *ws, int64_t Q, int32_t splits, int32_t k, int64_t *out
     }
 }
 
-static int64_t rt_auto_splits(int64_t Q, int64_t N)
-{
-    // about four workgroups per CU of a 256-CU part, but no split thinner than 16 table tiles (4 per wave)
-    const int64_t qtiles = ceil_div(Q, RT_QT), tiles = ceil_div(N, 32);
-    int64_t s = ceil_div(1024, qtiles);
-    const int64_t cap = tiles / 16 > 1 ? tiles / 16 : 1;
-    if (s > cap) s = cap;
-    if (s > RT_SPLITS_MAX) s = RT_SPLITS_MAX;
-    return s < 1 ? 1 : s;
-}
-
 static size_t rt_scan_lds(int64_t D, int esz, int32_t k, int waves)
 {
-    const int64_t chunks = ceil_div(D * esz, 16);
-    return (size_t)ceil_div(chunks, CH) * RT_QT * CH * 16 + (size_t)waves * RT_QT * k * sizeof(uint2);
+    return rt_query_lds(D, esz) + (size_t)waves * RT_QT * k * sizeof(uint2);
 }
 
 template <typename T>

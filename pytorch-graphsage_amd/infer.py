@@ -641,3 +641,126 @@ def nearest(emb, nodes=None, k=10, exclude="self", adj=None):
             raise ValueError("nearest: adj must be a store.DeviceCSR or a store.WeightedAdj")
         csr = adj
     return ops.topk_ip(emb, queries, k, query_ids=ids, csr=csr, exclude=exclude)
+
+
+# --------------------------------------------------------------------------------------------
+# exact link ranking over the exported embeddings
+# --------------------------------------------------------------------------------------------
+def _as_csr(adj, dev, who):
+    """`adj` as a store.DeviceCSR: a WeightedAdj is read as its CSR, a DenseAdj is refused with nearest()'s sentence."""
+    if isinstance(adj, DenseAdj):
+        raise ValueError("%s: exclude='neighbours' reads a CSR; a DenseAdj holds samples, not the edges" % who)
+    if isinstance(adj, WeightedAdj):
+        got = getattr(adj, "_device_csr", None)
+        if got is None or got.device != torch.device(dev):
+            got = DeviceCSR.from_scipy(adj.adj, dev)
+            adj._device_csr = got
+        adj = got
+    if not isinstance(adj, DeviceCSR):
+        raise ValueError("%s: adj must be a store.DeviceCSR or a store.WeightedAdj" % who)
+    return adj
+
+
+def filter_csr(adj):
+    """The stored edges of `adj` (a store.DeviceCSR, columns in any order, duplicates allowed) as the STRICTLY ASCENDING
+    CSR ops.rank_ip's filter wants: per row the distinct columns inside [0, n_rows), sorted.  Built once by torch ops on
+    the keys row * n_rows + col (sort, unique_consecutive) and cached on the adjacency object the way the closure
+    caches its local map; `.keys` keeps the sorted keys (held_out_edges looks edges up in them)."""
+    got = getattr(adj, "_rank_filter", None)
+    if got is not None:
+        return got
+    n = int(adj.n_rows)
+    rowptr, col = adj.rowptr, adj.col.long()
+    row = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=rowptr.device), rowptr[1:] - rowptr[:-1])
+    ok = (col >= 0) & (col < n)
+    keys = torch.unique_consecutive(torch.sort(row[ok] * n + col[ok]).values)
+    counts = torch.bincount(torch.div(keys, n, rounding_mode="floor"), minlength=n)
+    new_ptr = torch.zeros(n + 1, dtype=torch.int64, device=rowptr.device)
+    torch.cumsum(counts, 0, out=new_ptr[1:])
+    got = DeviceCSR(new_ptr, (keys % n).to(torch.int32), n, adj.max_deg)
+    got.keys = keys
+    adj._rank_filter = got
+    return got
+
+
+def _pair_ids(ids, dev, who, name, N=None):
+    ids = torch.as_tensor(ids)
+    if ids.is_floating_point() or ids.dtype == torch.bool:
+        raise ValueError("%s: %s must be integers, not %s" % (who, name, ids.dtype))
+    ids = ids.to(dev).long().view(-1)
+    if N is not None and ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= N):
+        raise IndexError("%s: %s id out of range of the %d embedding rows" % (who, name, N))
+    return ids
+
+
+def link_rank(emb, src, dst, exclude="neighbours", adj=None):
+    """Where does dst[i] rank among ALL rows of `emb` as a neighbour of src[i]?  -> (ranks int64 [P], scores fp32 [P])
+    for the pairs in the caller's order, duplicates repeated: rank = 1 + the number of allowed rows that beat dst by
+    inner product with emb[src] under the total order (score descending, row id ascending); ops.rank_ip, exact.
+
+    exclude: "none"; "self" (src itself does not count); "neighbours" (the filtered setting of link prediction: neither
+    src nor a node src already has an edge to in `adj` counts against dst -- dst itself always stays).  adj: a
+    store.DeviceCSR with columns in any order (the strictly ascending filter is built from it once and cached on it);
+    a WeightedAdj is read as its CSR.  A pair whose score is NaN is unranked: rank 0.  An id outside the table is an
+    IndexError."""
+    if not torch.is_tensor(emb) or emb.dim() != 2 or not emb.is_floating_point():
+        raise ValueError("link_rank: emb must be a [N, D] float tensor")
+    if exclude not in ops.TOPK_EXCLUDE:
+        raise ValueError("link_rank: exclude must be one of %s, not %r" % (sorted(ops.TOPK_EXCLUDE), exclude))
+    dev, N = emb.device, int(emb.shape[0])
+    src = _pair_ids(src, dev, "link_rank", "src", N)
+    dst = _pair_ids(dst, dev, "link_rank", "dst", N)
+    if int(src.shape[0]) != int(dst.shape[0]):
+        raise ValueError("link_rank: %d src for %d dst" % (int(src.shape[0]), int(dst.shape[0])))
+    csr = None
+    if exclude == "neighbours":
+        if adj is None:
+            raise ValueError("link_rank: exclude='neighbours' needs adj (a store.DeviceCSR)")
+        csr = filter_csr(_as_csr(adj, dev, "link_rank"))
+    if src.numel() == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.float32, device=dev)
+    return ops.rank_ip(emb, emb[src], dst, query_ids=src, csr=csr, exclude=exclude)
+
+
+def link_metrics(ranks, ks=(1, 10, 50)):
+    """{"n", "unranked", "mrr", "mean_rank", "hits@k"...} of link_rank's ranks.  An unranked pair (rank 0) counts as
+    reciprocal rank 0 and as a miss, and is left out of mean_rank (None when no pair is ranked)."""
+    r = np.asarray(ranks.cpu().numpy() if torch.is_tensor(ranks) else ranks, dtype=np.int64).reshape(-1)
+    if (r < 0).any():
+        raise ValueError("link_metrics: ranks are >= 1, or 0 for unranked")
+    n, live = int(r.size), r[r > 0].astype(np.float64)
+    out = {"n": n, "unranked": n - int(live.size),
+           "mrr": float((1.0 / live).sum() / n) if n else 0.0,
+           "mean_rank": float(live.mean()) if live.size else None}
+    for k in ks:
+        k = int(k)
+        if k < 1:
+            raise ValueError("link_metrics: ks must be >= 1, not %d" % k)
+        out["hits@%d" % k] = float((live <= k).sum() / n) if n else 0.0
+    return out
+
+
+def held_out_edges(adj, train_adj, nodes):
+    """The stored edges (u, v) of `adj` with u in `nodes` that `train_adj` does not store -> (src, dst) int64, on the
+    adjacency's device: by u in the caller's order (a repeated node repeats its edges), then v ascending; a duplicate
+    stored edge counts once.  adj, train_adj: store.DeviceCSR (a WeightedAdj is read as its CSR)."""
+    dev = adj.device if isinstance(adj, DeviceCSR) else torch.device("cpu")
+    full = filter_csr(_as_csr(adj, dev, "held_out_edges"))
+    seen = filter_csr(_as_csr(train_adj, dev, "held_out_edges"))
+    n = int(full.n_rows)
+    u = _pair_ids(nodes, dev, "held_out_edges", "node")
+    if u.numel() and (int(u.min()) < 0 or int(u.max()) >= n):
+        raise IndexError("held_out_edges: node id out of range of the adjacency")
+    deg = full.rowptr[u + 1] - full.rowptr[u]
+    first = torch.cumsum(deg, 0) - deg
+    src = torch.repeat_interleave(u, deg)
+    pos = torch.arange(int(src.shape[0]), dtype=torch.int64, device=dev) - torch.repeat_interleave(first, deg)
+    dst = full.col[torch.repeat_interleave(full.rowptr[u], deg) + pos].long()
+    m = int(seen.n_rows)
+    if seen.keys.numel():
+        key = src * m + dst
+        at = torch.searchsorted(seen.keys, key).clamp_(max=int(seen.keys.shape[0]) - 1)
+        stored = (seen.keys[at] == key) & (src < m) & (dst < m)
+    else:
+        stored = torch.zeros_like(src, dtype=torch.bool)
+    return src[~stored].contiguous(), dst[~stored].contiguous()

@@ -1455,3 +1455,145 @@ def topk_ip(table, queries, k, query_ids=None, csr=None, exclude="none", splits=
                                       _ptr(workspace), int(workspace.numel()) * workspace.element_size(), _ptr(ids),
                                       _ptr(scores), _stream()), "topk_ip")
     return ids, scores
+
+
+# =============================================================================================
+# Exact link ranking over embeddings: the rank of a target row among all rows (csrc/gsage_rank.hip)
+# =============================================================================================
+def rank_ip_workspace(Q, N, splits=0):
+    """(bytes of gsage_rank_ip's workspace, the split count used) for Q pairs over N rows -- host arithmetic."""
+    used = ctypes.c_int64(0)
+    nbytes = int(nat.lib().gsage_rank_ip_workspace(int(Q), int(N), int(splits), ctypes.byref(used)))
+    if nbytes < 0:
+        raise ValueError("rank_ip: Q = %d, N = %d, splits = %d are outside the kernel's limits "
+                         "(Q >= 1, 1 <= N < 2^31, 0 <= splits <= 1024)" % (Q, N, splits))
+    return nbytes, int(used.value)
+
+
+RANK_UNSORTED = ("rank_ip: a row of the filter csr is not strictly ascending (sorted columns, no duplicates) -- "
+                 "infer.link_rank builds such a filter from any adjacency")
+
+
+def _rank_ip_host(table, queries, target_ids, query_ids, csr, exclude):
+    """The definition in numpy (host mode): operands rounded as the compute mode sees them, float64 products rounded
+    to fp32, the count of allowed rows that beat the target under (score descending, id ascending)."""
+    dt = torch_dtype()
+    E = table.detach().to(dt).double().numpy()
+    Qm = queries.detach().to(dt).double().numpy()
+    Q, N = Qm.shape[0], E.shape[0]
+    tg = target_ids.numpy()
+    qid = None if query_ids is None else query_ids.numpy()
+    if exclude == "neighbours":
+        rowptr, col = csr.rowptr.cpu().numpy(), csr.col.cpu().numpy()
+    rank = np.zeros(Q, dtype=np.int64)
+    score = np.full(Q, -np.inf, dtype=np.float32)
+    ids = np.arange(N)
+    for q in range(Q):
+        t = int(tg[q])
+        if not 0 <= t < N:
+            continue
+        with np.errstate(invalid="ignore", over="ignore"):
+            s = (E @ Qm[q]).astype(np.float32)
+        score[q] = s[t]
+        allowed = np.ones(N, dtype=bool)
+        if exclude != "none" and 0 <= qid[q] < N:
+            allowed[qid[q]] = False
+            if exclude == "neighbours":
+                nb = col[rowptr[qid[q]]:rowptr[qid[q] + 1]].astype(np.int64)
+                if nb.size > 1 and (np.diff(nb) <= 0).any():
+                    raise ValueError(RANK_UNSORTED)
+                allowed[nb[(nb >= 0) & (nb < N)]] = False
+        allowed[t] = False
+        if np.isnan(s[t]):
+            continue
+        with np.errstate(invalid="ignore"):
+            beats = (s > s[t]) | ((s == s[t]) & (ids < t))
+        rank[q] = 1 + int((beats & allowed).sum())
+    return torch.from_numpy(rank), torch.from_numpy(score)
+
+
+def rank_ip(table, queries, target_ids, query_ids=None, csr=None, exclude="none", splits=0, workspace=None, out=None):
+    """The rank of row target_ids[q] of `table` [N, D] among all allowed rows for each row of `queries` [Q, D] by inner
+    product: rank = 1 + the number of allowed rows j != target that beat it under the total order (score descending,
+    row id ascending) -> (rank int64 [Q], score fp32 [Q] = the target's score); include/gsage.h, "Exact link ranking
+    over embeddings".  exclude: "none"; "self" (row query_ids[q] does not count); "neighbours" (neither that row nor
+    the columns of row query_ids[q] of `csr`, a store.DeviceCSR whose rows are STRICTLY ASCENDING -- ValueError
+    otherwise; infer.link_rank builds one from any adjacency).  The target itself is never excluded.  A target whose
+    score is NaN is unranked: rank 0.  A target or query id outside the table is an IndexError -- except in the
+    recorded form below, which cannot read ids back: there a target outside the table gets rank 0, score -inf.
+    Operands are taken in ops.config.compute_dtype (fp32 data is rounded to bf16 once in the bf16 mode).
+
+    CUDA: gsage_rank_ip (two launches, three for "neighbours"; recordable in a command list when the caller hands in
+    `workspace` -- a uint8 tensor of rank_ip_workspace(...) bytes -- and `out` = (rank, score); the filter's row
+    contract is then reported through csr.err_flag alone); the result does not depend on `splits` (0 = chosen by
+    the library).  CPU: the same definition in numpy."""
+    if exclude not in TOPK_EXCLUDE:
+        raise ValueError("rank_ip: exclude must be one of %s, not %r" % (sorted(TOPK_EXCLUDE), exclude))
+    if table.dim() != 2 or queries.dim() != 2 or int(table.shape[1]) != int(queries.shape[1]):
+        raise ValueError("rank_ip: table [N, D] and queries [Q, D] must share D")
+    if not (table.is_floating_point() and queries.is_floating_point()):
+        raise ValueError("rank_ip: table and queries must be floating point")
+    N, D = int(table.shape[0]), int(table.shape[1])
+    Q = int(queries.shape[0])
+    if not 1 <= D <= TOPK_D_MAX:
+        raise ValueError("rank_ip: D must be in [1, %d], not %d" % (TOPK_D_MAX, D))
+    if N < 1:
+        raise ValueError("rank_ip: the table has no rows")
+    if not 0 <= int(splits) <= 1024:
+        raise ValueError("rank_ip: splits must be in [0, 1024] (0 = chosen by the library), not %d" % int(splits))
+    recorded = workspace is not None and out is not None
+
+    def id_vector(ids, name):
+        ids = torch.as_tensor(ids)
+        if ids.is_floating_point() or ids.dtype == torch.bool:
+            raise ValueError("rank_ip: %s must be integers, not %s" % (name, ids.dtype))
+        ids = ids.to(device=table.device, dtype=torch.int64).contiguous().view(-1)
+        if int(ids.shape[0]) != Q:
+            raise ValueError("rank_ip: %d %s for %d queries" % (int(ids.shape[0]), name, Q))
+        if not recorded and Q and (int(ids.min()) < 0 or int(ids.max()) >= N):
+            raise IndexError("rank_ip: one of the %s is out of range of the %d table rows" % (name, N))
+        return ids
+    target_ids = id_vector(target_ids, "target_ids")
+    if exclude != "none":
+        if query_ids is None:
+            raise ValueError("rank_ip: exclude=%r needs query_ids" % exclude)
+        query_ids = id_vector(query_ids, "query_ids")
+    else:
+        query_ids = None
+    if exclude == "neighbours":
+        if csr is None:
+            raise ValueError("rank_ip: exclude='neighbours' needs csr")
+        if int(csr.n_rows) < N or csr.rowptr.device != table.device:
+            raise ValueError("rank_ip: csr must live on the table's device and have a row for each of its %d rows" % N)
+    else:
+        csr = None
+    if not table.is_cuda:
+        if Q == 0:
+            return torch.empty(0, dtype=torch.int64), torch.empty(0, dtype=torch.float32)
+        return _rank_ip_host(table, queries, target_ids, query_ids, csr, exclude)
+    dev = table.device
+    if out is None:
+        out = (torch.empty(Q, dtype=torch.int64, device=dev), torch.empty(Q, dtype=torch.float32, device=dev))
+    rank, score = out
+    assert rank.is_contiguous() and score.is_contiguous() and tuple(rank.shape) == (Q,) == tuple(score.shape)
+    assert rank.dtype == torch.int64 and score.dtype == torch.float32
+    if Q == 0:
+        return rank, score
+    cdt = torch_dtype()
+
+    def operand(t):
+        t = t.detach()
+        return t if t.dtype == cdt and t.stride(1) == 1 and t.stride(0) >= D else t.to(cdt).contiguous()
+    E, Qm = operand(table), operand(queries)
+    nbytes, _ = rank_ip_workspace(Q, N, splits)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nat.check(nat.lib().gsage_rank_ip(_ptr(E), _code(cdt), E.stride(0), N, _ptr(Qm), _code(cdt), Qm.stride(0), Q, D,
+                                      _ptr(target_ids), _ptr(query_ids), _ptr(csr.rowptr) if csr is not None else None,
+                                      _ptr(csr.col) if csr is not None else None, TOPK_EXCLUDE[exclude], int(splits),
+                                      _ptr(workspace), int(workspace.numel()) * workspace.element_size(), _ptr(rank),
+                                      _ptr(score), _ptr(csr.err_flag) if csr is not None else None, _stream()), "rank_ip")
+    if csr is not None and not recorded and int(csr.err_flag.item()) != 0:
+        csr.err_flag.zero_()
+        raise ValueError(RANK_UNSORTED)
+    return rank, score

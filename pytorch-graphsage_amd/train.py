@@ -44,6 +44,17 @@ Retrieval over the embeddings (infer.nearest, opt-in):
                           row of the adjacency, as one .npz with `ids` int64 [rows, k] and `scores` fp32 [rows, k],
                           best first, ties by ascending id (rank 0).  With --save-embeddings (and no --embed-nodes)
                           the embeddings are computed once for both files.
+  --link-eval             after training (sharing the one embedding pass with --save-embeddings / --save-neighbours):
+                          filtered link ranking of the held-out edges of the validation fold -- the edges stored in the
+                          evaluation adjacency whose source is in the fold and that the training adjacency does not
+                          store.  Each edge's target is ranked among ALL rows by gs.link_rank (exact; the source's known
+                          edges in the evaluation adjacency do not count against it) and one line
+                          {"link_eval": {"fold": "val", "n", "unranked", "mrr", "mean_rank", "hits@k"...}} is printed;
+                          with --show-test a second one for the test fold.  The embeddings come from the EVALUATION
+                          graph: the held-out edge takes part in message passing, as in GraphSAGE's inductive protocol;
+                          call gs.link_rank on embeddings of your own for anything else.  Sparse problems, one process.
+  --link-eval-edges M     at most M edges per fold (default 100000), a subsample seeded by --seed when there are more
+  --link-eval-ks 1,10,50  the k of hits@k
   --neighbours-k K        how many (default 10, at most 128)
   --neighbour-nodes IDS.npy   with --save-neighbours: only for the node ids in IDS.npy, in that order
   --neighbours-exclude none|self|neighbours   rows a node is never answered with (default self; neighbours: nor a
@@ -146,8 +157,29 @@ def save_embeddings(model, problem, path, nodes=None):
     np.save(path, gs.embeddings(model, problem.feats).cpu().numpy())
 
 
+def link_eval(model, problem, args, emb):
+    """--link-eval: filtered MRR / hits@k of the held-out edges of the validation fold (and, with --show-test, of the
+    test fold) over `emb`, one JSON line per fold.  Held out = stored in the evaluation adjacency with its source in
+    the fold, not stored in the training adjacency; filtered by the evaluation adjacency (gs.link_rank)."""
+    dev = emb.device
+    adj, train_adj = model.val_sampler.csr(dev), model.train_sampler.csr(dev)
+    ks = tuple(int(v) for v in args.link_eval_ks.split(','))
+    for i, fold in enumerate(['val', 'test'] if args.show_test else ['val']):
+        src, dst = gs.held_out_edges(adj, train_adj, torch.from_numpy(np.asarray(problem.nodes[fold], dtype=np.int64)))
+        n = int(src.shape[0])
+        if n > args.link_eval_edges:              # a seeded subsample, in the edges' order
+            pick = np.sort(np.random.RandomState(args.seed + i).choice(n, args.link_eval_edges, replace=False))
+            pick = torch.from_numpy(pick).to(dev)
+            src, dst = src[pick], dst[pick]
+        ranks, _ = gs.link_rank(emb, src, dst, exclude='neighbours', adj=adj)
+        res = {"fold": fold, "held_out_edges": n}
+        res.update(gs.link_metrics(ranks, ks))
+        print(dumps({"link_eval": res}))
+        sys.stdout.flush()
+
+
 def export(model, problem, args):
-    """--save-embeddings and --save-neighbours after training: one embedding pass serves both files."""
+    """--save-embeddings, --save-neighbours and --link-eval after training: one embedding pass serves all three."""
     emb = None
     if args.save_embeddings:
         if args.embed_nodes:
@@ -168,6 +200,8 @@ def export(model, problem, args):
             raise SystemExit('gsage: --save-neighbours: %s' % e)
         with open(args.save_neighbours, 'wb') as f:
             np.savez(f, ids=ids.cpu().numpy(), scores=scores.cpu().numpy())
+    if args.link_eval:
+        link_eval(model, problem, args, emb if emb is not None else gs.embeddings(model, problem.feats))
 
 
 class FusedEvaluator(object):
@@ -270,6 +304,9 @@ def parse_args(argv=None):
     parser.add_argument('--neighbours-k', type=int, default=10)
     parser.add_argument('--neighbour-nodes', type=str, default=None)
     parser.add_argument('--neighbours-exclude', type=str, default='self', choices=['none', 'self', 'neighbours'])
+    parser.add_argument('--link-eval', action="store_true")
+    parser.add_argument('--link-eval-edges', type=int, default=100000)
+    parser.add_argument('--link-eval-ks', type=str, default='1,10,50')
     parser.add_argument('--unsupervised', action="store_true")
     parser.add_argument('--walk-len', type=int, default=5)
     parser.add_argument('--n-negatives', type=int, default=20)
@@ -323,6 +360,15 @@ def main(argv=None, problem=None):
         raise SystemExit('gsage: --neighbour-nodes goes with --save-neighbours')
     if args.save_neighbours and not 1 <= args.neighbours_k <= gs.ops.TOPK_K_MAX:
         raise SystemExit('gsage: --neighbours-k must be in 1..%d' % gs.ops.TOPK_K_MAX)
+    if args.link_eval:
+        try:
+            ok = args.link_eval_edges >= 1 and all(int(v) >= 1 for v in args.link_eval_ks.split(','))
+        except ValueError:
+            ok = False
+        if not ok:
+            raise SystemExit('gsage: --link-eval-edges must be >= 1 and --link-eval-ks a comma-separated list of k >= 1')
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("GSAGE_FORCE_DDP", "0") == "1":
+            raise SystemExit('gsage: --link-eval: data-parallel launches are not supported (run a single process)')
     set_seeds(args.seed)
     gs.ops.set_compute_dtype(args.precision)
     gs.nn_modules.SparseUniformNeighborSampler.rng_default = args.rng
@@ -336,6 +382,8 @@ def main(argv=None, problem=None):
     ddp = gs.dist.init_from_env(args.cuda)            # no-op outside torch.distributed.run
     if problem is None:
         problem = NodeProblem(problem_path=args.problem_path, cuda=args.cuda)
+    if args.link_eval and not gs.problem._is_sparse(problem.adj):
+        raise SystemExit('gsage: --link-eval: a dense problem file holds neighbour samples, not edges to hold out')
     weighted = args.sampler_class == 'sparse_weighted_neighbor_sampler'
     if weighted:
         if not (isinstance(problem.adj, gs.store.WeightedAdj) and isinstance(problem.train_adj, gs.store.WeightedAdj)):
@@ -359,18 +407,18 @@ def main(argv=None, problem=None):
     if args.unsupervised:
         if args.full_neighbour_eval:
             raise SystemExit('gsage: --unsupervised: --full-neighbour-eval scores logits; there are none')
-        if args.save_embeddings or args.save_neighbours:
+        if args.save_embeddings or args.save_neighbours or args.link_eval:
             try:
                 gs.infer.check_supported(model)
             except ValueError as e:
-                raise SystemExit('gsage: --save-embeddings / --save-neighbours: %s' % e)
+                raise SystemExit('gsage: --save-embeddings / --save-neighbours / --link-eval: %s' % e)
         set_seeds(args.seed ** 2)
         return train_unsupervised(args, problem, model)
-    if args.full_neighbour_eval or args.save_embeddings or args.save_neighbours:
+    if args.full_neighbour_eval or args.save_embeddings or args.save_neighbours or args.link_eval:
         try:
             gs.infer.check_supported(model, model.val_sampler.csr('cpu') if weighted else None)
         except ValueError as e:
-            raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings / --save-neighbours: %s' % e)
+            raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings / --save-neighbours / --link-eval: %s' % e)
     evaluate_fn = (lambda mode: full_neighbour_evaluate(model, problem, mode=mode, closure=args.eval_closure)) \
         if args.full_neighbour_eval else \
         (lambda mode: evaluate(model, problem, mode=mode))
@@ -410,7 +458,7 @@ def main(argv=None, problem=None):
         sys.stdout.flush()
         if args.show_test:
             print(dumps({"test_f1": evaluate_fn('test')}))
-        if args.save_embeddings or args.save_neighbours:
+        if args.save_embeddings or args.save_neighbours or args.link_eval:
             export(model, problem, args)
     if ddp is not None:
         ddp.close()
@@ -455,7 +503,7 @@ def train_unsupervised(args, problem, model):
     if args.show_test:
         print(dumps({"test": evaluate_unsupervised(model, problem, 'test')}))
     sys.stdout.flush()
-    if args.save_embeddings or args.save_neighbours:
+    if args.save_embeddings or args.save_neighbours or args.link_eval:
         export(model, problem, args)
 
 
@@ -644,7 +692,7 @@ def train_fused(args, problem, model, ddp, start_time, cls):
         sys.stdout.flush()
         if args.show_test:
             print(dumps({"test_f1": test_metric}))
-        if args.save_embeddings or args.save_neighbours:
+        if args.save_embeddings or args.save_neighbours or args.link_eval:
             export(model, problem, args)
     if ddp is not None:
         ddp.close()
