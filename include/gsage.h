@@ -771,6 +771,10 @@ int32_t gsage_mean_tail_mfma_sampler_wgs(int64_t B, int64_t widest);
  * gsage_finalize_grads) and the norm pass is skipped.  prep_descs (DEVICE array of n_prep
  * gsage_prep_desc whose src point into p; may be NULL): the bf16 operand copies of the updated
  * weights are refreshed in the same launch.
+ * beta1, beta2, eps, weight_decay and max_norm are FLOAT arguments: the update is Adam with the float32 roundings of
+ * the caller's values, and 1 - beta is formed from those.  1 - float32(0.999) = 0.00099998713 is 1.3e-5 (relative)
+ * below 0.001, so against torch.optim.Adam(betas=(0.9, 0.999)), whose 1 - beta2 is a double, the g^2 term of v is
+ * smaller by that fraction (|dv| <= 1.3e-8 (g^2 + v)); for beta1 the fraction is 2.4e-7.
  */
 int gsage_clip_adam_step(float *p, float *g, float *m, float *v, int64_t n, float *partial,
                          const float *lr, int64_t *step, float beta1, float beta2, float eps,
@@ -804,9 +808,11 @@ typedef struct gsage_adam_desc {
     uint64_t *norm_slots;
     /* ABI 5 (with norm_slots, n_partial_ready == 0): NO finalisation launch ran -- g does not exist yet.  reduce_descs:
      * DEVICE array of n_reduce (<= 16) gsage_reduce_desc (below) that together cover [0, n): every update workgroup
-     * sums the partial buffers of the 1 024 elements it is about to update (buffer order 0 .. S-1: the bits
-     * gsage_finalize_grads would produce), stores them to g (then the clipped values, when the clip is active) and
-     * goes on as above.  Replaces the finalisation launch of the single-GPU step (~6.5 us between K5b and the update,
+     * sums the partial buffers of the 1 024 elements it is about to update in buffer order 0 .. S-1, stores them to g
+     * (then the clipped values, when the clip is active) and goes on as above.  Those are the bits gsage_finalize_grads
+     * produces where it adds in buffer order too -- its 16-byte and scalar paths (S < 32, or descriptors that fill
+     * their grid row) --; where it shares the partials of an element among threads (S >= 32 with few elements: per-share
+     * sums met in LDS) the two agree within the summation bound S 2^-24 sum |x_s| of a float32 sum, not bit for bit.  Replaces the finalisation launch of the single-GPU step (~6.5 us between K5b and the update,
      * reading the same partial buffers); a data-parallel step keeps it (the exchange needs the flat bucket).  The
      * step's ticks then ride in the K5b launch (gsage_wgrad_ticks_next).  NULL: g holds the gradient. */
     const void *reduce_descs;

@@ -77,13 +77,14 @@ struct AdamParams {
                                    // may also be updated by gsage_rows_*: both must produce the same bits
     unsigned long long *norm_slots;   // != null: the workgroups form the squared norm themselves (slot = update << 32 | partial)
     const ReduceDesc *rdesc;          // != null (with norm_slots): g does not exist yet -- element i of the bucket is the
-    int32_t n_rdesc;                  // sum of its descriptor's S partial buffers (what gsage_finalize_grads would store)
+    int32_t n_rdesc;                  // sum of its descriptor's S partial buffers, added in buffer order (reduce_partials4)
     int32_t stage_prep;               // != 0: kernels that can (adam_workgroup<.., STAGE>) stage the descriptors in LDS
 };
 
 // g[i] for four elements of the flat bucket (i[u] < 0: none) out of the partial buffers of their descriptors.
-// Partials are added in buffer order 0 .. S-1 (gsage_finalize_grads' order: the same bits), four buffers of each of
-// the four elements in flight together (16 loads per lane and round: the register budget of k_gather_multi_adam;
+// Partials are added in buffer order 0 .. S-1 -- the order, hence the bits, of gsage_finalize_grads' 16-byte and scalar
+// paths; its SL, 16-thread and four-wave paths add per-share sums and agree only within S 2^-24 sum |x_s| --, four
+// buffers of each of the four elements in flight together (16 loads per lane and round: the register budget of k_gather_multi_adam;
 // R = 12 in k_gather_multi_adam_wide: 48 per round, K5b's 24 slabs in two rounds instead of six).
 template <int R = 4>
 __device__ __forceinline__ void reduce_partials4(const ReduceDesc *__restrict__ rd, int n_rd, const int64_t (&i)[4],
