@@ -1075,6 +1075,18 @@ int gsage_head_skipgram(const float *E, int64_t lde, int32_t B, int32_t Q, int32
                         void *stream);
 int64_t gsage_head_skipgram_scratch(int32_t B, int32_t Q, int32_t D);
 
+/* gsage_head_skipgram_live -- the same two launches for a batch of fixed geometry whose last seeds are padding (the
+ * fused unsupervised engine: the reference's array_split chunks are never all of one size).  n_valid: device int32
+ * word, read by the kernels as gsage_head_ce reads its own; b = clamp(*n_valid, 1, B) seeds are live:
+ *     loss = (1/b) sum_{i < b} [ pair_w[i] softplus(-a_i) + neg_weight sum_q softplus(n_iq) ]
+ *   Seeds i >= b add nothing to the loss or to d z of the negatives, their rows of aff are left as they were, and rows
+ *   i and B + i of dE are written as zeros (the weight-gradient launch reads every row).  Every workgroup still
+ *   writes its partial and launch 2 sums all of them in workgroup order.  n_valid == NULL, or *n_valid >= B: the bits
+ *   of gsage_head_skipgram.  Same scratch, same limits, same errors.  Additive; the ABI version is unchanged. */
+int gsage_head_skipgram_live(const float *E, int64_t lde, int32_t B, int32_t Q, int32_t D, const float *pair_w,
+                             float neg_weight, const int32_t *n_valid, void *dE, int dE_dtype, int64_t ldd, float *loss,
+                             float *aff, float *scratch, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Weighted adjacency (csrc/gsage_weighted.hip, csrc/gsage_fullgraph.hip): edge-weight neighbour sampling and the
  * weight-normalised mean of layer-wise inference.  Additive; the ABI version is unchanged.  No reference counterpart.

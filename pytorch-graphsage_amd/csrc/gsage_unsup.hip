@@ -106,6 +106,7 @@ struct SkipgramParams {
     float *aff;              // [B, 1 + Q] or NULL
     float *partial;          // [n_wg][Q * D + 1]: d z_neg | loss
     float *loss;
+    const int32_t *n_valid;  // live seeds (device word) or NULL: seeds [b, B) are padding, b = clamp(*n_valid, 1, B)
     int64_t lde, ldd;
     int32_t B, Q, D, dE_dtype, n_wg;
     float neg_weight;
@@ -123,6 +124,12 @@ __device__ __forceinline__ float sg_sigmoid(float x)
 {
     const float e = expf(-fabsf(x));
     return (x >= 0.f ? 1.f : e) / (1.f + e);
+}
+
+// live seeds of the batch, as k_head_ce reads them (gsage_head.hip): a padded seed has no loss and no gradient
+__device__ __forceinline__ int sg_live(const SkipgramParams &p)
+{
+    return p.n_valid ? min(max(*p.n_valid, 1), p.B) : p.B;
 }
 
 __device__ __forceinline__ void sg_store(const SkipgramParams &p, int64_t row, int k, float g)
@@ -159,7 +166,7 @@ __global__ void __launch_bounds__(256)
 k_head_skipgram(const SkipgramParams p)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int D = p.D, Q = p.Q, B = p.B;
+    const int D = p.D, Q = p.Q, B = p.B, b = sg_live(p);
     float *nT = lds;                                  // [SG_QMAX][16] n_iq           (16-byte rows: ds_read_b128)
     float *dT = nT + SG_QMAX * SG_ROWS;               // [SG_QMAX][16] d n_iq
     float *sinv = dT + SG_QMAX * SG_ROWS;             // [16] 1 / norm of the seed rows
@@ -169,7 +176,7 @@ k_head_skipgram(const SkipgramParams p)
     float *zdz = dav + SG_ROWS;                       // [16] <z_i, d z_i>
     float *ninv = zdz + SG_ROWS;                      // [SG_QMAX] 1 / norm of the negatives' rows
     float *red = ninv + SG_QMAX;                      // [4] (+ 12 of padding)
-    float *zs = red + 16;                             // [16][D] normalised seed rows (zero rows past B)
+    float *zs = red + 16;                             // [16][D] normalised seed rows (zero rows past b)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int row0 = blockIdx.x * SG_ROWS;
@@ -184,7 +191,7 @@ k_head_skipgram(const SkipgramParams p)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int k = lane + 64 * j;
-            const bool ok = k < D && i < B;
+            const bool ok = k < D && i < b;
             es[j] = ok ? E[(int64_t)i * p.lde + k] : 0.f;
             ep[j] = ok ? E[((int64_t)B + i) * p.lde + k] : 0.f;
         }
@@ -241,12 +248,12 @@ k_head_skipgram(const SkipgramParams p)
     __syncthreads();
 
     // 3. loss, aff, d n_iq; then (a lane per row) d a_i and <z_i, d z_i> = d a_i a_i + sum_q d n_iq n_iq
-    const float invB = 1.f / (float)B;
+    const float invB = 1.f / (float)b;
     float my_loss = 0.f;
     for (int e = tid; e < Q * SG_ROWS; e += 256) {
         const int q = e >> 4, i = row0 + (e & 15);
         float dn = 0.f;
-        if (i < B) {
+        if (i < b) {
             const float n = nT[e];
             if (p.aff) p.aff[(int64_t)i * (1 + Q) + 1 + q] = n;
             my_loss += p.neg_weight * sg_softplus(n);
@@ -258,7 +265,7 @@ k_head_skipgram(const SkipgramParams p)
     if (tid < SG_ROWS) {
         const int r = tid, i = row0 + r;
         float da = 0.f, s = 0.f;
-        if (i < B) {
+        if (i < b) {
             const float a = av[r], w = p.pair_w[i];
             if (p.aff) p.aff[(int64_t)i * (1 + Q)] = a;
             my_loss += w * sg_softplus(-a);
@@ -283,7 +290,7 @@ k_head_skipgram(const SkipgramParams p)
         for (int r = 0; r < SG_ROWS; ++r) {
             z[r] = zs[r * D + k];
             dz[r] = 0.f;
-            zp[r] = (row0 + r < B) ? E[((int64_t)B + row0 + r) * p.lde + k] : 0.f;
+            zp[r] = (row0 + r < b) ? E[((int64_t)B + row0 + r) * p.lde + k] : 0.f;
         }
         for (int q0 = 0; q0 < Q; q0 += 4) {
             float en[4];
@@ -310,7 +317,9 @@ k_head_skipgram(const SkipgramParams p)
 #pragma unroll
         for (int r = 0; r < SG_ROWS; ++r) {
             const int i = row0 + r;
-            if (i < B) {                                       // block-uniform
+            if (i >= b) {                                      // block-uniform; padding: exact zeros (K5b reads them)
+                if (i < B) { sg_store(p, i, k, 0.f); sg_store(p, (int64_t)B + i, k, 0.f); }
+            } else {
                 const float da = dav[r], zpos = zp[r] * pinv[r];
                 sg_store(p, i, k, (da * zpos + dz[r] - z[r] * zdz[r]) * sinv[r]);
                 sg_store(p, (int64_t)B + i, k, da * (z[r] - zpos * av[r]) * pinv[r]);     // <z_pos, d z_pos> = d a_i a_i
@@ -370,7 +379,7 @@ k_head_skipgram_neg(const SkipgramParams p)
         float l = 0.f;
         for (int g = lane; g < p.n_wg; g += 64) l += p.partial[(int64_t)g * width + width - 1];
         l = sg_wave_sum(l);
-        if (lane == 0) *p.loss = l / (float)p.B;
+        if (lane == 0) *p.loss = l / (float)sg_live(p);
     }
 }
 
@@ -418,9 +427,9 @@ int64_t gsage_head_skipgram_scratch(int32_t B, int32_t Q, int32_t D)
     return ceil_div(B, SG_ROWS) * ((int64_t)Q * D + 1);
 }
 
-int gsage_head_skipgram(const float *E, int64_t lde, int32_t B, int32_t Q, int32_t D, const float *pair_w,
-                        float neg_weight, void *dE, int dE_dtype, int64_t ldd, float *loss, float *aff, float *scratch,
-                        void *stream)
+int gsage_head_skipgram_live(const float *E, int64_t lde, int32_t B, int32_t Q, int32_t D, const float *pair_w,
+                             float neg_weight, const int32_t *n_valid, void *dE, int dE_dtype, int64_t ldd, float *loss,
+                             float *aff, float *scratch, void *stream)
 {
     GSAGE_REQUIRE(E && pair_w && dE && loss && scratch, "head_skipgram: null pointer");
     GSAGE_REQUIRE(B > 0 && Q > 0 && Q <= SG_QMAX && D > 0 && D <= SG_DMAX,
@@ -430,6 +439,7 @@ int gsage_head_skipgram(const float *E, int64_t lde, int32_t B, int32_t Q, int32
     SkipgramParams p;
     p.E = E; p.pair_w = pair_w; p.dE = dE; p.aff = aff; p.partial = scratch; p.loss = loss; p.lde = lde; p.ldd = ldd;
     p.B = B; p.Q = Q; p.D = D; p.dE_dtype = dE_dtype; p.n_wg = (int32_t)ceil_div(B, SG_ROWS); p.neg_weight = neg_weight;
+    p.n_valid = n_valid;
     const size_t lds = sizeof(float) * (2 * SG_QMAX * SG_ROWS + 5 * SG_ROWS + SG_QMAX + 16 + (size_t)SG_ROWS * D);
     hipStream_t s = (hipStream_t)stream;
     if (D <= 256) {
@@ -446,6 +456,14 @@ int gsage_head_skipgram(const float *E, int64_t lde, int32_t B, int32_t Q, int32
     if (rc != GSAGE_OK) return rc;
     launch(k_head_skipgram_neg, dim3(Q), dim3(256), 0, s, p);
     return check_launch("head_skipgram_neg");
+}
+
+int gsage_head_skipgram(const float *E, int64_t lde, int32_t B, int32_t Q, int32_t D, const float *pair_w,
+                        float neg_weight, void *dE, int dE_dtype, int64_t ldd, float *loss, float *aff, float *scratch,
+                        void *stream)
+{
+    return gsage_head_skipgram_live(E, lde, B, Q, D, pair_w, neg_weight, nullptr, dE, dE_dtype, ldd, loss, aff, scratch,
+                                    stream);
 }
 
 }  // extern "C"

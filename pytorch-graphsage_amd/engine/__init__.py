@@ -7,6 +7,8 @@ engine -- the whole train_step (reference models.py:97-104) as recorded launches
   mean.FusedMeanTrainStep      mean aggregators (BASELINE configs[1], [4])
   pool.FusedPoolTrainStep      max-pool / mean-pool aggregators (configs[2])
   attn.FusedAttnTrainStep      attention aggregators, optionally over trainable node embeddings (configs[3])
+  unsup.FusedUnsupMeanTrainStep  GSUnsupervised under mean aggregators: builder, encoder, skip-gram head, update
+                               (opt-in: train.py --unsupervised --engine fused; not one of ENGINES, whose call takes targets)
 
 `fused_engine_for(model, feats)` picks the engine that covers a model, or explains why none does.
 """
@@ -17,6 +19,7 @@ from .common import FusedTrainStep, _PrepDesc, _ReduceDesc   # noqa: F401
 from .mean import FusedMeanTrainStep
 from .pool import FusedPoolTrainStep
 from .attn import FusedAttnTrainStep
+from .unsup import FusedUnsupMeanTrainStep                   # noqa: F401
 
 ENGINES = (FusedMeanTrainStep, FusedPoolTrainStep, FusedAttnTrainStep)
 

@@ -200,12 +200,7 @@ class FusedTrainStep(object):
         self._upload_prep_descs()
         self._init_head(loss_fn, example_targets)
         if self.eval_only:
-            Cc, D2c = model.fc.weight.shape
-            if self.fused_l1:                      # (what _install_reduce gives the training engines' heads)
-                self.l1_scratch = torch.zeros(nat.lib().gsage_head_l1_scratch(self.B, D2c), dtype=torch.float32,
-                                              device=self.dev)
-            elif not self.fused_head:
-                self.head_stage = torch.zeros(Cc * D2c + Cc, dtype=torch.float32, device=self.dev)
+            self._init_head_eval()
             self._param_ptrs = self._current_param_ptrs()
             self.refresh_weights()
         else:
@@ -397,13 +392,22 @@ class FusedTrainStep(object):
                 assert self.world * self.B <= 8192, "gsage_head_l1_sharded: the global batch must stay <= 8192 seeds"
                 self.tg_all = torch.zeros(self.world * self.B, dtype=torch.float32, device=self.dev)
 
-    def _install_reduce(self, rdesc):
-        """Append the prep bias's and the head's gradient sources, check that every parameter is covered, upload."""
-        model, dev = self.model, self.dev
-        f32 = torch.float32
-        if self.emb:                                      # prep.fc.bias: column sums of the level-0 input gradient
-            E, ib = self.E, self.pidx[id(model.prep.fc.bias)]
-            rdesc.append(_ReduceDesc(self.prep_bpart.data_ptr(), E, self.poff[ib], self.prep_bpart.shape[0], 1, E, E))
+    def _init_head_eval(self):
+        """(eval_only) the head's work buffers that _install_reduce gives the training engines' heads"""
+        Cc, D2c = self.model.fc.weight.shape
+        if self.fused_l1:
+            self.l1_scratch = torch.zeros(nat.lib().gsage_head_l1_scratch(self.B, D2c), dtype=torch.float32,
+                                          device=self.dev)
+        elif not self.fused_head:
+            self.head_stage = torch.zeros(Cc * D2c + Cc, dtype=torch.float32, device=self.dev)
+
+    def _head_recordable(self):
+        """can the head's launches sit in a native command list?  (the stock-torch head cannot)"""
+        return bool(self.fused_head or self.fused_l1)
+
+    def _head_reduce_descs(self):
+        """The head's gradient sources for the finalisation (fc.weight and fc.bias: one descriptor)."""
+        model, dev, f32, rdesc = self.model, self.dev, torch.float32, []
         Cc, D2c = model.fc.weight.shape
         ifc = self.pidx[id(model.fc.weight)]
         assert self.pidx[id(model.fc.bias)] == ifc + 1
@@ -419,6 +423,16 @@ class FusedTrainStep(object):
             self.head_stage = torch.zeros(Cc * D2c + Cc, dtype=f32, device=dev)
             rdesc.append(_ReduceDesc(self.head_stage.data_ptr(), 0, self.poff[ifc], 1, 1, Cc * D2c + Cc,
                                      Cc * D2c + Cc))
+        return rdesc
+
+    def _install_reduce(self, rdesc):
+        """Append the prep bias's and the head's gradient sources, check that every parameter is covered, upload."""
+        model, dev = self.model, self.dev
+        f32 = torch.float32
+        if self.emb:                                      # prep.fc.bias: column sums of the level-0 input gradient
+            E, ib = self.E, self.pidx[id(model.prep.fc.bias)]
+            rdesc.append(_ReduceDesc(self.prep_bpart.data_ptr(), E, self.poff[ib], self.prep_bpart.shape[0], 1, E, E))
+        rdesc += self._head_reduce_descs()
         covered = sum(d.rows * d.cols for d in rdesc)
         uncovered = int(self.table.numel()) if self.emb else 0     # the scatter-added embedding table
         assert covered + uncovered == self.flat_p.numel(), "every parameter must be covered by a gradient source"
@@ -494,7 +508,7 @@ class FusedTrainStep(object):
         # "graph" = hipGraphs.
         self.capture_mode = {True: "cmdlist", False: None, None: None}.get(capture, capture)
         assert self.capture_mode in (None, "cmdlist", "graph")
-        if self.capture_mode == "cmdlist" and not (self.fused_head or self.fused_l1):
+        if self.capture_mode == "cmdlist" and not self._head_recordable():
             self.capture_mode = "graph"              # the stock-torch head cannot be recorded
         if self.capture_mode == "graph" and self.world > 1 and self.fused_l1:
             self.capture_mode = "cmdlist"            # (the sharded L1 head gathers the global targets INSIDE the step:

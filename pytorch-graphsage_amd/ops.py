@@ -1300,10 +1300,12 @@ def _skipgram_host(E, B, Q, pair_w, neg_weight):
     return loss, torch.cat([a.unsqueeze(1), n], dim=1)
 
 
-def skipgram_head(E, B, Q, pair_w, neg_weight=1.0, grad_dtype=torch.float32, grad_ld=None):
+def skipgram_head(E, B, Q, pair_w, neg_weight=1.0, grad_dtype=torch.float32, grad_ld=None, n_valid=None):
     """gsage_head_skipgram on the un-normalised rows E [2B + Q, D] = [seeds | positives | negatives] (CUDA, fp32, unit
     column stride): -> (loss [1], aff [B, 1 + Q] = [a_i | n_iq], dE [2B + Q, D] = d loss / d E in `grad_dtype`).
-        loss = (1/B) sum_i [pair_w_i softplus(-a_i) + neg_weight sum_q softplus(n_iq)],  a, n = cosines of the rows"""
+        loss = (1/B) sum_i [pair_w_i softplus(-a_i) + neg_weight sum_q softplus(n_iq)],  a, n = cosines of the rows
+    n_valid (an int, or an int32 device word): gsage_head_skipgram_live -- only the first b = clamp(n_valid, 1, B) seeds
+    are live: the loss is their mean, rows i and B + i of dE are zero for i >= b, and aff[b:] is returned as zeros."""
     assert E.is_cuda and E.dtype == torch.float32 and E.dim() == 2 and int(E.shape[0]) == 2 * B + Q
     if E.stride(1) != 1:
         E = E.contiguous()
@@ -1315,11 +1317,20 @@ def skipgram_head(E, B, Q, pair_w, neg_weight=1.0, grad_dtype=torch.float32, gra
     dE = torch.empty(2 * B + Q, ldd, dtype=grad_dtype, device=E.device) if ldd == D else \
         torch.zeros(2 * B + Q, ldd, dtype=grad_dtype, device=E.device)
     loss = torch.empty(1, dtype=torch.float32, device=E.device)
-    aff = torch.empty(B, 1 + Q, dtype=torch.float32, device=E.device)
     scratch = torch.empty(max(int(L.gsage_head_skipgram_scratch(B, Q, D)), 1), dtype=torch.float32, device=E.device)
-    nat.check(L.gsage_head_skipgram(_ptr(E), E.stride(0), B, Q, D, _ptr(pair_w), float(neg_weight), _ptr(dE),
-                                    _code(grad_dtype), ldd, _ptr(loss), _ptr(aff), _ptr(scratch), _stream()),
-              "head_skipgram")
+    if n_valid is None:
+        aff = torch.empty(B, 1 + Q, dtype=torch.float32, device=E.device)
+        nat.check(L.gsage_head_skipgram(_ptr(E), E.stride(0), B, Q, D, _ptr(pair_w), float(neg_weight), _ptr(dE),
+                                        _code(grad_dtype), ldd, _ptr(loss), _ptr(aff), _ptr(scratch), _stream()),
+                  "head_skipgram")
+        return loss, aff, dE[:, :D]
+    if not torch.is_tensor(n_valid):
+        n_valid = torch.tensor([int(n_valid)], dtype=torch.int32, device=E.device)
+    assert n_valid.is_cuda and n_valid.dtype == torch.int32 and n_valid.numel() == 1
+    aff = torch.zeros(B, 1 + Q, dtype=torch.float32, device=E.device)
+    nat.check(L.gsage_head_skipgram_live(_ptr(E), E.stride(0), B, Q, D, _ptr(pair_w), float(neg_weight), _ptr(n_valid),
+                                         _ptr(dE), _code(grad_dtype), ldd, _ptr(loss), _ptr(aff), _ptr(scratch),
+                                         _stream()), "head_skipgram_live")
     return loss, aff, dE[:, :D]
 
 

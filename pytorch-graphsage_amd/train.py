@@ -63,7 +63,10 @@ Retrieval over the embeddings (infer.nearest, opt-in):
 --unsupervised (with --walk-len, --n-negatives, --neg-weight): train the encoder without labels (models.GSUnsupervised:
 random-walk positives, degree^0.75 negatives, skip-gram loss on the HIP head).  Targets are ignored; every batch
 prints one JSON line with its loss, every epoch the validation fold's loss and mean reciprocal rank ("mrr").  The
-module path runs it (said on stderr); data-parallel launches are refused.
+module path runs it (said on stderr) under --engine auto / eager; data-parallel launches are refused.  --engine fused
+(opt-in, with --rng philox, mean aggregators, the identity prep and the sparse sampler) runs every step as one recorded
+list of launches on engine.FusedUnsupMeanTrainStep -- batch builder, sampler, encoder, skip-gram head, backward,
+update -- and is an error, with the engine's sentence, where that engine does not cover the run.
 
 --sampler-class sparse_weighted_neighbor_sampler: neighbours drawn in proportion to edge weights (a problem file with
 `adj_weight` / `train_adj_weight`; include/gsage.h, "Weighted adjacency").  Always Philox; the module path runs it (said
@@ -294,7 +297,10 @@ def parse_args(argv=None):
     # build-specific (not in the reference)
     parser.add_argument('--rng', type=str, default='compat', choices=['compat', 'philox'])
     parser.add_argument('--precision', type=str, default='bf16', choices=['bf16', 'fp32'])
-    parser.add_argument('--engine', type=str, default='auto', choices=['auto', 'eager', 'fused'])
+    parser.add_argument('--engine', type=str, default='auto', choices=['auto', 'eager', 'fused'],
+                        help='auto: a fused engine where one covers the run, else the module path (said on stderr); '
+                             'eager: the module path; fused: an engine or an error.  --unsupervised runs on the module '
+                             'path unless --engine fused asks for FusedUnsupMeanTrainStep (needs --rng philox)')
     parser.add_argument('--feature-dtype', type=str, default='native', choices=['native', 'fp8'])
     parser.add_argument('--full-neighbour-eval', action="store_true")
     parser.add_argument('--save-embeddings', type=str, default=None)
@@ -479,8 +485,18 @@ def evaluate_unsupervised(model, problem, mode='val'):
 
 
 def train_unsupervised(args, problem, model):
-    """The --unsupervised run: GSUnsupervised.train_step on the module path, one JSON line per batch."""
-    choose_engine(args, problem, model, None)          # (says on stderr that the module path runs)
+    """The --unsupervised run, one JSON line per batch: GSUnsupervised.train_step on the module path, or -- with
+    --engine fused -- the same step on engine.FusedUnsupMeanTrainStep (the batches are the reference's chunks either
+    way; the engine pads the short ones and gives the padding no loss)."""
+    cls = choose_engine(args, problem, model, None)    # (None: says on stderr that the module path runs)
+    eng = None
+    if cls is not None:
+        nodes = problem.nodes['train']
+        n_batches = nodes.shape[0] // args.batch_size + 1
+        B = -(-nodes.shape[0] // n_batches)            # the largest of the reference's array_split chunks
+        example = torch.from_numpy(np.ascontiguousarray(nodes[:B])).long().to(torch.device('cuda'))
+        eng = cls(model, problem.feats, example)
+        print('gsage: train_step runs on %s' % cls.__name__, file=sys.stderr)
     start_time = time()
     val = {"loss": None, "mrr": None}
     loss = None
@@ -488,8 +504,8 @@ def train_unsupervised(args, problem, model):
     for epoch in range(args.epochs):
         model.train()
         for ids, _, epoch_progress in problem.iterate(mode='train', shuffle=True, batch_size=args.batch_size):
-            model.set_progress((epoch + epoch_progress) / args.epochs)
-            loss = float(model.train_step(ids=ids, feats=problem.feats))
+            (eng if eng is not None else model).set_progress((epoch + epoch_progress) / args.epochs)
+            loss = float(eng(ids) if eng is not None else model.train_step(ids=ids, feats=problem.feats))
             print(dumps({"epoch": epoch, "epoch_progress": epoch_progress, "loss": loss, "val_loss": val["loss"],
                          "val_mrr": val["mrr"], "time": time() - start_time}))
             sys.stdout.flush()
@@ -503,6 +519,8 @@ def train_unsupervised(args, problem, model):
     if args.show_test:
         print(dumps({"test": evaluate_unsupervised(model, problem, 'test')}))
     sys.stdout.flush()
+    if eng is not None:
+        eng.close()
     if args.save_embeddings or args.save_neighbours or args.link_eval:
         export(model, problem, args)
 
@@ -514,15 +532,24 @@ def choose_engine(args, problem, model, ddp):
     reference's unequal chunks) and the batch geometry.  --engine auto: one stderr line says why the module path
     runs; --engine fused: the same sentence is an error."""
     def give_up(why):
-        if args.unsupervised:
+        if args.unsupervised and args.engine != 'fused':
             print('gsage: unsupervised model: module path', file=sys.stderr)
             return None
         if args.engine == 'fused':
             raise SystemExit('gsage: --engine fused: %s (use --engine auto / eager)' % why)
         print('gsage: %s; using the module path' % why, file=sys.stderr)
         return None
-    if args.unsupervised:                           # no fused engine is attempted
-        return give_up('unsupervised model')
+    if args.unsupervised:                           # the engine is opt-in: --engine fused, or the module path
+        if args.engine != 'fused':
+            return give_up('unsupervised model')
+        cls = gs.engine.FusedUnsupMeanTrainStep
+        why = cls.why_not(model, problem.feats, ddp)
+        if why is not None:
+            return give_up(why)
+        nodes = problem.nodes['train']
+        if nodes.shape[0] // (nodes.shape[0] // args.batch_size + 1) < 2:
+            return give_up('chunks of fewer than two training nodes')
+        return cls
     if isinstance(model.train_sampler, gs.nn_modules.SparseWeightedNeighborSampler):
         return give_up('no fused engine covers the weighted sampler (SparseWeightedNeighborSampler)')
     cls = gs.engine.fused_engine_for(model, problem.feats, explain=True, ddp=ddp)

@@ -4,12 +4,15 @@ fan-out 25/10, dims 128/128, B = 512 seeds, Q = 20 negatives, walk_len = 5, bf16
 
 One JSON line per measurement, appended to --out (default profiles/unsup_bench.jsonl), all in one process:
   unsup_train_step   ms / step of GSUnsupervised.train_step (builder + one encoder pass over 2B + Q ids + head + Adam)
+  unsup_engine_step  ms / step of engine.FusedUnsupMeanTrainStep on a twin model: the same step as one recorded list
+  unsup_engine_launches   us of the launches the recorded step times in place (builder, the head's two launches, the
+                     level-0 projection, K5b), from the list's timing marks
   sup_train_step     ms / step of GSSupervised.train_step on the module path with 2B + Q = 1044 seeds: the comparison
                      (same encoder work, cross-entropy head through torch ops instead of the skip-gram head)
   unsup_batch        us / call of the builder's one launch
   head_skipgram      us / call of the head's two launches (D = 256)
 Times are device events around `--steps` back-to-back calls after `--warmup` calls; the two train steps alternate
-`--rounds` times so that a drift of the machine shows in the spread.  Needs a GPU: there is no CPU fallback."""
+(and the engine's step) alternate `--rounds` times so that a drift of the machine shows in the spread.  Needs a GPU: there is no CPU fallback."""
 import argparse
 import importlib
 import json
@@ -73,6 +76,8 @@ def main():
     torch.manual_seed(0)
     unsup = gs.GSUnsupervised(walk_len=args.walk_len, n_negatives=Q, **common).to(dev)
     sup = gs.GSSupervised(n_classes=41, **common).to(dev)
+    torch.manual_seed(0)
+    unsup_e = gs.GSUnsupervised(walk_len=args.walk_len, n_negatives=Q, **common).to(dev)
     seeds = torch.from_numpy(rng.randint(1, n, size=B)).to(dev)
     seeds_sup = torch.from_numpy(rng.randint(1, n, size=2 * B + Q)).to(dev)
     targets = torch.from_numpy(rng.randint(0, 41, size=(2 * B + Q, 1))).to(dev)
@@ -82,13 +87,28 @@ def main():
             "B": B, "Q": Q, "walk_len": args.walk_len, "precision": "bf16", "steps": args.steps, "warmup": args.warmup,
             "stamp": time.strftime("%Y-%m-%d")}
     rows = []
-    un, su = [], []
+    eng = gs.engine.FusedUnsupMeanTrainStep(unsup_e, store, seeds)
+    un, su, en = [], [], []
     for _ in range(args.rounds):
         un.append(timed(lambda: unsup.train_step(seeds, store), args.steps, args.warmup))
+        en.append(timed(lambda: eng(seeds), args.steps, args.warmup))
         su.append(timed(lambda: sup.train_step(seeds_sup, store, targets, gs.ProblemLosses.classification), args.steps,
                         args.warmup))
     rows.append(dict(base, what="unsup_train_step", ms_per_step=float(np.median(un)), rounds_ms=un))
     rows.append(dict(base, what="sup_train_step", seeds=2 * B + Q, ms_per_step=float(np.median(su)), rounds_ms=su))
+    rows.append(dict(base, what="unsup_engine_step", rows=eng.B, capture=eng.capture_mode,
+                     ms_per_step=float(np.median(en)), rounds_ms=en))
+    eng.instrument(True)
+    marks = []
+    for _ in range(20):
+        eng(seeds)
+        torch.cuda.synchronize()
+        marks.append(eng.last_launch_ms())
+    names = sorted(set().union(*marks))
+    rows.append(dict(base, what="unsup_engine_launches", steps=len(marks),
+                     us={k: 1e3 * float(np.median([m[k] for m in marks if k in m])) for k in names},
+                     note="head = both launches between two marks; the others are single kernels timed at dispatch"))
+    eng.instrument(False)
 
     csr, cdf = unsup._walk_graph(True, dev)
     ph = {"seed": 0, "call_base": 0}
