@@ -1267,6 +1267,53 @@ int gsage_rank_ip(const void *table, int table_dtype, int64_t ldt, int64_t N, co
                   const int64_t *rowptr, const int32_t *col, int exclude, int32_t splits, void *workspace,
                   int64_t workspace_bytes, int64_t *out_rank, float *out_score, int32_t *err_flag, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Linear probe over embeddings (csrc/gsage_probe.hip): one full-batch loss-and-gradient evaluation of a linear
+ * classifier on selected rows of a table (ops.probe_pass / infer.LinearProbe).  Additive; the ABI version is
+ * unchanged.  The losses are the reference's ProblemLosses.classification (F.cross_entropy) and
+ * ProblemLosses.multilabel_classification (F.multilabel_soft_margin_loss).
+ *
+ * Given a table X [N, ldx], ids int64 [n], an fp32 master W [C, D] (dense), bias fp32 [C] and targets:
+ *     z[i, c] = sum_d X[ids[i], d] * W~[c, d] + bias[c]
+ *     task = 0 (classification)            targets int64 [n], class ids in [0, C):
+ *         l_i = logsumexp_c z[i, .] - z[i, y_i],                      G[i, c] = softmax(z_i)[c] - [c == y_i]
+ *     task = 1 (multilabel_classification) targets fp32 [n, ldy], values in [0, 1]:
+ *         l_i = (1/C) sum_c (softplus(z[i, c]) - y[i, c] z[i, c]),    G[i, c] = (sigmoid(z[i, c]) - y[i, c]) / C
+ *     loss = (1/n) sum_i l_i,   dW = (1/n) G^T X[ids]  [C, D],   db = (1/n) sum_i G[i, .]
+ * Compute mode = the table's dtype: GSAGE_BF16 rows meet W~ = W rounded to bf16 (RNE, when it is staged) on
+ * mfma_f32_32x32x16_bf16; GSAGE_F32 rows meet W~ = W on the exact mfma_f32_32x32x2f32.  Logits, probabilities and G
+ * never leave the registers (no n x C buffer); in bf16 mode G enters the gradient product as a hi + lo pair of bf16
+ * (relative error 2^-17, not 2^-9).
+ *
+ * Outputs:
+ *     partial   fp32 [S][C*D + C + 1]: one row [dW | db | loss] per workgroup (a contiguous range of 32-row tiles),
+ *               already scaled by 1/n -- gsage_head_ce's convention, so ONE gsage_reduce_desc (src = partial, S,
+ *               rows = 1, cols = C*D + C, stride = ld = C*D + C + 1) hands it to gsage_finalize_grads unchanged.
+ *               S = splits, or for splits = 0 the count the library chooses: min(ceil(n / 32), 256).  A range
+ *               that holds no tile (splits > tiles) writes zeros.
+ *     loss_out  device float: the sum over S of the loss slots in buffer order (a second, one-workgroup launch).
+ *               After gsage_probe_loss_index_next(index) the NEXT gsage_probe_pass of the calling thread writes
+ *               loss_out[*index] instead (index: DEVICE int64, read when the launch runs; consumed by that call,
+ *               also while a command list is being recorded) -- e.g. the step counter gsage_finalize_grads ticks
+ *               AFTER the pass, so a replayed list fills a loss history.
+ * No atomics: for fixed (n, C, D, splits) every sum has one order and the result is bit-identical from call to call;
+ * different splits agree to fp32 round-off.
+ *
+ * Limits (GSAGE_EINVAL, the message names the argument; checked on the host before anything touches the GPU):
+ * 1 <= C <= 128; 1 <= D <= 1024; 1 <= n < 2^31; N >= 1; ldx >= D (elements; nothing past a row's D columns is
+ * read); ldy >= C for task 1; 0 <= splits <= 1024.  ids must lie in [0, N) and class ids in [0, C) (the callers
+ * check once; an id outside [0, N) reads as a zero row, a class outside [0, C) as no class).  Two launches;
+ * recordable in a command list.
+ *
+ * gsage_probe_pass_scratch (HOST arithmetic, no GPU): the number of FLOATS of `partial` for (n, C, D, splits), -1 for
+ * arguments outside the limits; divided by C*D + C + 1 it is S.
+ * ---------------------------------------------------------------------------------------- */
+int64_t gsage_probe_pass_scratch(int64_t n, int32_t C, int32_t D, int32_t splits);
+int gsage_probe_loss_index_next(const int64_t *index);
+int gsage_probe_pass(const void *table, int dtype, int64_t ldx, int64_t N, const int64_t *ids, int64_t n,
+                     const void *targets, int task, int64_t ldy, const float *W, const float *bias, int32_t C,
+                     int32_t D, int32_t splits, float *partial, float *loss_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

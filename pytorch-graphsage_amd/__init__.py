@@ -13,7 +13,9 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
                               its k-hop closure blocks (infer.closure / infer.query); infer.nearest: the k nearest
                               rows of an embedding table (ops.topk_ip, csrc/gsage_retrieve.hip); infer.link_rank /
                               link_metrics / held_out_edges: the exact (filtered) rank of an edge's other endpoint
-                              among all rows, MRR and hits@k (ops.rank_ip, csrc/gsage_rank.hip)
+                              among all rows, MRR and hits@k (ops.rank_ip, csrc/gsage_rank.hip); infer.linear_probe /
+                              probe_eval: a linear classifier fitted on the frozen embeddings, micro / macro F1 of
+                              the val / test folds (ops.probe_pass, csrc/gsage_probe.hip)
     store.WeightedAdj         edge weights: sparse_weighted_neighbor_sampler, weight-normalised full-neighbourhood mean
     models.GSUnsupervised     label-free training: random-walk positives, degree^0.75 negatives, skip-gram head
     engine/                   the whole train_step as recorded launches (captured autograd path; fused mean /
@@ -21,8 +23,8 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
 """
 from . import _native, dist, engine, helpers, infer, nn_modules, ops, optim, problem, store        # noqa: F401
 from .helpers import set_seeds, to_numpy                            # noqa: F401
-from .infer import (embeddings, full_neighbour, held_out_edges, link_metrics, link_rank, nearest,   # noqa: F401
-                    query)
+from .infer import (LinearProbe, embeddings, full_neighbour, held_out_edges, linear_probe, link_metrics,   # noqa: F401
+                    link_rank, nearest, probe_eval, query)
 from .lr import LRSchedule                                          # noqa: F401
 from .models import GSSupervised, GSUnsupervised                                # noqa: F401
 from .nn_modules import aggregator_lookup, find_sampler, prep_lookup, sampler_extensions, sampler_lookup   # noqa: F401
@@ -31,4 +33,5 @@ from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef, WeightedAdj       
 
 __all__ = ["GSSupervised", "GSUnsupervised", "NodeProblem", "aggregator_lookup", "prep_lookup", "sampler_lookup",
            "set_seeds", "to_numpy", "LRSchedule", "FeatureStore", "DeviceCSR", "RowRef", "ops", "full_neighbour",
-           "embeddings", "query", "nearest", "link_rank", "link_metrics", "held_out_edges", "WeightedAdj", "find_sampler", "sampler_extensions"]
+           "embeddings", "query", "nearest", "link_rank", "link_metrics", "held_out_edges", "LinearProbe", "linear_probe",
+           "probe_eval", "WeightedAdj", "find_sampler", "sampler_extensions"]

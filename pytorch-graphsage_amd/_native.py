@@ -202,6 +202,10 @@ SIGNATURES = {
     "gsage_rank_ip_workspace": (_i64, [_i64, _i64, _i64, ctypes.POINTER(_i64)]),
     "gsage_rank_ip": (_int, [_vp, _int, _i64, _i64, _vp, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _i32, _vp, _i64,
                              _vp, _vp, _vp, _vp]),
+    "gsage_probe_pass_scratch": (_i64, [_i64, _i32, _i32, _i32]),
+    "gsage_probe_loss_index_next": (_int, [_vp]),
+    "gsage_probe_pass": (_int, [_vp, _int, _i64, _i64, _vp, _i64, _vp, _int, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
+                                _vp]),
 }
 
 

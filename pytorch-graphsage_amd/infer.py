@@ -764,3 +764,171 @@ def held_out_edges(adj, train_adj, nodes):
     else:
         stored = torch.zeros_like(src, dtype=torch.bool)
     return src[~stored].contiguous(), dst[~stored].contiguous()
+
+
+# --------------------------------------------------------------------------------------------
+# linear probe over the exported embeddings
+# --------------------------------------------------------------------------------------------
+PROBE_BETAS, PROBE_EPS = (0.9, 0.999), 1e-8
+
+
+class LinearProbe(object):
+    """A linear classifier fitted on frozen embeddings (linear_probe): W fp32 [C, D], b fp32 [C], the loss of every
+    iteration (loss_history fp32 [iters]) and the task it was fitted for."""
+
+    def __init__(self, W, b, loss_history, task):
+        self.W, self.b, self.loss_history, self.task = W, b, loss_history, task
+
+    def logits(self, emb, nodes=None):
+        """emb[nodes] @ W^T + b (every row when nodes is None), fp32, through ops.linear."""
+        x = emb if nodes is None else emb[_pair_ids(nodes, emb.device, "LinearProbe.logits", "node", int(emb.shape[0]))]
+        return ops.linear(x, self.W, self.b)
+
+    def predict(self, emb, nodes=None):
+        """classification: the arg-max class, int64 [n]; multilabel_classification: the labels whose logit is positive,
+        bool [n, C] -- what the F1 metrics of problem.py count."""
+        z = self.logits(emb, nodes)
+        return z.argmax(dim=1) if self.task == "classification" else z > 0
+
+
+def linear_probe(emb, targets, nodes, task, n_classes=None, iters=100, lr=0.1, weight_decay=0.0):
+    """Fit a linear classifier on the rows `nodes` of the frozen embeddings `emb` [N, D] -> LinearProbe: the GraphSAGE
+    paper's judgement of unsupervised embeddings.  targets: one per node of `nodes`, in its order -- int64 class ids
+    [n] for task "classification", float [n, C] in [0, 1] for "multilabel_classification".  n_classes: C (default:
+    the largest class id + 1, or the targets' columns).
+
+    Zero-initialised W, b; `iters` steps of full-batch Adam (betas 0.9 / 0.999, eps 1e-8, `weight_decay` as Adam's
+    L2 term, no clipping).  On CUDA one iteration is ops.probe_pass's kernels (csrc/gsage_probe.hip),
+    gsage_finalize_grads and gsage_clip_adam_step, recorded once as a command list and replayed `iters` times
+    without a host synchronisation; the loss of iteration t lands in loss_history[t], read back by the caller when it
+    wants it.  CPU tensors: the same loop over ops.probe_pass's host definition.  Deterministic: two fits on the same
+    inputs are bit-identical.  Refused with a sentence: regression tasks, C > 128, D > 1024, targets of the wrong
+    dtype or shape, node ids outside the table, class ids outside [0, C)."""
+    ops.probe_task(task)
+    if not torch.is_tensor(emb) or emb.dim() != 2 or not emb.is_floating_point():
+        raise ValueError("linear_probe: emb must be a [N, D] float tensor")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError("linear_probe: iters must be at least 1, not %d" % iters)
+    dev, N, D = emb.device, int(emb.shape[0]), int(emb.shape[1])
+    targets = torch.as_tensor(targets)
+    if n_classes is None:
+        if task == "classification":
+            if targets.is_floating_point() or targets.numel() == 0:
+                raise ValueError("linear_probe: classification targets must be integer class ids, not %s" % targets.dtype)
+            n_classes = int(targets.max()) + 1
+        else:
+            if targets.dim() != 2:
+                raise ValueError("linear_probe: multilabel targets must have shape [n, C], not %s" % (tuple(targets.shape),))
+            n_classes = int(targets.shape[1])
+    C = int(n_classes)
+    ids, y = ops.probe_check(emb, nodes, targets, C, D, task, who="linear_probe")
+    if int(ids.min()) < 0 or int(ids.max()) >= N:
+        raise IndexError("linear_probe: node id out of range of the %d embedding rows" % N)
+    if task == "classification":
+        if int(y.min()) < 0 or int(y.max()) >= C:
+            raise ValueError("linear_probe: class id out of range [0, %d)" % C)
+    elif float(y[:, :C].min()) < 0.0 or float(y[:, :C].max()) > 1.0:
+        raise ValueError("linear_probe: multilabel targets must lie in [0, 1]")
+    f32, total = torch.float32, C * D + C
+    b1, b2 = PROBE_BETAS
+    if not emb.is_cuda:
+        # host mode: the same loop over the float64 definition, torch.optim.Adam's arithmetic in fp32
+        p = torch.zeros(total, dtype=f32)
+        m, v = torch.zeros_like(p), torch.zeros_like(p)
+        hist = torch.zeros(iters, dtype=f32)
+        for t in range(iters):
+            loss, dW, db = ops.probe_pass(emb, ids, y, p[:C * D].view(C, D), p[C * D:], task)
+            g = torch.cat([dW.reshape(-1), db]) + weight_decay * p
+            m = b1 * m + (1 - b1) * g
+            v = b2 * v + (1 - b2) * g * g
+            step = lr / (1 - b1 ** (t + 1))
+            p = p - step * m / (v.sqrt() / (1 - b2 ** (t + 1)) ** 0.5 + PROBE_EPS)
+            hist[t] = loss
+        return LinearProbe(p[:C * D].view(C, D).clone(), p[C * D:].clone(), hist, task)
+
+    fit = ProbeIteration(emb, ids, y, task, C, iters, lr, weight_decay)
+    fit.replay(iters)
+    probe = LinearProbe(fit.flat_p[:C * D].view(C, D), fit.flat_p[C * D:], fit.loss_history, task)
+    probe._fit = fit                                   # the recorded list and its buffers: alive until the replays ran
+    return probe
+
+
+class ProbeIteration(object):
+    """One Adam iteration of the probe on the device -- gsage_probe_pass (two launches), gsage_finalize_grads,
+    gsage_clip_adam_step -- recorded once as a command list; replay(k) issues it k times without a host
+    synchronisation.  Iteration t (counted on the device) writes its loss to loss_history[t], t < capacity.
+    emb, ids, y: as ops.probe_check returns them; the parameters live in flat_p = [W | b], zero-initialised."""
+
+    def __init__(self, emb, ids, y, task, C, capacity, lr, weight_decay):
+        from .engine.common import _ReduceDesc
+        lib, code = nat.lib(), ops.PROBE_TASKS[task]
+        dev, f32 = emb.device, torch.float32
+        N, D = int(emb.shape[0]), int(emb.shape[1])
+        self.E = E = ops.probe_operand(emb, D)
+        self.ids, self.y = ids, y
+        n, total = int(ids.shape[0]), C * D + C
+        floats, S = ops.probe_scratch(n, C, D, 0)
+        self.splits, self.capacity = S, int(capacity)
+        self.flat_p = flat_p = torch.zeros(total, dtype=f32, device=dev)
+        self.flat_g, self.flat_m, self.flat_v = (torch.zeros_like(flat_p) for _ in range(3))
+        self.partial = torch.empty(floats, dtype=f32, device=dev)
+        n_sq = int(lib.gsage_finalize_partials(1, total))
+        self.sq = torch.zeros(max(n_sq, int(lib.gsage_adam_partials(total))), dtype=f32, device=dev)
+        self.step = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.lr_t = torch.tensor([float(lr)], dtype=f32, device=dev)
+        self.loss_history = torch.zeros(self.capacity, dtype=f32, device=dev)
+        desc = _ReduceDesc(self.partial.data_ptr(), total + 1, 0, S, 1, total, total + 1)
+        self.descs = torch.frombuffer(bytearray(bytes(desc)), dtype=torch.uint8).to(dev)
+        self.issued = 0
+        b1, b2 = PROBE_BETAS
+        stream = ops._stream()
+        with nat.CommandList.record() as cl:
+            # the pass reads the step count BEFORE the finalisation ticks it: iteration t writes loss_history[t]
+            nat.check(lib.gsage_probe_loss_index_next(self.step.data_ptr()), "probe_loss_index_next")
+            nat.check(lib.gsage_probe_pass(ops._ptr(E), ops._code(E.dtype), E.stride(0), N, ops._ptr(ids), n, ops._ptr(y),
+                                           code, y.stride(0) if code else 0, flat_p.data_ptr(),
+                                           flat_p[C * D:].data_ptr(), C, D, 0, self.partial.data_ptr(),
+                                           self.loss_history.data_ptr(), stream), "probe_pass")
+            nat.check(lib.gsage_finalize_grads(self.descs.data_ptr(), 1, total, self.flat_g.data_ptr(), self.sq.data_ptr(),
+                                               self.step.data_ptr(), None, 0, None, 0, stream), "finalize_grads")
+            nat.check(lib.gsage_clip_adam_step(flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_m.data_ptr(),
+                                               self.flat_v.data_ptr(), total, self.sq.data_ptr(), self.lr_t.data_ptr(),
+                                               self.step.data_ptr(), b1, b2, PROBE_EPS, float(weight_decay), 3.0e38, None,
+                                               1, n_sq, None, 0, None, 0, None, 0, stream), "clip_adam_step")
+        self.cl = cl
+
+    def replay(self, k=1):
+        if self.issued + k > self.capacity:
+            raise ValueError("ProbeIteration: %d iterations asked of a loss history of %d" % (self.issued + k, self.capacity))
+        stream = ops._stream()
+        for _ in range(k):
+            self.cl.replay(stream)
+        self.issued += k
+
+
+def probe_eval(emb, problem, iters=100, lr=0.1, weight_decay=0.0):
+    """Fit a linear probe on the embeddings of problem.nodes['train'] and score the val and test folds with the
+    problem's F1 metric (on the device for CUDA tensors) ->
+    {"task", "iters", "loss_first", "loss_last", "val": {"micro", "macro"}, "test": {...}}."""
+    from .problem import batch_metric
+    task = problem.task
+    ops.probe_task(task)
+    dev = emb.device
+
+    def fold(name):
+        nodes = np.asarray(problem.nodes[name]).reshape(-1)
+        y = torch.as_tensor(np.asarray(problem.targets[nodes]))
+        y = y.long().view(-1) if task == "classification" else y.float()
+        return torch.as_tensor(nodes).long().to(dev), y.to(dev)
+
+    nodes, y = fold("train")
+    C = int(problem.n_classes)
+    probe = linear_probe(emb, y, nodes, task, n_classes=C, iters=iters, lr=lr, weight_decay=weight_decay)
+    out = {"task": task, "iters": int(iters)}
+    for name in ("val", "test"):
+        nodes, y = fold(name)
+        out[name] = batch_metric(task, y, probe.logits(emb, nodes)) if nodes.numel() else None
+    hist = probe.loss_history.cpu()
+    out["loss_first"], out["loss_last"] = float(hist[0]), float(hist[-1])
+    return out

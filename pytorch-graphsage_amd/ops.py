@@ -1608,3 +1608,128 @@ def rank_ip(table, queries, target_ids, query_ids=None, csr=None, exclude="none"
         csr.err_flag.zero_()
         raise ValueError(RANK_UNSORTED)
     return rank, score
+
+
+# =============================================================================================
+# Linear probe over embeddings: one loss-and-gradient pass of a linear classifier (csrc/gsage_probe.hip)
+# =============================================================================================
+PROBE_TASKS = {"classification": 0, "multilabel_classification": 1}
+PROBE_C_MAX, PROBE_D_MAX = 128, 1024
+
+
+def probe_task(task):
+    """The kernel's code of a probe task; regression has no probe."""
+    if task not in PROBE_TASKS:
+        raise ValueError("probe: a linear probe is a classifier -- the task must be classification or "
+                         "multilabel_classification, not %r" % (task,))
+    return PROBE_TASKS[task]
+
+
+def probe_check(table, ids, targets, C, D, task, who="probe_pass"):
+    """Shape and dtype checks shared by probe_pass and infer.linear_probe -> (ids int64 [n], targets) on the table's
+    device: int64 [n] for classification, fp32 [n, >= C] (unit column stride) for multilabel_classification."""
+    code = probe_task(task)
+    if not torch.is_tensor(table) or table.dim() != 2 or not table.is_floating_point():
+        raise ValueError("%s: the table must be a [N, D] float tensor" % who)
+    if int(table.shape[1]) != D:
+        raise ValueError("%s: the table has %d columns, the classifier D = %d" % (who, int(table.shape[1]), D))
+    if not 1 <= C <= PROBE_C_MAX:
+        raise ValueError("%s: the number of classes must be in [1, %d], not %d (one workgroup holds every class of a row)"
+                         % (who, PROBE_C_MAX, C))
+    if not 1 <= D <= PROBE_D_MAX:
+        raise ValueError("%s: D must be in [1, %d], not %d" % (who, PROBE_D_MAX, D))
+    ids = torch.as_tensor(ids)
+    if ids.is_floating_point() or ids.dtype == torch.bool:
+        raise ValueError("%s: node ids must be integers, not %s" % (who, ids.dtype))
+    ids = ids.to(table.device).long().contiguous().view(-1)
+    n = int(ids.shape[0])
+    if n < 1:
+        raise ValueError("%s: no rows to fit on" % who)
+    targets = torch.as_tensor(targets).to(table.device)
+    if code == 0:
+        if targets.is_floating_point() or targets.dtype == torch.bool:
+            raise ValueError("%s: classification targets must be integer class ids, not %s" % (who, targets.dtype))
+        if targets.numel() != n or targets.dim() > 2 or (targets.dim() == 2 and int(targets.shape[1]) != 1):
+            raise ValueError("%s: classification targets must have shape [%d] (one class id per row), not %s"
+                             % (who, n, tuple(targets.shape)))
+        targets = targets.long().contiguous().view(-1)
+    else:
+        if not targets.is_floating_point():
+            raise ValueError("%s: multilabel targets must be floating point (values in [0, 1]), not %s" % (who, targets.dtype))
+        if targets.dim() != 2 or int(targets.shape[0]) != n or int(targets.shape[1]) < C:
+            raise ValueError("%s: multilabel targets must have shape [%d, %d], not %s" % (who, n, C, tuple(targets.shape)))
+        if targets.dtype != torch.float32 or targets.stride(1) != 1 or targets.stride(0) < C:
+            targets = targets.float().contiguous()
+    return ids, targets
+
+
+def probe_scratch(n, C, D, splits=0):
+    """(floats of gsage_probe_pass's partial buffer, its rows S) -- host arithmetic."""
+    floats = int(nat.lib().gsage_probe_pass_scratch(int(n), int(C), int(D), int(splits)))
+    if floats < 0:
+        raise ValueError("probe_pass: n = %d, C = %d, D = %d, splits = %d are outside the kernel's limits "
+                         "(C <= %d, D <= %d, n < 2^31, 0 <= splits <= 1024)" % (n, C, D, splits, PROBE_C_MAX, PROBE_D_MAX))
+    return floats, floats // (C * D + C + 1)
+
+
+def probe_operand(table, D):
+    """The table as the compute mode sees it (fp32 data is rounded to bf16 once in the bf16 mode)."""
+    cdt = torch_dtype()
+    t = table.detach()
+    return t if t.dtype == cdt and t.stride(1) == 1 and t.stride(0) >= D else t.to(cdt).contiguous()
+
+
+def _probe_pass_host(table, ids, targets, W, b, code):
+    """The definition in float64 torch (host mode): operands rounded as the compute mode sees them."""
+    dt = torch_dtype()
+    C, D = int(W.shape[0]), int(W.shape[1])
+    X = table.detach()[ids].to(dt).double()
+    z = X @ W.detach().to(dt).double().t() + b.detach().double()
+    n = int(ids.shape[0])
+    if code == 0:
+        lse = torch.logsumexp(z, dim=1)
+        loss = (lse - z.gather(1, targets.view(-1, 1)).view(-1)).mean()
+        G = torch.softmax(z, dim=1)
+        G[torch.arange(n), targets] -= 1.0
+    else:
+        y = targets[:, :C].double()
+        loss = ((F.softplus(z) - y * z).sum(dim=1) / C).mean()
+        G = (torch.sigmoid(z) - y) / C
+    return loss.float(), (G.t() @ X / n).float(), (G.sum(dim=0) / n).float()
+
+
+def probe_pass(table, ids, targets, W, b, task, splits=0):
+    """One full-batch loss-and-gradient evaluation of the linear classifier z = table[ids] @ W~^T + b ->
+    (loss fp32 scalar, dW fp32 [C, D], db fp32 [C]); include/gsage.h, "Linear probe over embeddings".
+    task: "classification" (targets int64 [n], F.cross_entropy) or "multilabel_classification" (targets float
+    [n, >= C], F.multilabel_soft_margin_loss).  W [C, D], b [C]: fp32 masters.  Operands are taken in
+    ops.config.compute_dtype (fp32 data is rounded to bf16 once in the bf16 mode, W when it is staged).
+
+    CUDA: gsage_probe_pass + gsage_finalize_grads (three launches); `splits` = partial rows (0 = chosen by the
+    library), bit-identical from call to call.  CPU: the same definition in float64 torch."""
+    if not (torch.is_tensor(W) and W.dim() == 2 and W.dtype == torch.float32 and torch.is_tensor(b)
+            and b.dtype == torch.float32 and tuple(b.shape) == (int(W.shape[0]),)):
+        raise ValueError("probe_pass: W must be fp32 [C, D] and b fp32 [C]")
+    C, D = int(W.shape[0]), int(W.shape[1])
+    code = probe_task(task)
+    ids, targets = probe_check(table, ids, targets, C, D, task)
+    if not table.is_cuda:
+        return _probe_pass_host(table, ids, targets, W, b, code)
+    from .engine.common import _ReduceDesc
+    dev, f32 = table.device, torch.float32
+    E = probe_operand(table, D)
+    n, width = int(ids.shape[0]), C * D + C + 1
+    floats, S = probe_scratch(n, C, D, splits)
+    Wc, bc = W.detach().contiguous(), b.detach().contiguous()
+    partial = torch.empty(floats, dtype=f32, device=dev)
+    loss = torch.zeros(1, dtype=f32, device=dev)
+    nat.check(nat.lib().gsage_probe_pass(_ptr(E), _code(E.dtype), E.stride(0), int(E.shape[0]), _ptr(ids), n,
+                                         _ptr(targets), code, targets.stride(0) if code else 0, _ptr(Wc), _ptr(bc), C, D,
+                                         int(splits), _ptr(partial), _ptr(loss), _stream()), "probe_pass")
+    desc = _ReduceDesc(partial.data_ptr(), width, 0, S, 1, width - 1, width)
+    descs = torch.frombuffer(bytearray(bytes(desc)), dtype=torch.uint8).to(dev)
+    flat = torch.empty(width - 1, dtype=f32, device=dev)
+    sq = torch.empty(nat.lib().gsage_finalize_partials(1, width - 1), dtype=f32, device=dev)
+    nat.check(nat.lib().gsage_finalize_grads(_ptr(descs), 1, width - 1, _ptr(flat), _ptr(sq), None, None, 0, None, 0,
+                                             _stream()), "finalize_grads")
+    return loss[0], flat[:C * D].view(C, D), flat[C * D:]

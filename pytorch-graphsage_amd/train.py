@@ -53,6 +53,17 @@ Retrieval over the embeddings (infer.nearest, opt-in):
                           with --show-test a second one for the test fold.  The embeddings come from the EVALUATION
                           graph: the held-out edge takes part in message passing, as in GraphSAGE's inductive protocol;
                           call gs.link_rank on embeddings of your own for anything else.  Sparse problems, one process.
+  --probe                 after training (sharing the one embedding pass with --save-embeddings / --link-eval): the
+                          GraphSAGE paper's judgement of the embeddings.  A linear classifier is fitted on the frozen
+                          embeddings of the train fold (gs.linear_probe: zero start, full-batch Adam, every iteration a
+                          fused loss / gradient pass of csrc/gsage_probe.hip) and scored on the validation fold with the
+                          problem's F1 metric; one line {"probe": {"fold": "val", "task", "micro", "macro", "loss_first",
+                          "loss_last"}} is printed, with --show-test a second one for the test fold.  Classification
+                          and multilabel problems, with and without --unsupervised; a regression problem exits with
+                          one sentence.
+  --probe-iters N         Adam iterations (default 100)     --probe-lr F   learning rate (default 0.1)
+  --probe-l2 F            Adam's L2 term (default 0).  The defaults reach the toy results of the tests; nobody has
+                          tuned them on a real graph.
   --link-eval-edges M     at most M edges per fold (default 100000), a subsample seeded by --seed when there are more
   --link-eval-ks 1,10,50  the k of hits@k
   --neighbours-k K        how many (default 10, at most 128)
@@ -181,8 +192,22 @@ def link_eval(model, problem, args, emb):
         sys.stdout.flush()
 
 
+def probe_eval(problem, args, emb):
+    """--probe: micro / macro F1 of a linear classifier fitted on the train fold's rows of `emb` (gs.probe_eval), one
+    JSON line for the validation fold and, with --show-test, one for the test fold."""
+    try:
+        res = gs.probe_eval(emb, problem, iters=args.probe_iters, lr=args.probe_lr, weight_decay=args.probe_l2)
+    except (ValueError, IndexError) as e:
+        raise SystemExit('gsage: --probe: %s' % e)
+    for fold in (['val', 'test'] if args.show_test else ['val']):
+        f1 = res[fold] or {"micro": None, "macro": None}
+        print(dumps({"probe": {"fold": fold, "task": res["task"], "micro": f1["micro"], "macro": f1["macro"],
+                               "loss_first": res["loss_first"], "loss_last": res["loss_last"]}}))
+        sys.stdout.flush()
+
+
 def export(model, problem, args):
-    """--save-embeddings, --save-neighbours and --link-eval after training: one embedding pass serves all three."""
+    """--save-embeddings, --save-neighbours, --link-eval and --probe after training: one embedding pass serves all."""
     emb = None
     if args.save_embeddings:
         if args.embed_nodes:
@@ -203,8 +228,12 @@ def export(model, problem, args):
             raise SystemExit('gsage: --save-neighbours: %s' % e)
         with open(args.save_neighbours, 'wb') as f:
             np.savez(f, ids=ids.cpu().numpy(), scores=scores.cpu().numpy())
+    if args.link_eval or args.probe:
+        emb = emb if emb is not None else gs.embeddings(model, problem.feats)
     if args.link_eval:
-        link_eval(model, problem, args, emb if emb is not None else gs.embeddings(model, problem.feats))
+        link_eval(model, problem, args, emb)
+    if args.probe:
+        probe_eval(problem, args, emb)
 
 
 class FusedEvaluator(object):
@@ -313,6 +342,10 @@ def parse_args(argv=None):
     parser.add_argument('--link-eval', action="store_true")
     parser.add_argument('--link-eval-edges', type=int, default=100000)
     parser.add_argument('--link-eval-ks', type=str, default='1,10,50')
+    parser.add_argument('--probe', action="store_true")
+    parser.add_argument('--probe-iters', type=int, default=100)
+    parser.add_argument('--probe-lr', type=float, default=0.1)
+    parser.add_argument('--probe-l2', type=float, default=0.0)
     parser.add_argument('--unsupervised', action="store_true")
     parser.add_argument('--walk-len', type=int, default=5)
     parser.add_argument('--n-negatives', type=int, default=20)
@@ -375,6 +408,8 @@ def main(argv=None, problem=None):
             raise SystemExit('gsage: --link-eval-edges must be >= 1 and --link-eval-ks a comma-separated list of k >= 1')
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("GSAGE_FORCE_DDP", "0") == "1":
             raise SystemExit('gsage: --link-eval: data-parallel launches are not supported (run a single process)')
+    if args.probe and (args.probe_iters < 1 or not args.probe_lr > 0 or args.probe_l2 < 0):
+        raise SystemExit('gsage: --probe-iters must be >= 1, --probe-lr > 0 and --probe-l2 >= 0')
     set_seeds(args.seed)
     gs.ops.set_compute_dtype(args.precision)
     gs.nn_modules.SparseUniformNeighborSampler.rng_default = args.rng
@@ -388,6 +423,8 @@ def main(argv=None, problem=None):
     ddp = gs.dist.init_from_env(args.cuda)            # no-op outside torch.distributed.run
     if problem is None:
         problem = NodeProblem(problem_path=args.problem_path, cuda=args.cuda)
+    if args.probe and problem.task not in gs.ops.PROBE_TASKS:
+        raise SystemExit('gsage: --probe: a linear probe is a classifier; this problem\'s task is %s' % problem.task)
     if args.link_eval and not gs.problem._is_sparse(problem.adj):
         raise SystemExit('gsage: --link-eval: a dense problem file holds neighbour samples, not edges to hold out')
     weighted = args.sampler_class == 'sparse_weighted_neighbor_sampler'
@@ -413,18 +450,18 @@ def main(argv=None, problem=None):
     if args.unsupervised:
         if args.full_neighbour_eval:
             raise SystemExit('gsage: --unsupervised: --full-neighbour-eval scores logits; there are none')
-        if args.save_embeddings or args.save_neighbours or args.link_eval:
+        if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
             try:
                 gs.infer.check_supported(model)
             except ValueError as e:
-                raise SystemExit('gsage: --save-embeddings / --save-neighbours / --link-eval: %s' % e)
+                raise SystemExit('gsage: --save-embeddings / --save-neighbours / --link-eval / --probe: %s' % e)
         set_seeds(args.seed ** 2)
         return train_unsupervised(args, problem, model)
-    if args.full_neighbour_eval or args.save_embeddings or args.save_neighbours or args.link_eval:
+    if args.full_neighbour_eval or args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
         try:
             gs.infer.check_supported(model, model.val_sampler.csr('cpu') if weighted else None)
         except ValueError as e:
-            raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings / --save-neighbours / --link-eval: %s' % e)
+            raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings / --save-neighbours / --link-eval / --probe: %s' % e)
     evaluate_fn = (lambda mode: full_neighbour_evaluate(model, problem, mode=mode, closure=args.eval_closure)) \
         if args.full_neighbour_eval else \
         (lambda mode: evaluate(model, problem, mode=mode))
@@ -464,7 +501,7 @@ def main(argv=None, problem=None):
         sys.stdout.flush()
         if args.show_test:
             print(dumps({"test_f1": evaluate_fn('test')}))
-        if args.save_embeddings or args.save_neighbours or args.link_eval:
+        if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
             export(model, problem, args)
     if ddp is not None:
         ddp.close()
@@ -521,7 +558,7 @@ def train_unsupervised(args, problem, model):
     sys.stdout.flush()
     if eng is not None:
         eng.close()
-    if args.save_embeddings or args.save_neighbours or args.link_eval:
+    if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
         export(model, problem, args)
 
 
@@ -719,7 +756,7 @@ def train_fused(args, problem, model, ddp, start_time, cls):
         sys.stdout.flush()
         if args.show_test:
             print(dumps({"test_f1": test_metric}))
-        if args.save_embeddings or args.save_neighbours or args.link_eval:
+        if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
             export(model, problem, args)
     if ddp is not None:
         ddp.close()
