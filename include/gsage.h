@@ -464,7 +464,8 @@ int gsage_wgrad_ticks_next(int64_t *tick, int64_t *tick1, int64_t inc1, int64_t 
  *
  *     pooled[i, j] = pool_{r in [0,n)} relu( sum_k A[i*n+r, k] * W[j,k] + bias[j] )
  *     A rows are gathered through a_rows when given (A row = A + a_rows[i*n+r]*lda).
- *     argmax (int32 [M, H], may be NULL; max pool only) receives the winning r for backward.
+ *     argmax (int32 [M, H], may be NULL; max pool only) receives the winning r for backward: the FIRST
+ *     maximum of the segment (as torch.max / np.argmax; row 0 when every ReLU'd value is 0).
  *     The [M*n, H] hidden activations are never written to HBM.
  * ---------------------------------------------------------------------------------------- */
 int gsage_pool_mlp(const void *A, int dtype, int64_t lda, const int64_t *a_rows, const void *W,
@@ -485,25 +486,38 @@ int gsage_pool_mlp_packed(const void *A, int64_t lda, const int64_t *a_rows, con
                           float *pooled, int64_t pooled_ld, int32_t *argmax, void *pooled_bf16,
                           int64_t pooled_bf16_ld, uint32_t *relu_mask, void *stream);
 
-/* Backward routing of the max pool: the bf16 [M*n, ldo] gradient of the hidden activations,
- *     out[i*n + j, c] = (argmax[i, c] == j && pooled[i, c] > 0) ? g[i, c] : 0
+/* Backward routing of the max pool: the [M*n, ldo] gradient of the hidden activations, bf16 or fp32 (out_dtype),
+ *     out[i*n + j, c] = (argmax[i, c] == j && pooled[i, c] > 0) ? T(g[i, c]) : +0
  * (autograd of nn_modules.py:224-226,240: max picks one row per (segment, channel), ReLU passes
- * positive maxima only) -- the dC operand of gsage_wgrad for the MLP's weight gradient.
- * H, ldo % 8 == 0. */
+ * positive maxima only) -- the dC operand of gsage_wgrad for the MLP's weight gradient.  Selects, not
+ * products: a closed gate (pooled +0, -0, negative or NaN) gives all-zero bits whatever g holds, an open
+ * one g's bf16 rounding (fp32: g's own bits).  An argmax outside [0, n) routes nothing: its column is
+ * zero in all n rows of the segment.  Every element of rows [0, M*n) x columns [0, H) is written.
+ * bf16: H, ldo % 8 == 0;  fp32: H, ldo % 4 == 0;  out 16-byte aligned; ldg, ldp, lda >= H (any
+ * alignment: 16-byte loads when all three are multiples of 4 and the pointers 16-byte aligned, else
+ * 4-byte loads, the same bits).  M == 0 launches nothing. */
 int gsage_pool_route_bwd(const float *g, int64_t ldg, const float *pooled, int64_t ldp,
                          const int32_t *argmax, int64_t lda, int64_t M, int32_t n, int32_t H, void *out,
                          int out_dtype, int64_t ldo, void *stream);
 
-/* Same for the mean pool: out[i*n + j, c] = relu_mask(i*n + j, c) ? g[i, c] / n : 0   (autograd of
- * nn_modules.py:224-226,252), plus -- when bias_part != NULL -- the MLP bias gradient as n_part
- * deterministic partial rows (summed by gsage_finalize_grads).  H % 32 == 0. */
+/* Same for the mean pool: out[i*n + j, c] = relu_mask(i*n + j, c) ? T(g[i, c] * fl(1 / n)) : +0   (autograd
+ * of nn_modules.py:224-226,252; relu_mask as K3 writes it, [M*n, H/32] words).  The quotient is the
+ * product with the ROUNDED fp32 reciprocal -- two roundings, within 2^-23 of g / n, exact for n a power of
+ * two -- not a division.  Plus -- when bias_part != NULL -- the MLP bias gradient as n_part deterministic
+ * partial rows [n_part, H] (a second launch; summed by gsage_finalize_grads): row b holds
+ * (sum over segments i = b, b + n_part, ... of g[i, c] * cnt(i, c)) / n, cnt = the segment's set bits
+ * at c, a segment without a set bit contributing nothing whatever g holds; rows no segment feeds
+ * (n_part > M) are written as zeros.  H % 32 == 0, ldo % 8 == 0 (both output types), out 16-byte
+ * aligned, 1 <= n_part <= 1024. */
 int gsage_pool_route_mean_bwd(const float *g, int64_t ldg, const uint32_t *relu_mask, int64_t M, int32_t n,
                               int32_t H, void *out, int out_dtype, int64_t ldo, float *bias_part, int32_t n_part,
                               void *stream);
 
 /* Bias gradient of the pooling MLP under the max pool: column sums of g * (pooled > 0) over the M
  * segments, as `n_part` deterministic partial rows part[b, c] (b < n_part; summed by
- * gsage_finalize_grads with S = n_part, stride = H).  n_part <= 1024. */
+ * gsage_finalize_grads with S = n_part, stride = H): row b sums the segments b, b + n_part, ...
+ * in that order, rows no segment feeds are zeros.  A select: g behind a closed gate (+0, -0, negative,
+ * NaN) adds nothing.  n_part <= 1024; H, ldg, ldp % 4 == 0; g, pooled, part 16-byte aligned. */
 int gsage_pool_bias_partials(const float *g, int64_t ldg, const float *pooled, int64_t ldp, int64_t M,
                              int32_t H, float *part, int32_t n_part, void *stream);
 
@@ -511,7 +525,13 @@ int gsage_pool_bias_partials(const float *g, int64_t ldg, const float *pooled, i
  * w.r.t. the previous level's post-ReLU output Hprev [R, ldh] bf16):
  *     dH[m, c] = (Hprev[m, c] > 0) * ( (m < r_x ? DX[m, c] : 0) + (m >= r0 ? DN[m - r0, c] : 0) )
  * DX fp32 [r_x, ldx] = gradient through fc_x of the rows that were "x", DN fp32 [R - r0, ldn] =
- * gradient through the pooling MLP of the rows that were neighbours.  D % 4 == 0. */
+ * gradient through the pooling MLP of the rows that were neighbours.  One IEEE fp32 addition where both
+ * apply (a row with DX alone keeps DX's bits, a row with DN alone holds 0 + DN, a row with neither --
+ * r_x <= m < r0 -- is written as zeros), then the gate (a select: Hprev +0, -0, negative or NaN gives
+ * +0), then the rounding to bf16 when dtype is GSAGE_BF16 (Hprev and dH share dtype).  D and the four
+ * leading dimensions % 4 == 0; 0 <= r_x, r0 <= R.  The kernel moves four columns per load and store:
+ * DX and DN must be 16-byte aligned, Hprev and dH 16-byte aligned in fp32 and 8-byte aligned in bf16
+ * (the caller's obligation: the entry point checks the leading dimensions, not the pointers). */
 int gsage_pool_merge_bwd(const void *Hprev, int dtype, int64_t ldh, const float *DX, int64_t ldx, int64_t r_x,
                          const float *DN, int64_t ldn, int64_t r0, void *dH, int64_t ldo, int64_t R,
                          int32_t D, void *stream);

@@ -853,7 +853,7 @@ k_pool_bias_partials_mean(const float *__restrict__ g, int64_t ldg, const uint32
     for (int64_t i = blockIdx.x; i < M; i += gridDim.x) {
         int cnt = 0;
         for (int j = 0; j < n; ++j) cnt += (mask[(i * n + j) * words + (c >> 5)] >> (c & 31)) & 1u;
-        s += g[i * ldg + c] * (float)cnt;
+        if (cnt) s += g[i * ldg + c] * (float)cnt;      // (a select, like the route: no active row, no NaN * 0)
     }
     part[(int64_t)blockIdx.x * H + c] = s / (float)n;
 }
