@@ -707,6 +707,32 @@ int gsage_head_ce(const float *E, int64_t lde, const float *W, const float *bias
                   const int64_t *batch_idx, int64_t n_batches, void *stream);
 int64_t gsage_head_ce_scratch(int32_t B, int32_t C, int32_t D);
 
+/* The head for a WIDE class dimension, forward + backward in one launch (csrc/gsage_head_wide.hip), the three
+ * products as exact fp32 MFMAs:
+ *
+ *     z = E / max(||E||_2, 1e-12);  preds = z W^T + bias                                       (fp32 [B, C])
+ *     task 0 (targets int64 [B]):            l_i = logsumexp(preds_i) - preds_i[y_i]              F.cross_entropy
+ *     task 1 (targets fp32 [B, ldy >= C]):   l_i = (1/C) sum_c softplus(preds_ic) - y_ic preds_ic
+ *                                                                               F.multilabel_soft_margin_loss
+ *     loss = (1/Bv) sum_{i < Bv} l_i;  dE (bf16 or fp32, [B, ldd]), dW [C, D], db [C] = its gradients.
+ *
+ * Limits (GSAGE_EINVAL before any launch, also without a GPU): 1 <= C <= 128, 1 <= D <= 1024, lde, ldd >= D,
+ * ldy >= C, task 0 or 1.  Bv: the live rows announced by gsage_head_n_valid_next (consumed by this call on every
+ * return path, clamped to [1, B]; B without it); rows Bv .. B-1 get predictions, no loss term, and explicit zeros in
+ * dE.  batch_idx (may be NULL): targets is a queue [n_batches, B] (task 1: [n_batches, B, ldy]) and n_valid an array
+ * [n_batches]; batch *batch_idx % n_batches is used.
+ * scratch: fp32, gsage_head_wide_scratch(B, C, D) floats (-1 outside the limits) = one partial row
+ * [dW | db | sum of l_i] of C*D + C + 1 floats per 16 rows of the batch -- gsage_head_ce's convention: with dW == NULL
+ * (and db == NULL) the rows are left for gsage_finalize_grads (one gsage_reduce_desc, stride = ld = C*D + C + 1,
+ * cols = C*D + C); otherwise a second launch sums them in buffer order into dW, db and, when not NULL, loss.
+ * targets == NULL and dE == NULL: forward only -- preds is written, scratch and dE are not touched.
+ * No atomics: for fixed (B, C, D) the result is bit-identical from launch to launch. */
+int gsage_head_wide(const float *E, int64_t lde, const float *W, const float *bias, const void *targets, int task,
+                    int64_t ldy, int32_t B, int32_t C, int32_t D, float *preds, void *dE, int dE_dtype, int64_t ldd,
+                    float *dW, float *db, float *loss, float *scratch, const int64_t *batch_idx, int64_t n_batches,
+                    void *stream);
+int64_t gsage_head_wide_scratch(int32_t B, int32_t C, int32_t D);
+
 /* The whole seed level of a mean-aggregator model in one launch: segment mean of the n sampled
  * neighbours (nn_modules.py:197-198), emb = cat[fc_x(x), fc_neib(agg)] (:200-202, identity
  * activation), the classification head above (models.py:90-91, problem.py:34) and the backward down
@@ -856,6 +882,9 @@ int gsage_gather_adam_capacity(int dtype, int64_t lds_bytes);
  * an epoch into near-equal chunks that are never all of one size, while a recorded step has one geometry -- short
  * chunks are padded to it.  NULL (the default): every row is live. */
 int gsage_head_n_valid_next(const int32_t *n_valid);
+/* 1 while a count announced by gsage_head_n_valid_next waits for the calling thread's next head launch, else 0 (a peek:
+ * nothing is consumed).  Every head entry point takes the count before its first return path, refusals included. */
+int gsage_head_n_valid_pending(void);
 
 /* gsage_gather_mean_multi (the NEXT batch's level-0 gathers: they read features and ids only) with up
  * to two short latency-bound jobs riding in the same launch, each a few hundred workgroups that are

@@ -82,6 +82,7 @@ SIGNATURES = {
     "gsage_mt_jump_table_words": (_i64, []),
     "gsage_mt_jump_host": (_int, [_vp, _vp, _vp]),
     "gsage_head_n_valid_next": (_int, [_vp]),
+    "gsage_head_n_valid_pending": (_int, []),
     "gsage_gather_role_next": (_int, [_vp]),
     "gsage_hops_role_next": (_int, [_vp]),
     "gsage_gather_mean": (_int, [_vp, _int, _i64, _vp, _i64, _i32, _i64, _vp, _int, _i64, _vp]),
@@ -112,6 +113,9 @@ SIGNATURES = {
     "gsage_head_ce": (_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _int, _i64, _vp, _vp,
                              _vp, _vp, _vp, _i64, _vp]),
     "gsage_head_ce_scratch": (_i64, [_i32, _i32, _i32]),
+    "gsage_head_wide": (_int, [_vp, _i64, _vp, _vp, _vp, _int, _i64, _i32, _i32, _i32, _vp, _vp, _int, _i64, _vp, _vp,
+                               _vp, _vp, _vp, _i64, _vp]),
+    "gsage_head_wide_scratch": (_i64, [_i32, _i32, _i32]),
     "gsage_mean_tail_ce": (_int, [_vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "gsage_mean_tail_ce_scratch": (_i64, [_i32, _i32]),

@@ -46,6 +46,9 @@ int gsage_head_n_valid_next(const int32_t *n_valid)
     t_head_n_valid = n_valid;
     return GSAGE_OK;
 }
+
+int gsage_head_n_valid_pending(void) { return t_head_n_valid != nullptr; }
+
 int gsage_gather_role_next(const gsage_tail_gather_desc *gather)
 {
     t_gather_role = gather;

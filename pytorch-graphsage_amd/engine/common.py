@@ -46,6 +46,7 @@ _Wgrad = collections.namedtuple("_Wgrad", "dC A lda a_gstride M Ntot K n_per_gro
 
 
 # what every engine without an FP8 form says of an FP8 store (train.py --engine auto then takes the module path)
+_WIDE_DDP_REFUSAL = "wide_head=True under a data-parallel handle is not supported (the wide head runs in one process)"
 _FP8_REFUSAL = ("an FP8 feature table, which this engine's kernels do not decode (the module path reads it through "
                 "the FP8 gather kernels)")
 
@@ -89,17 +90,26 @@ class FusedTrainStep(object):
         return cls.why_not(model, feats, ddp) is None
 
     @classmethod
-    def head_why_not(cls, model, loss_fn, example_targets, batch, padded, world=1):
+    def head_why_not(cls, model, loss_fn, example_targets, batch, padded, world=1, wide=False):
         """What the head of (model, loss_fn) costs a caller BEFORE an engine is built (train.py decides between the
         engine and the module path with it): None when a fused head applies (cross-entropy with <= 64 classes and an
         fc input of <= 1024, or the L1 regression head with <= 2048 seeds), else a sentence.  Without a fused head an
         engine still trains (stock torch ops for the head inside the captured step) but cannot ignore padded seeds:
-        `padded` says whether the caller will pad short batches (the reference's array_split chunks)."""
+        `padded` says whether the caller will pad short batches (the reference's array_split chunks).
+        wide=True (the engine's wide_head=True): gsage_head_wide also fuses the multilabel soft-margin head with
+        2 <= C <= 128 outputs and cross-entropy with 64 < C <= 128 classes (fc input <= 1024); a problem of one of
+        these two kinds beyond those limits gets a sentence naming the limit.  One process only."""
         from ..problem import ProblemLosses
         C, D2 = model.fc.weight.shape
         post = _split_activation(list(model.agg_layers.children())[-1].activation)[1]
         probe = torch.linspace(-2.0, 2.0, 12).view(3, 4)          # (no draw from torch's generator: the run's own)
         ident = post is None or torch.equal(post(probe), probe)
+        if wide:
+            if world > 1:
+                return _WIDE_DDP_REFUSAL
+            kind, why = cls._wide_head_case(loss_fn, int(C), int(D2), ident, example_targets.dtype)
+            if kind is not None:
+                return why                                         # (None: gsage_head_wide applies)
         if loss_fn is ProblemLosses.classification and ident and C <= 64 and D2 <= 1024 and \
                 example_targets.dtype == torch.int64:
             return None
@@ -113,6 +123,27 @@ class FusedTrainStep(object):
             return None
         return ("the head of this problem (loss %s, %d outputs) has no fused kernel, and only a fused head can "
                 "ignore the padding of the reference's unequal chunks" % (getattr(loss_fn, "__name__", "?"), int(C)))
+
+    @staticmethod
+    def _wide_head_case(loss_fn, C, D2, ident, target_dtype):
+        """Is (loss, C, fc input) a case of gsage_head_wide?  -> (None, None): not its kind of problem (the other
+        heads decide); (task code, None): it applies; (task code, sentence): its kind, beyond the named limit."""
+        from ..problem import ProblemLosses
+        if loss_fn is ProblemLosses.multilabel_classification and target_dtype == torch.float32:
+            task, lo = ops.PROBE_TASKS["multilabel_classification"], 2
+        elif loss_fn is ProblemLosses.classification and target_dtype == torch.int64 and C > 64:
+            task, lo = ops.PROBE_TASKS["classification"], 65
+        else:
+            return None, None
+        if not ident:
+            return task, "the wide head needs an identity post-activation on the last layer"
+        if not lo <= C <= ops.WIDE_HEAD_C_MAX:
+            return task, ("the wide head (gsage_head_wide) covers %d to %d outputs, this problem has %d"
+                          % (lo, ops.WIDE_HEAD_C_MAX, C))
+        if D2 > ops.WIDE_HEAD_D_MAX:
+            return task, ("the wide head (gsage_head_wide) covers an fc input of at most %d columns, this model's has %d"
+                          % (ops.WIDE_HEAD_D_MAX, D2))
+        return task, None
 
     @staticmethod
     def _why_not_common(model, feats, agg_types, what):
@@ -178,9 +209,13 @@ class FusedTrainStep(object):
         return None
 
     def __init__(self, model, feats, loss_fn, example_ids, example_targets, ddp=None, capture=True,
-                 warmup=2, pipelined=False, eval_only=False):
+                 warmup=2, pipelined=False, eval_only=False, wide_head=False):
         """capture: "cmdlist" (or True) / "graph" / False; pipelined: two batches in flight on two streams (Philox
-        sampler only); eval_only: the forward launches over the validation sampler (evaluate_fold)."""
+        sampler only); eval_only: the forward launches over the validation sampler (evaluate_fold); wide_head: opt in
+        to gsage_head_wide for the multilabel head and for cross-entropy with 64 < C <= 128 (head_why_not, wide=True)."""
+        self._wide_req = bool(wide_head)
+        if self._wide_req and ddp is not None:
+            raise ValueError("%s: %s" % (type(self).__name__, _WIDE_DDP_REFUSAL))
         if not type(self).supports(model, feats, ddp):
             raise ValueError("%s does not cover this (model, feature store): %s"
                              % (type(self).__name__, type(self).why_not(model, feats, ddp)))
@@ -376,6 +411,18 @@ class FusedTrainStep(object):
             self.head_scratch = torch.zeros(n_scr, dtype=torch.float32, device=dev)
             self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
             self.preds = torch.zeros(B, C, dtype=torch.float32, device=dev)
+        # opt-in: the multilabel head, and cross-entropy past gsage_head_ce's 64 classes, on gsage_head_wide
+        self.fused_wide, self.wide_task = False, None
+        if getattr(self, "_wide_req", False) and not self.fused_head:
+            probe = torch.linspace(-2.0, 2.0, 12, device=dev).view(3, 4)
+            ident = self.post is None or torch.equal(self.post(probe), probe)
+            task, why = self._wide_head_case(loss_fn, int(C), int(D2), ident, example_targets.dtype)
+            shaped = example_targets.numel() == (B * C if task == 1 else B)
+            if task is not None and why is None and shaped:
+                self.fused_wide, self.wide_task = True, task
+                self.preds = torch.zeros(B, C, dtype=torch.float32, device=dev)
+                if not self.eval_only:                  # (evaluation launches the forward-only form: no scratch)
+                    self.head_scratch = torch.zeros(ops.wide_head_scratch(B, C, D2)[0], dtype=torch.float32, device=dev)
         # the regression head of the Pokec problem (F.l1_loss with the reference's [B,1]-vs-[B] broadcast) as one kernel
         from ..problem import ProblemLosses
         probe = torch.randn(3, 4, device=self.dev)
@@ -398,12 +445,12 @@ class FusedTrainStep(object):
         if self.fused_l1:
             self.l1_scratch = torch.zeros(nat.lib().gsage_head_l1_scratch(self.B, D2c), dtype=torch.float32,
                                           device=self.dev)
-        elif not self.fused_head:
+        elif not (self.fused_head or self.fused_wide):
             self.head_stage = torch.zeros(Cc * D2c + Cc, dtype=torch.float32, device=self.dev)
 
     def _head_recordable(self):
         """can the head's launches sit in a native command list?  (the stock-torch head cannot)"""
-        return bool(self.fused_head or self.fused_l1)
+        return bool(self.fused_head or self.fused_l1 or self.fused_wide)
 
     def _head_reduce_descs(self):
         """The head's gradient sources for the finalisation (fc.weight and fc.bias: one descriptor)."""
@@ -411,7 +458,7 @@ class FusedTrainStep(object):
         Cc, D2c = model.fc.weight.shape
         ifc = self.pidx[id(model.fc.weight)]
         assert self.pidx[id(model.fc.bias)] == ifc + 1
-        if self.fused_head:
+        if self.fused_head or self.fused_wide:            # (gsage_head_wide writes gsage_head_ce's partial rows)
             width = Cc * D2c + Cc + 1
             rdesc.append(_ReduceDesc(self.head_scratch.data_ptr(), width, self.poff[ifc],
                                      self.head_scratch.numel() // width, 1, Cc * D2c + Cc, width))
@@ -829,7 +876,7 @@ class FusedTrainStep(object):
             assert self.n_rdesc is not None, "asked before _install_reduce(): the kept answer would not be the table's"
             mode = os.environ.get("GSAGE_FOLD_FINALIZE", "0")
             ok = (mode in ("1", "all") and (self.MEAN_ENGINE or mode == "all") and self.ddp is None and not self.emb
-                  and (self.fused_head or self.fused_l1) and self.n_rdesc <= 16
+                  and (self.fused_head or self.fused_l1 or self.fused_wide) and self.n_rdesc <= 16
                   and self._rdesc_max_S <= 32 and self._meet_fits())
             self._fold = bool(ok)
         return self._fold
@@ -910,12 +957,39 @@ class FusedTrainStep(object):
                                           self.dc[L - 1].data_ptr(), self.code, self.dc[L - 1].stride(0),
                                           self.l1_scratch.data_ptr(), ops._stream()), "head_l1")
 
+    def _stage_head_wide(self, s):
+        """normalize + fc + multilabel soft-margin loss (or cross-entropy over 65..128 classes) + their gradients in
+        one launch (gsage_head_wide): predictions, d loss / d embedding into dc[L-1], one partial row
+        [dW | db | loss] per 16 seeds for the finalisation.  eval_only: its forward-only form (no targets)."""
+        m, L, B = self.model, self.L, self.B
+        C, D2 = m.fc.weight.shape
+        E = self.hout[L - 1]
+        lib = nat.lib()
+        if self.eval_only:
+            nat.check(lib.gsage_head_wide(E.data_ptr(), E.stride(0), m.fc.weight.data_ptr(), m.fc.bias.data_ptr(), None,
+                                          self.wide_task, 0, B, C, D2, self.preds.data_ptr(), None, nat.F32, 0, None,
+                                          None, None, None, None, 0, ops._stream()), "head_wide")
+            return
+        tg, dE = self.tg_set[s], self.dc[L - 1]
+        ldy = C if self.wide_task == 1 else 0
+        assert tg.is_contiguous() and tg.numel() == (B * C if self.wide_task == 1 else B)
+        self._time_next(*self.WIDE_MARKS)
+        self._head_live_rows()
+        nat.check(lib.gsage_head_wide(E.data_ptr(), E.stride(0), m.fc.weight.data_ptr(), m.fc.bias.data_ptr(),
+                                      tg.data_ptr(), self.wide_task, ldy, B, C, D2, self.preds.data_ptr(),
+                                      dE.data_ptr(), nat.BF16 if dE.dtype == torch.bfloat16 else nat.F32, dE.stride(0),
+                                      None, None, None, self.head_scratch.data_ptr(), None, 0, ops._stream()),
+                  "head_wide")
+
     def _stage_head(self, s):
-        """the head this model gets: fused cross-entropy, fused L1, or stock torch autograd over three ops"""
+        """the head this model gets: fused cross-entropy, fused L1, the opt-in wide head, or stock torch autograd over
+        three ops"""
         if self.fused_head:
             self._stage_head_ce(s)
         elif self.fused_l1:
             self._stage_head_l1(s)
+        elif self.fused_wide:
+            self._stage_head_wide(s)
         else:
             self._torch_head(s)
 
@@ -1337,7 +1411,7 @@ class FusedTrainStep(object):
     def _finish_init_eval(self, capture, warmup):
         dev, B, nb = self.dev, self.B, self.EVAL_BATCHES
         self.capture_mode = {True: "cmdlist", False: None, None: None}.get(capture, capture)
-        if self.capture_mode == "cmdlist" and not (self.fused_head or self.fused_l1):
+        if self.capture_mode == "cmdlist" and not (self.fused_head or self.fused_l1 or self.fused_wide):
             self.capture_mode = None               # (the stock-torch head cannot be recorded: eager launches)
         assert self.capture_mode in (None, "cmdlist"), "eval_only records command lists (or launches eagerly)"
         # the fold's batches as a device-resident queue (ids, draws): one recorded list serves every batch
@@ -1536,6 +1610,7 @@ class FusedTrainStep(object):
 
     # launches an engine can time in place: name -> (start mark, stop mark); subclasses add theirs
     TIMED = {"gather": (0, 1)}
+    WIDE_MARKS = (14, 15)     # instrument(): events around the gsage_head_wide launch ("head_wide" in last_launch_ms)
 
     def instrument(self, on=True):
         """Measurement only (bench.py's roofline objects): re-record the command lists with HIP start / stop events
@@ -1561,6 +1636,8 @@ class FusedTrainStep(object):
             cl = front = self.g_main[0].cl
         out = {}
         timed = dict(self.TIMED) if self.ddp is None else {"exchange": (8, 9)}
+        if self.ddp is None and getattr(self, "fused_wide", False):
+            timed["head_wide"] = self.WIDE_MARKS
         for name, (a, b) in timed.items():
             try:
                 out[name] = (front if name == "gather" else cl).elapsed_ms(a, b)
@@ -1715,7 +1792,7 @@ class FusedTrainStep(object):
     def _pad_batch(self, ids, targets):
         """A batch one or a few seeds short of B (the reference's near-equal chunks): pad with its first seed."""
         b = int(ids.shape[0])
-        if not (2 <= b < self.B) or not (self.fused_head or self.fused_l1):
+        if not (2 <= b < self.B) or not (self.fused_head or self.fused_l1 or self.fused_wide):
             raise ValueError("this engine was recorded for batches of %d seeds (got %d); shorter batches need one of "
                              "the fused heads" % (self.B, b))
         pad = self.B - b

@@ -114,7 +114,7 @@ class FusedUnsupMeanTrainStep(FusedMeanTrainStep):
 
     def _init_head(self, loss_fn, example_targets):
         model, dev, Bs, Q = self.model, self.dev, self.Bs, self.Q
-        self.fused_head = self.fused_l1 = self.fused_tail = False
+        self.fused_head = self.fused_l1 = self.fused_tail = self.fused_wide = False
         self.D = int(model.output_dim)
         assert self.D == int(self.hout[self.L - 1].shape[1])
         f32 = torch.float32

@@ -1733,3 +1733,115 @@ def probe_pass(table, ids, targets, W, b, task, splits=0):
     nat.check(nat.lib().gsage_finalize_grads(_ptr(descs), 1, width - 1, _ptr(flat), _ptr(sq), None, None, 0, None, 0,
                                              _stream()), "finalize_grads")
     return loss[0], flat[:C * D].view(C, D), flat[C * D:]
+
+
+# =============================================================================================
+# The head for a wide class dimension: normalize + fc + loss + gradients in one launch (csrc/gsage_head_wide.hip)
+# =============================================================================================
+WIDE_HEAD_C_MAX, WIDE_HEAD_D_MAX = 128, 1024
+
+
+def wide_head_scratch(B, C, D):
+    """(floats of gsage_head_wide's scratch, its partial rows) -- host arithmetic."""
+    floats = int(nat.lib().gsage_head_wide_scratch(int(B), int(C), int(D)))
+    if floats < 0:
+        raise ValueError("wide_head: B = %d, C = %d, D = %d are outside the kernel's limits (B >= 1, C <= %d, D <= %d)"
+                         % (B, C, D, WIDE_HEAD_C_MAX, WIDE_HEAD_D_MAX))
+    return floats, floats // (C * D + C + 1)
+
+
+def _wide_head_host(E, W, b, targets, code, bv, dE_dtype):
+    """The definition in torch float32 (host mode)."""
+    C = int(W.shape[0])
+    Ed = E.detach().float().clone().requires_grad_(True)
+    Wd, bd = W.detach().clone().requires_grad_(True), b.detach().clone().requires_grad_(True)
+    preds = F.normalize(Ed, dim=1) @ Wd.t() + bd
+    if targets is None:
+        return preds.detach(), None, None, None, None
+    live = preds[:bv]
+    if code == 0:
+        loss = (torch.logsumexp(live, dim=1) - live.gather(1, targets[:bv].view(-1, 1)).view(-1)).sum() / bv
+    else:
+        y = targets[:bv, :C].float()
+        loss = ((F.softplus(live) - y * live).sum(dim=1) / C).sum() / bv
+    dE, dW, db = torch.autograd.grad(loss, [Ed, Wd, bd])
+    return preds.detach(), loss.detach(), dE.to(dE_dtype), dW, db
+
+
+def wide_head(E, W, b, targets, task, n_valid=None, dE_dtype=None):
+    """gsage_head_wide: z = normalize(E), preds = z W^T + b, the task's loss over the first n_valid rows and its
+    gradients -> (preds fp32 [B, C], loss fp32 scalar, dE [B, D], dW fp32 [C, D], db fp32 [C]); include/gsage.h.
+    E fp32 [B, D] (unit column stride), W fp32 [C, D], b fp32 [C]; task: "classification" (targets int64 [B],
+    F.cross_entropy) or "multilabel_classification" (targets fp32 [B, >= C], F.multilabel_soft_margin_loss), the codes
+    of PROBE_TASKS.  1 <= C <= 128, 1 <= D <= 1024.  n_valid (an int in [1, B], default B): rows past it are padding --
+    predictions, no loss, zero rows of dE.  dE_dtype: torch.float32 (default) or torch.bfloat16.
+    targets None: forward only -> (preds, None, None, None, None).
+
+    CUDA: one launch plus the deterministic sum of its partial rows.  CPU: the same definition in torch float32."""
+    code = probe_task(task)
+    if not (torch.is_tensor(E) and E.dim() == 2 and E.dtype == torch.float32):
+        raise ValueError("wide_head: E must be an fp32 [B, D] tensor")
+    if not (torch.is_tensor(W) and W.dim() == 2 and W.dtype == torch.float32):
+        raise ValueError("wide_head: W must be an fp32 [C, D] tensor")
+    C, D = int(W.shape[0]), int(W.shape[1])
+    B = int(E.shape[0])
+    if not (torch.is_tensor(b) and b.dtype == torch.float32 and tuple(b.shape) == (C,)):
+        raise ValueError("wide_head: b must be an fp32 [%d] tensor (one bias per row of W)" % C)
+    if int(E.shape[1]) != D:
+        raise ValueError("wide_head: E has %d columns, W %d" % (int(E.shape[1]), D))
+    if not 1 <= C <= WIDE_HEAD_C_MAX:
+        raise ValueError("wide_head: W must have between 1 and %d rows (classes), not %d" % (WIDE_HEAD_C_MAX, C))
+    if not 1 <= D <= WIDE_HEAD_D_MAX:
+        raise ValueError("wide_head: W must have between 1 and %d columns, not %d" % (WIDE_HEAD_D_MAX, D))
+    if B < 1:
+        raise ValueError("wide_head: E has no rows")
+    if W.device != E.device or b.device != E.device:
+        raise ValueError("wide_head: W and b must be on E's device")
+    dE_dtype = torch.float32 if dE_dtype is None else dE_dtype
+    if dE_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("wide_head: dE_dtype must be torch.float32 or torch.bfloat16, not %s" % (dE_dtype,))
+    bv = B if n_valid is None else int(n_valid)
+    if not 1 <= bv <= B:
+        raise ValueError("wide_head: n_valid must be in [1, %d], not %d" % (B, bv))
+    if targets is not None:
+        if not torch.is_tensor(targets) or targets.device != E.device:
+            raise ValueError("wide_head: targets must be a tensor on E's device")
+        if code == 0:
+            if targets.dtype != torch.int64 or targets.numel() != B or targets.dim() > 2:
+                raise ValueError("wide_head: classification targets must be int64 [%d], not %s %s"
+                                 % (B, targets.dtype, tuple(targets.shape)))
+            targets = targets.contiguous().view(-1)
+        else:
+            if targets.dtype != torch.float32 or targets.dim() != 2 or int(targets.shape[0]) != B or \
+                    int(targets.shape[1]) < C:
+                raise ValueError("wide_head: multilabel targets must be fp32 [%d, >= %d], not %s %s"
+                                 % (B, C, targets.dtype, tuple(targets.shape)))
+            if targets.stride(1) != 1 or targets.stride(0) < C:
+                targets = targets.contiguous()
+    if not E.is_cuda:
+        return _wide_head_host(E, W, b, targets, code, bv, dE_dtype)
+    dev, f32 = E.device, torch.float32
+    Ec = E.detach()
+    if Ec.stride(1) != 1 or Ec.stride(0) < D:
+        Ec = Ec.contiguous()
+    Wc, bc = W.detach().contiguous(), b.detach().contiguous()
+    preds = torch.empty(B, C, dtype=f32, device=dev)
+    L = nat.lib()
+    if targets is None:
+        nat.check(L.gsage_head_wide(_ptr(Ec), Ec.stride(0), _ptr(Wc), _ptr(bc), None, code, 0, B, C, D, _ptr(preds),
+                                    None, nat.F32, 0, None, None, None, None, None, 0, _stream()), "head_wide")
+        return preds, None, None, None, None
+    floats, _rows = wide_head_scratch(B, C, D)
+    scratch = torch.empty(floats, dtype=f32, device=dev)
+    dE = torch.empty(B, D, dtype=dE_dtype, device=dev)
+    dW, db = torch.empty(C, D, dtype=f32, device=dev), torch.empty(C, dtype=f32, device=dev)
+    loss = torch.empty(1, dtype=f32, device=dev)
+    nv = None
+    if bv != B:
+        nv = torch.full((1,), bv, dtype=torch.int32, device=dev)
+        nat.check(L.gsage_head_n_valid_next(_ptr(nv)), "head_n_valid_next")
+    nat.check(L.gsage_head_wide(_ptr(Ec), Ec.stride(0), _ptr(Wc), _ptr(bc), _ptr(targets), code,
+                                targets.stride(0) if code else 0, B, C, D, _ptr(preds), _ptr(dE), _code(dE_dtype),
+                                dE.stride(0), _ptr(dW), _ptr(db), _ptr(loss), _ptr(scratch), None, 0, _stream()),
+              "head_wide")
+    return preds, loss[0], dE, dW, db

@@ -28,6 +28,12 @@ loading to one OCP e4m3 byte per element with a power-of-two scale per column (s
 on stderr how large the table was and is and the largest absolute error.  The mean engine reads the FP8 table through
 the FP8 gather launch; every other model takes the module path (said on stderr, as for every uncovered model).
 
+--wide-head (default off: nothing changes): the multilabel head (2..128 labels) and cross-entropy over 65..128 classes
+run on gsage_head_wide inside the engine's step (engine wide_head=True).  That head ignores padded seeds, so such a
+problem gets a fused engine whatever the sizes of the reference's chunks, training and evaluation both as native
+command lists; one stderr line names the head that runs.  One batch per call (no device-resident queue); one process;
+refused with --unsupervised.
+
 Layer-wise full-neighbourhood inference (infer.py, opt-in; the default output is unchanged):
   --full-neighbour-eval   val_metric / test_f1 come from infer.full_neighbour on the val / test folds (deterministic:
                           every neighbour of every node, no sampling) instead of the sampled forward
@@ -243,8 +249,8 @@ class FusedEvaluator(object):
     would draw from, no autograd, no per-op launches, the metric on the device.  One engine per fold (their chunk
     sizes differ), built on first use; a model / store no engine covers keeps the module path (said once)."""
 
-    def __init__(self, cls, model, problem):
-        self.cls, self.model, self.problem = cls, model, problem
+    def __init__(self, cls, model, problem, wide_head=False):
+        self.cls, self.model, self.problem, self.wide_head = cls, model, problem, bool(wide_head)
         self.engines, self.off = {}, False
 
     def _fold(self, mode, batch_size=512):
@@ -271,7 +277,9 @@ class FusedEvaluator(object):
                     if problem.task == 'classification' else \
                     torch.zeros((ids.shape[1],) + tuple(np.asarray(problem.targets[:1]).shape[1:]), dtype=torch.float32,
                                 device=ids.device)
-                eng = self.engines[mode] = self.cls(model, problem.feats, problem.loss_fn, ids[0], tg, eval_only=True)
+                kw = {"wide_head": True} if self.wide_head else {}
+                eng = self.engines[mode] = self.cls(model, problem.feats, problem.loss_fn, ids[0], tg, eval_only=True,
+                                                    **kw)
             except Exception as e:
                 self.off = True
                 print('gsage: evaluation stays on the module path (%s: %s)' % (type(e).__name__, e), file=sys.stderr)
@@ -331,6 +339,9 @@ def parse_args(argv=None):
                              'eager: the module path; fused: an engine or an error.  --unsupervised runs on the module '
                              'path unless --engine fused asks for FusedUnsupMeanTrainStep (needs --rng philox)')
     parser.add_argument('--feature-dtype', type=str, default='native', choices=['native', 'fp8'])
+    parser.add_argument('--wide-head', action="store_true",
+                        help='fuse the multilabel head (2..128 labels) and cross-entropy over 65..128 classes '
+                             '(gsage_head_wide): such a problem then runs on a fused engine whatever its chunk sizes')
     parser.add_argument('--full-neighbour-eval', action="store_true")
     parser.add_argument('--save-embeddings', type=str, default=None)
     parser.add_argument('--eval-closure', action="store_true")
@@ -418,6 +429,8 @@ def main(argv=None, problem=None):
     gs.helpers.legacy_stream.enabled = bool(args.cuda and args.rng == 'compat' and
                                             os.environ.get("GSAGE_HOST_SEL", "0") != "1")
 
+    if args.unsupervised and args.wide_head:
+        raise SystemExit('gsage: --unsupervised: --wide-head fuses a supervised head; there is none')
     if args.unsupervised and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("GSAGE_FORCE_DDP", "0") == "1"):
         raise SystemExit('gsage: --unsupervised: data-parallel training is not supported (run a single process)')
     ddp = gs.dist.init_from_env(args.cuda)            # no-op outside torch.distributed.run
@@ -607,7 +620,10 @@ def choose_engine(args, problem, model, ddp):
         if nodes.shape[0] // n_batches < 2:           # the smallest of the reference's array_split chunks
             return give_up('chunks of fewer than two training nodes')
     example = torch.zeros(1, dtype=torch.int64 if problem.task == 'classification' else torch.float32)
-    why = cls.head_why_not(model, problem.loss_fn, example, B, padded, world)
+    if args.wide_head:
+        why = cls.head_why_not(model, problem.loss_fn, example, B, padded, world, wide=True)
+    else:
+        why = cls.head_why_not(model, problem.loss_fn, example, B, padded, world)
     if why is not None:
         return give_up(why)
     return cls
@@ -660,19 +676,23 @@ def train_fused(args, problem, model, ddp, start_time, cls):
                     [int(c.shape[0]) for c in chunks])
     ids, tgs, live = epoch_batches()
     first = tgs[0].view(B, 1) if cls_task else tgs[0]
-    step = cls(model, problem.feats, problem.loss_fn, ids[0], first, ddp=ddp)
+    step = cls(model, problem.feats, problem.loss_fn, ids[0], first, ddp=ddp, **({"wide_head": True} if args.wide_head else {}))
+    if args.wide_head:
+        print('gsage: --wide-head: the head runs on %s' % (
+            'gsage_head_wide' if step.fused_wide else 'gsage_head_ce (at most 64 classes)' if step.fused_head else
+            'gsage_head_l1' if step.fused_l1 else 'stock torch ops (not a case of the wide head)'), file=sys.stderr)
     # engines with the fused classification head walk a device-resident queue of the epoch's batches; the others
     # (regression: the fused L1 head; multilabel: stock torch ops inside the captured step) take one batch per call
     queued = bool(step.fused_head)
     # (choose_engine has made sure that a head without a fused kernel never meets padded chunks)
-    assert live is None or step.fused_head or step.fused_l1 or min(live) == B
+    assert live is None or step.fused_head or step.fused_l1 or step.fused_wide or min(live) == B
     val_metric = train_metric = None
     epoch = 0
     if args.full_neighbour_eval:
         fold_eval = lambda mode='val': full_neighbour_evaluate(model, problem, mode=mode,      # noqa: E731
                                                                closure=args.eval_closure)
     elif os.environ.get("GSAGE_FUSED_EVAL", "1") == "1":
-        fold_eval = FusedEvaluator(cls, model, problem).prepare('val')
+        fold_eval = FusedEvaluator(cls, model, problem, wide_head=args.wide_head).prepare('val')
     else:
         fold_eval = lambda mode='val': evaluate(model, problem, mode=mode)                     # noqa: E731
     # The per-batch line (train.py:150-158) without a host sync per step: batch b is scored on the device right behind
