@@ -1182,6 +1182,50 @@ int gsage_segment_reduce_weighted(const void *table, int dtype, int64_t ld, int6
                                   int out_dtype, int64_t out_ld, int act, int32_t *err_flag, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Importance neighbourhoods (csrc/gsage_importance.hip): a node's most-visited nodes under short random walks become
+ * its neighbourhood, the visit counts its edge weights (the construction PinSAGE introduced).  What turns ANY
+ * adjacency into a weighted one for everything under "Weighted adjacency".  Additive; the ABI version is unchanged.
+ * No reference counterpart.
+ *
+ * Inputs: a device CSR (rowptr int64 [n_rows + 1], col int32 [nnz]; n_rows < 2^31), optionally its per-edge table
+ * cdf uint64 [nnz] ("Weighted adjacency"; NULL: the graph is unweighted), sources ids int64 [M], n_walks R >= 1,
+ * walk_len L in 1..16, top T in 1..64, R * L <= 4096, a 64-bit seed.
+ *
+ * Walks.  For source v = ids[i] and walk r in [0, R): u = v, then steps s = 0 .. L - 1:
+ *     w    = philox4x32_10({lo(v), r, s >> 1, 0}, {lo(seed), hi(seed) ^ 0x49000000})
+ *     r64  = (w[2*(s&1)] << 32) | w[2*(s&1) + 1]                                    (a block holds two steps)
+ *   The counter holds the source's ID, not its position in ids: a source's row does not depend on which other sources
+ *   share the launch, on their order, or on how the caller cuts them into launches.
+ *     uniform step  (cdf == NULL)   deg = rowptr[u+1] - rowptr[u];  deg <= 0: the walk ends;
+ *                                   u = col[rowptr[u] + ((r64 * deg) >> 64)]        (128-bit product)
+ *     weighted step                 T_u = cdf[rowptr[u+1] - 1] (0 for an empty row);  T_u == 0: the walk ends;
+ *                                   x = (r64 * T_u) >> 64;  u = col[first e of the row with cdf[e] > x]
+ *                                   (the search of gsage_sample_csr_weighted)
+ *   A step that lands on an id outside [0, n_rows) raises *err_flag (int32, may be NULL), ends the walk and is not
+ *   counted.  A source outside [0, n_rows) raises the flag and gets an empty row.
+ * Counting.  Every landing u != v is one visit of u; landings on the source itself are not counted.  Row 0 is a node
+ * like any other here (the reference's convention never stores it as a neighbour).
+ * Result row.  The distinct visited nodes in the TOTAL ORDER (count descending, id ascending); k_i = min(T, distinct):
+ *     out_deg[i]      = k_i                                   int32 [M]
+ *     out_col[i*T+j]  = the j-th node, j < k_i                int32 [M, T]
+ *     out_w[i*T+j]    = its count as a float (an exact integer <= 4096, which the quanta of gsage_edge_cdf_build
+ *                       represent without loss)                fp32 [M, T]
+ *   Entries j >= k_i are written as 0 / 0.f: the padded row is fully defined.
+ * The result is a pure function of the graph, the source's id and the seed: no atomics, same bits for every grid.
+ * One launch.  GSAGE_EINVAL (without a GPU) for sizes outside the limits; the message names R * L > 4096.
+ *
+ * gsage_importance_compact -- the padded rows packed into a CSR: for j < out_deg[i],
+ *     col_new[rowptr_new[i] + j] = out_col[i*T+j],  w_new[rowptr_new[i] + j] = out_w[i*T+j]
+ * rowptr_new int64 [M]: the exclusive scan of out_deg (the caller's: set-up, once per graph).  One launch.
+ * ---------------------------------------------------------------------------------------- */
+int gsage_importance_walks(const int64_t *rowptr, const int32_t *col, const uint64_t *cdf, int64_t n_rows,
+                           const int64_t *ids, int64_t M, int32_t n_walks, int32_t walk_len, int32_t top, uint64_t seed,
+                           int32_t *out_col, float *out_w, int32_t *out_deg, int32_t *err_flag, void *stream);
+int gsage_importance_compact(const int32_t *out_col, const float *out_w, const int32_t *out_deg,
+                             const int64_t *rowptr_new, int64_t M, int32_t top, int32_t *col_new, float *w_new,
+                             void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * k-hop closure blocks (csrc/gsage_block.hip, csrc/gsage_fullgraph.hip): full-neighbourhood inference for a query
  * set (infer.closure / infer.query).  Additive; the ABI version is unchanged.  No reference counterpart.
  *

@@ -17,6 +17,8 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
                               probe_eval: a linear classifier fitted on the frozen embeddings, micro / macro F1 of
                               the val / test folds (ops.probe_pass, csrc/gsage_probe.hip)
     store.WeightedAdj         edge weights: sparse_weighted_neighbor_sampler, weight-normalised full-neighbourhood mean
+    store.importance_adj      any adjacency -> its importance-weighted one: visit counts of short random walks, the
+                              top-T most-visited nodes per row (DeviceCSR.importance, csrc/gsage_importance.hip)
     models.GSUnsupervised     label-free training: random-walk positives, degree^0.75 negatives, skip-gram head
     engine/                   the whole train_step as recorded launches (captured autograd path; fused mean /
                               pool / attention engines on a shared base)
@@ -29,9 +31,9 @@ from .lr import LRSchedule                                          # noqa: F401
 from .models import GSSupervised, GSUnsupervised                                # noqa: F401
 from .nn_modules import aggregator_lookup, find_sampler, prep_lookup, sampler_extensions, sampler_lookup   # noqa: F401
 from .problem import DeviceMetrics, NodeProblem, ProblemLosses, ProblemMetrics, batch_metric   # noqa: F401
-from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef, WeightedAdj                  # noqa: F401
+from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef, WeightedAdj, importance_adj  # noqa: F401
 
 __all__ = ["GSSupervised", "GSUnsupervised", "NodeProblem", "aggregator_lookup", "prep_lookup", "sampler_lookup",
            "set_seeds", "to_numpy", "LRSchedule", "FeatureStore", "DeviceCSR", "RowRef", "ops", "full_neighbour",
            "embeddings", "query", "nearest", "link_rank", "link_metrics", "held_out_edges", "LinearProbe", "linear_probe",
-           "probe_eval", "WeightedAdj", "find_sampler", "sampler_extensions"]
+           "probe_eval", "WeightedAdj", "find_sampler", "sampler_extensions", "importance_adj"]

@@ -17,6 +17,7 @@
 //                              first entry of the row above it.  The n draws of a parent sit in consecutive lanes: the
 //                              first probes of their searches read the same words.
 #include "gsage_common.h"
+#include "gsage_weighted_dev.h"
 
 namespace gsage {
 
@@ -155,16 +156,9 @@ k_sample_weighted(const int64_t *__restrict__ rowptr, const int32_t *__restrict_
         const uint64_t blk = g >> 1;
         const philox4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)call, (uint32_t)(call >> 32),
                                         seed_lo, seed_hi ^ WEIGHTED_TAG);
-        const bool odd = (g & 1ull) != 0;                 // selects, not r.v[2 * (g & 1)]: no scratch
-        const uint64_t r64 = ((uint64_t)(odd ? r.v[2] : r.v[0]) << 32) | (uint64_t)(odd ? r.v[3] : r.v[1]);
+        const uint64_t r64 = philox_r64(r, (g & 1ull) != 0);
         const uint64_t x = __umul64hi(r64, T);            // < T
-        int64_t lo = beg, hi = end - 1;                   // cdf[end - 1] = T > x: the answer is in [beg, end - 1]
-        while (lo < hi) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (cdf[mid] > x) hi = mid;
-            else lo = mid + 1;
-        }
-        out[t] = (int64_t)col[lo];
+        out[t] = (int64_t)col[cdf_first_above(cdf, beg, end, x)];
     }
 }
 

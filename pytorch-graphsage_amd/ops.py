@@ -405,6 +405,148 @@ def sample_csr_weighted(csr, ids, n, philox, out=None):
 
 
 # =============================================================================================
+# Importance neighbourhoods: visit counts of short random walks and their top-T (csrc/gsage_importance.hip)
+# =============================================================================================
+IMPORTANCE_TAG = 0x49000000                                                           # include/gsage.h
+IMPORTANCE_MAX_LANDINGS, IMPORTANCE_MAX_LEN, IMPORTANCE_MAX_TOP = 4096, 16, 64
+
+
+def importance_check(n_walks, walk_len, top):
+    """ValueError for sizes outside the limits of gsage_importance_walks (the library's own sentences)."""
+    if n_walks < 1:
+        raise ValueError("importance_walks: n_walks must be >= 1")
+    if not 1 <= walk_len <= IMPORTANCE_MAX_LEN:
+        raise ValueError("importance_walks: walk_len must be in 1..%d" % IMPORTANCE_MAX_LEN)
+    if not 1 <= top <= IMPORTANCE_MAX_TOP:
+        raise ValueError("importance_walks: top must be in 1..%d" % IMPORTANCE_MAX_TOP)
+    if n_walks * walk_len > IMPORTANCE_MAX_LANDINGS:
+        raise ValueError("importance_walks: n_walks * walk_len = %d, more than %d landings per source"
+                         % (n_walks * walk_len, IMPORTANCE_MAX_LANDINGS))
+
+
+def _philox4_np(c, k0, k1):
+    """Philox4x32-10 over four uint64 arrays of 32-bit counter words -> four such arrays (host mode)"""
+    mask, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    c = list(c)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> s32) ^ c[1] ^ np.uint64(k0)) & mask, p1 & mask, ((p0 >> s32) ^ c[3] ^ np.uint64(k1)) & mask, p0 & mask]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c
+
+
+def _importance_host(csr, idn, R, L, T, seed):
+    """gsage_importance_walks in numpy: every (source, walk) pair is one element, the steps are the loop.
+    -> (col int32 [M, T], w fp32 [M, T], deg int32 [M], err)"""
+    rp, col, n_rows = csr.rowptr.numpy(), csr.col.numpy(), csr.n_rows
+    cdf = csr.edge_cdf.numpy().view(np.uint64) if csr.edge_cdf is not None else None
+    M = int(idn.shape[0])
+    out_col, out_w = np.zeros((M, T), dtype=np.int32), np.zeros((M, T), dtype=np.float32)
+    out_deg = np.zeros(M, dtype=np.int32)
+    in_range = (idn >= 0) & (idn < n_rows)
+    err = not bool(in_range.all())
+    if col.shape[0] == 0:
+        return out_col, out_w, out_deg, err
+    k0, k1 = seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ IMPORTANCE_TAG
+    s32 = np.uint64(32)
+    per = max(1, (1 << 21) // R)                          # sources per piece: the working arrays stay at ~2 M elements
+    for o in range(0, M, per):
+        v = idn[o:o + per]
+        m = int(v.shape[0])
+        src, vv = np.repeat(np.arange(m, dtype=np.int64), R), np.repeat(v, R)
+        r = np.tile(np.arange(R, dtype=np.uint64), m)
+        alive = np.repeat(in_range[o:o + per], R)
+        u = np.where(alive, vv, 0)
+        c0, zero = vv.astype(np.uint64) & np.uint64(0xFFFFFFFF), np.zeros(m * R, dtype=np.uint64)
+        land_src, land_id = [], []
+        for s in range(L):
+            if not s & 1:
+                w = _philox4_np([c0, r, np.full(m * R, s >> 1, dtype=np.uint64), zero], k0, k1)
+            r64 = (w[2] << s32) | w[3] if s & 1 else (w[0] << s32) | w[1]
+            beg, end = rp[u], rp[u + 1]
+            if cdf is None:
+                go = alive & (end > beg)
+                e = beg + _mulhi64(r64, np.where(go, end - beg, 0).astype(np.uint64)).astype(np.int64)
+            else:
+                Tu = np.where(end > beg, cdf[np.maximum(end, 1) - 1], np.uint64(0)).astype(np.uint64)
+                go = alive & (Tu > 0)
+                x = _mulhi64(r64, Tu)
+                lo, hi = np.where(go, beg, 0), np.where(go, end - 1, 0)      # cdf[end - 1] = T_u > x
+                while True:
+                    act = lo < hi
+                    if not act.any():
+                        break
+                    mid = (lo + hi) >> 1
+                    gt = cdf[mid] > x
+                    hi = np.where(act & gt, mid, hi)
+                    lo = np.where(act & ~gt, mid + 1, lo)
+                e = lo
+            nu = col[np.where(go, e, 0)].astype(np.int64)
+            inside = (nu >= 0) & (nu < n_rows)
+            err = err or bool((go & ~inside).any())
+            alive = go & inside
+            u = np.where(alive, nu, 0)
+            counted = alive & (u != vv)
+            land_src.append(src[counted])
+            land_id.append(u[counted])
+        uniq, count = np.unique((np.concatenate(land_src) << 32) | np.concatenate(land_id), return_counts=True)
+        us, ui = uniq >> 32, uniq & 0xFFFFFFFF
+        order = np.lexsort((ui, -count, us))              # by source, then count descending, then id ascending
+        us, ui, count = us[order], ui[order], count[order]
+        pos = np.arange(us.shape[0]) - np.searchsorted(us, np.arange(m))[us]
+        keep = pos < T
+        out_col[o + us[keep], pos[keep]] = ui[keep]
+        out_w[o + us[keep], pos[keep]] = count[keep]
+        out_deg[o:o + m] = np.minimum(np.bincount(us, minlength=m), T)
+    return out_col, out_w, out_deg, err
+
+
+def importance_walks(csr, ids, n_walks, walk_len, top, seed):
+    """Importance neighbourhoods (include/gsage.h, gsage_importance_walks): from every source in ids (LongTensor [M]
+    on csr.device), n_walks random walks of walk_len steps -- weighted steps exactly when csr.edge_cdf is not None --
+    and the `top` most-visited nodes, visit count descending then id ascending.
+    -> (col int32 [M, top], w fp32 [M, top] = the counts, deg int32 [M]); entries at and beyond deg are 0.
+    An id outside the graph (a source, or a stored neighbour a walk reaches) raises csr.err_flag: csr.check().
+    CPU tensors: the same definition in numpy (host mode), the same bits."""
+    n_walks, walk_len, top, seed = int(n_walks), int(walk_len), int(top), int(seed) & 0xFFFFFFFFFFFFFFFF
+    importance_check(n_walks, walk_len, top)
+    ids = ids.contiguous().view(-1)
+    assert ids.dtype == torch.int64 and ids.device == csr.rowptr.device
+    M = int(ids.shape[0])
+    if ids.is_cuda:
+        col = torch.empty(M, top, dtype=torch.int32, device=ids.device)
+        w = torch.empty(M, top, dtype=torch.float32, device=ids.device)
+        deg = torch.empty(M, dtype=torch.int32, device=ids.device)
+        nat.check(nat.lib().gsage_importance_walks(_ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.edge_cdf), csr.n_rows,
+                                                   _ptr(ids), M, n_walks, walk_len, top, seed, _ptr(col), _ptr(w),
+                                                   _ptr(deg), _ptr(csr.err_flag), _stream()), "importance_walks")
+        return col, w, deg
+    col, w, deg, err = _importance_host(csr, ids.numpy(), n_walks, walk_len, top, seed)
+    if err:
+        csr.err_flag.fill_(1)
+    return torch.from_numpy(col), torch.from_numpy(w), torch.from_numpy(deg)
+
+
+def importance_compact(col, w, deg):
+    """The padded rows of importance_walks packed into a CSR's arrays (gsage_importance_compact; the row offsets are a
+    torch.cumsum: set-up, once per graph).  -> (col int32 [nnz], w fp32 [nnz]), nnz = deg.sum()."""
+    M, top = int(col.shape[0]), int(col.shape[1])
+    if not col.is_cuda:
+        keep = torch.arange(top)[None, :] < deg[:, None]
+        return col[keep], w[keep]
+    ends = torch.cumsum(deg, 0, dtype=torch.int64)
+    nnz = int(ends[-1]) if M else 0
+    col_new = torch.empty(nnz, dtype=torch.int32, device=col.device)
+    w_new = torch.empty(nnz, dtype=torch.float32, device=col.device)
+    if nnz:
+        begs = ends - deg
+        nat.check(nat.lib().gsage_importance_compact(_ptr(col), _ptr(w), _ptr(deg), _ptr(begs), M, top, _ptr(col_new),
+                                                     _ptr(w_new), _stream()), "importance_compact")
+    return col_new, w_new
+
+
+# =============================================================================================
 # Unsupervised batches: random-walk positives + degree^0.75 negatives (csrc/gsage_unsup.hip)
 # =============================================================================================
 UNSUP_TAG_LEN, UNSUP_TAG_STEP, UNSUP_TAG_NEG = 0x4C000000, 0x53000000, 0x4E000000     # include/gsage.h

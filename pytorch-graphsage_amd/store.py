@@ -132,6 +132,39 @@ class DeviceCSR(object):
         self.edge_cdf = ops.edge_cdf(self.rowptr, w, self.n_rows)
         return self
 
+    def _importance_rows(self, n_walks, walk_len, top, seed, chunk):
+        """(rowptr int64 [n_rows + 1], col int32 [nnz], counts fp32 [nnz]) of importance(), on this adjacency's device"""
+        from . import ops
+        ops.importance_check(int(n_walks), int(walk_len), int(top))
+        chunk = max(int(chunk), 1)
+        degs, cols, counts = [], [], []
+        for o in range(0, self.n_rows, chunk):
+            ids = torch.arange(o, min(o + chunk, self.n_rows), dtype=torch.int64, device=self.device)
+            c, w, d = ops.importance_walks(self, ids, n_walks, walk_len, top, seed)
+            c, w = ops.importance_compact(c, w, d)        # (the padded buffers of a chunk end here)
+            degs.append(d)
+            cols.append(c)
+            counts.append(w)
+        self.check()
+        rowptr = torch.zeros(self.n_rows + 1, dtype=torch.int64, device=self.device)
+        if not degs:
+            return rowptr, torch.zeros(0, dtype=torch.int32, device=self.device), \
+                torch.zeros(0, dtype=torch.float32, device=self.device)
+        torch.cumsum(torch.cat(degs), 0, dtype=torch.int64, out=rowptr[1:])
+        return rowptr, torch.cat(cols), torch.cat(counts)
+
+    def importance(self, n_walks=50, walk_len=2, top=16, seed=0, chunk=1 << 20):
+        """The importance-weighted adjacency of this one (include/gsage.h, "Importance neighbourhoods"): from every
+        row, n_walks random walks of walk_len steps (weighted steps when this adjacency carries an edge_cdf); the row's
+        new neighbours are its `top` most-visited nodes, most visited first, and the visit counts are the edge weights.
+        -> a new DeviceCSR over the same n_rows with max_deg = top and its edge_cdf (with_weights(counts)).  Built
+        `chunk` rows at a time: the padded [chunk, top] buffers are all that exists beside the result.  IndexError
+        (check()) when a stored neighbour id lies outside the graph.  n_walks in 1.., walk_len in 1..16, top in 1..64,
+        n_walks * walk_len <= 4096.  The defaults reach the toy results of the tests; nobody has tuned them on a real
+        graph."""
+        rowptr, col, counts = self._importance_rows(n_walks, walk_len, top, seed, chunk)
+        return DeviceCSR(rowptr, col, self.n_rows, int(top)).with_weights(counts)
+
     @staticmethod
     def from_scipy(adj, device, weight=None):
         """adj: scipy.sparse matrix in the reference convention.  Checks the convention instead
@@ -199,6 +232,28 @@ class DeviceCSR(object):
             n = min(chunk, nnz - o)
             col[o:o + n] = torch.randint(1, int(n_rows), (n,), dtype=torch.int32, device=device, generator=gen)
         return DeviceCSR(rowptr, col, n_rows, max_deg if max_deg is not None else int(deg_hi))
+
+
+def importance_adj(adj, n_walks=50, walk_len=2, top=16, seed=0, device=None):
+    """Any sparse adjacency -> its importance-weighted one (DeviceCSR.importance), as the WeightedAdj a weighted problem
+    would hand to the samplers.  adj: a scipy matrix in the reference's sparse convention, or a WeightedAdj (its walks
+    then step in proportion to the edge weights).  -> WeightedAdj in the same convention: shape (n_rows, top), row v in
+    columns 0..k_v - 1, data the neighbour ids most visited first, weight the visit counts.  Accepted as it is by
+    sparse_weighted_neighbor_sampler, by full-neighbourhood inference (mean and mean-pool models, as for any weighted
+    graph) and by DeviceCSR.from_scipy.  device: where the walks run -- default the GPU when there is one, else host
+    mode (the same rows).  The defaults reach the toy results of the tests; nobody has tuned them on a real graph."""
+    from scipy import sparse
+    if device is None:
+        device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    if isinstance(adj, WeightedAdj):
+        csr = DeviceCSR.from_scipy(adj.adj, device, weight=adj.weight)
+    else:
+        csr = DeviceCSR.from_scipy(adj, device)
+    rowptr, col, counts = csr._importance_rows(n_walks, walk_len, top, seed, 1 << 20)
+    indptr = rowptr.cpu().numpy()
+    out = sparse.csr_matrix((col.cpu().numpy().astype(np.int64), row_positions(indptr), indptr),
+                            shape=(csr.n_rows, int(top)))
+    return WeightedAdj(out, counts.cpu().numpy())
 
 
 class DenseAdj(object):

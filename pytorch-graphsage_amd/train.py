@@ -89,6 +89,14 @@ update -- and is an error, with the engine's sentence, where that engine does no
 `adj_weight` / `train_adj_weight`; include/gsage.h, "Weighted adjacency").  Always Philox; the module path runs it (said
 on stderr); --full-neighbour-eval / --save-embeddings compute the weight-normalised mean (mean and mean-pool models);
 --unsupervised is refused: its walks are unweighted.
+
+--importance-walks R (with --importance-len L, --importance-top T, --importance-seed S; default off: nothing changes):
+after the problem is loaded, the training and the evaluation adjacency are each replaced by gs.importance_adj of
+THEMSELVES (include/gsage.h, "Importance neighbourhoods": R random walks of L steps from every node, its T most-visited
+nodes as neighbours, the visit counts as edge weights; the training graph's walks never see evaluation edges), and the
+run is a weighted one: --sampler-class sparse_uniform_neighbor_sampler is switched to the weighted sampler (said on
+stderr), the dense sampler is refused, and everything the weighted sampler refuses or redirects stays as it is.  The
+defaults of L and T (2, 16) reach the toy results of the tests; nobody has tuned them on a real graph.
 """
 from __future__ import division, print_function
 
@@ -361,6 +369,12 @@ def parse_args(argv=None):
     parser.add_argument('--walk-len', type=int, default=5)
     parser.add_argument('--n-negatives', type=int, default=20)
     parser.add_argument('--neg-weight', type=float, default=1.0)
+    parser.add_argument('--importance-walks', type=int, default=0,
+                        help='rebuild both adjacencies from this many random walks per node (gs.importance_adj) and '
+                             'train with the weighted sampler; 0 (default): off')
+    parser.add_argument('--importance-len', type=int, default=2)
+    parser.add_argument('--importance-top', type=int, default=16)
+    parser.add_argument('--importance-seed', type=int, default=0)
 
     args = parser.parse_args(argv)
     args.cuda = not args.no_cuda
@@ -371,6 +385,32 @@ def parse_args(argv=None):
     assert 1 <= args.walk_len <= 16 and 1 <= args.n_negatives <= 64, \
         'parse_args: --walk-len must be in 1..16 and --n-negatives in 1..64'
     return args
+
+
+def importance_graphs(args, problem):
+    """--importance-walks: problem.train_adj and problem.adj become the importance-weighted adjacencies of themselves
+    and the run a weighted one (args.sampler_class); one stderr line says what was built and which sampler draws."""
+    if args.sampler_class == 'uniform_neighbor_sampler' or not gs.problem._is_sparse(problem.adj):
+        raise SystemExit('gsage: --importance-walks: random walks need the stored edges of a sparse problem, not the dense '
+                         'sampler\'s pre-sampled table (use --sampler-class sparse_uniform_neighbor_sampler)')
+    if args.sampler_class == 'sparse_uniform_neighbor_sampler':
+        print('gsage: --importance-walks: --sampler-class sparse_uniform_neighbor_sampler becomes '
+              'sparse_weighted_neighbor_sampler (the visit counts are the edge weights)', file=sys.stderr)
+        args.sampler_class = 'sparse_weighted_neighbor_sampler'
+    device = torch.device('cuda' if args.cuda else 'cpu')
+    kw = dict(n_walks=args.importance_walks, walk_len=args.importance_len, top=args.importance_top,
+              seed=args.importance_seed, device=device)
+    t0 = time()
+    try:
+        same = problem.train_adj is problem.adj
+        problem.train_adj = gs.importance_adj(problem.train_adj, **kw)
+        problem.adj = problem.train_adj if same else gs.importance_adj(problem.adj, **kw)
+    except (ValueError, IndexError) as e:
+        raise SystemExit('gsage: --importance-walks: %s' % e)
+    print('gsage: --importance-walks: both adjacencies rebuilt from %d walks of %d steps per node, top %d (%d training '
+          'edges, %d evaluation edges, %.2f s on %s)' % (args.importance_walks, args.importance_len, args.importance_top,
+                                                         problem.train_adj.adj.nnz, problem.adj.adj.nnz, time() - t0,
+                                                         device.type), file=sys.stderr)
 
 
 def build_model(args, problem):
@@ -440,6 +480,8 @@ def main(argv=None, problem=None):
         raise SystemExit('gsage: --probe: a linear probe is a classifier; this problem\'s task is %s' % problem.task)
     if args.link_eval and not gs.problem._is_sparse(problem.adj):
         raise SystemExit('gsage: --link-eval: a dense problem file holds neighbour samples, not edges to hold out')
+    if args.importance_walks:
+        importance_graphs(args, problem)
     weighted = args.sampler_class == 'sparse_weighted_neighbor_sampler'
     if weighted:
         if not (isinstance(problem.adj, gs.store.WeightedAdj) and isinstance(problem.train_adj, gs.store.WeightedAdj)):
