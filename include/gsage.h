@@ -1162,6 +1162,20 @@ int gsage_head_skipgram_live(const float *E, int64_t lde, int32_t B, int32_t Q, 
  *     out[i*n+j] = col[first e in the row with cdf[e] > x]                          (binary search)
  * T == 0 or degree 0 yields the dummy 0; an id outside [0, n_rows) yields 0 and raises *err_flag (may be NULL).
  *
+ * gsage_sample_hops_weighted -- every hop of a frontier in ONE launch: gsage_sample_hops' descriptor, geometry (a
+ * 256-lane workgroup walks the sub-tree of its seeds, the previous hop in LDS) and queue fields, with the draw above per
+ * sample.  Sample (hop k, global index g = rank * |hop k| + local):
+ *     call = call_base + (call_ctr ? *call_ctr : 0) + (k - 1);   w, r64, T, x and the child as above
+ * -- the frontier is bit-identical to n_hops launches of gsage_sample_csr_weighted with call indices call_base + k - 1
+ * and g0 = rank * |hop k|.  T == 0 or degree 0 yields the dummy 0; a parent outside [0, n_rows) yields 0 and raises
+ * *err_flag.  seed_queue / batch_idx / batch_base / n_batches as in gsage_sample_hops: batch
+ * (*batch_idx + batch_base) % n_batches is copied into hop 0.  cdf is an argument of its own: gsage_hops_desc is
+ * unchanged.  max_deg is ignored.  hops == NULL, cdf == NULL, sel != NULL, dense_adj != NULL, n_hops outside 1..5 and a
+ * fan-out product beyond gsage_sample_hops' LDS bound give GSAGE_EINVAL without a launch (and without a GPU); B == 0
+ * returns GSAGE_OK without one.  The search probes seven evenly spaced entries of the row per round (cdf is
+ * non-decreasing inside a row: the first entry above x is one entry however it is found); the environment variable
+ * GSAGE_WEIGHTED_SEARCH=binary, read per call, selects the binary search instead.
+ *
  * gsage_segment_reduce_weighted -- gsage_segment_reduce's arguments for a mean (no keys) plus cdf:
  *     out[v, c] = sum_e p_e table[col[e], c],   p_e = (cdf[e] - cdf[e-1]) / T_v    (the row's first edge subtracts 0)
  * -- what the sampled mean estimates under gsage_sample_csr_weighted, from the same quanta (mode
@@ -1175,6 +1189,7 @@ int gsage_edge_cdf_build(const int64_t *rowptr, const float *weight, int64_t n_r
 int gsage_sample_csr_weighted(const int64_t *rowptr, const int32_t *col, const uint64_t *cdf, int64_t n_rows,
                               const int64_t *ids, int64_t M, int32_t n, uint64_t seed, const uint64_t *call_ctr,
                               uint64_t call_base, uint64_t g0, int64_t *out, int32_t *err_flag, void *stream);
+int gsage_sample_hops_weighted(const gsage_hops_desc *hops, const uint64_t *cdf, void *stream);
 int gsage_segment_reduce_weighted(const void *table, int dtype, int64_t ld, int64_t D, const int64_t *rowptr,
                                   const int32_t *col, const uint64_t *cdf, int64_t n_rows, const int32_t *order,
                                   int64_t n_short, const int64_t *slices, int64_t n_slices, const int64_t *long_rows,

@@ -146,9 +146,10 @@ class FusedTrainStep(object):
         return task, None
 
     @staticmethod
-    def _why_not_common(model, feats, agg_types, what):
+    def _why_not_common(model, feats, agg_types, what, sampler=True):
         """The checks every engine shares: one aggregator family with the stock concat, ReLU on all but the last
-        layer, a sampler whose frontier the fused K1 can produce."""
+        layer, a sampler whose frontier the fused K1 can produce (sampler=False: the caller has checked the sampler
+        itself -- an engine with a sampler launch of its own)."""
         layers = list(model.agg_layers.children())
         if not layers or {type(l) for l in layers} not in [{t} for t in agg_types]:
             return "the layers are not all %s aggregators" % what
@@ -157,6 +158,8 @@ class FusedTrainStep(object):
         codes = [_split_activation(l.activation)[0] for l in layers]
         if codes[:-1] != [nat.ACT_RELU] * (len(layers) - 1) or codes[-1] != nat.ACT_NONE:
             return "activations other than ReLU on the hidden layers and identity on the last (train.py:105-118)"
+        if not sampler:
+            return None
         s = model.train_sampler
         if isinstance(s, SparseUniformNeighborSampler):
             if s.rng not in ("philox", "compat"):
@@ -1661,6 +1664,11 @@ class FusedTrainStep(object):
     def _k1_in_tail(self):
         return False
 
+    def _k1_own_launch(self):
+        """Is the frontier of the batch after the next a launch of its own, behind the gather launch, instead of that
+        launch's sampler role?  The role walks a CSR with uniform draws: the dense frontier is a launch of its own."""
+        return self.dense
+
     def _nx(self, par):
         """ring position of the NEXT batch (gathered during this step)"""
         return (par + 1) % self.P
@@ -1684,7 +1692,7 @@ class FusedTrainStep(object):
             return
         self._time_next(0, 1)
         nx = self._nx(par)
-        if self.dense:           # (the gather launch's sampler role walks a CSR: the dense frontier is a launch of its own)
+        if self._k1_own_launch():
             self._stage_gather(self._qset(nx), with_adam=with_adam, ids=self.ids_q[nx],
                                skip_rows=self._ahead_rows())
             self._stage_sample(0, ids=self.ids_q[par], ahead=True)

@@ -54,7 +54,11 @@ class FusedMeanTrainStep(FusedTrainStep):
         # (utils/pokec.sh:5-13) the level-0 rows are weights: computed per step, nothing is gathered ahead.
         # FP8 storage (identity prep, bf16 compute): the level-0 gathers run on the FP8 gather launch, which writes
         # the bf16 operands the bf16 engine would have gathered, bit for bit; everything behind them is that engine.
-        why = cls._why_not_common(model, feats, (MeanAggregator,), "mean") or \
+        return cls._why_not_mean(model, feats, ddp)
+
+    @classmethod
+    def _why_not_mean(cls, model, feats, ddp, sampler=True):
+        why = cls._why_not_common(model, feats, (MeanAggregator,), "mean", sampler=sampler) or \
             cls._why_not_input(model, feats, ddp, concat_ok=True, fp8_ok=True)
         if why:
             return why
@@ -403,7 +407,7 @@ class FusedMeanTrainStep(FusedTrainStep):
         """data-parallel order: K1(i+2) rides in the launch that gathers the bulk of batch i+1 WHILE the exchange is in
         flight instead of in the launch that follows it (its ~9 us chain of dependent loads would otherwise sit on
         the critical path behind the collective, beside Adam).  Sampling reads no weights: same frontier either way."""
-        return (not self.dense) and os.environ.get("GSAGE_DDP_K1_EARLY", "1") == "1"
+        return (not self._k1_own_launch()) and os.environ.get("GSAGE_DDP_K1_EARLY", "1") == "1"
 
     def _queue_front_means(self, par):
         self._stage_gather(self._qset(1 - par), ids=self.ids_q[1 - par], skip_rows=self._ahead_rows(), part="means",
@@ -420,8 +424,9 @@ class FusedMeanTrainStep(FusedTrainStep):
                       "grad_sqnorm")
             d.n_partial_ready = n_sq
         self._stage_gather(self._qset(1 - par), ids=self.ids_q[1 - par], part="rest", adam=d,
-                           hops=None if (self.dense or self._k1_early()) else self._hops_desc(self.ids_q[par], True))
-        if self.dense:
+                           hops=None if (self._k1_own_launch() or self._k1_early())
+                           else self._hops_desc(self.ids_q[par], True))
+        if self._k1_own_launch():
             self._stage_sample(0, ids=self.ids_q[par], ahead=True)
 
     def _k1_in_k5(self):

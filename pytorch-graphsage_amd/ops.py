@@ -404,6 +404,45 @@ def sample_csr_weighted(csr, ids, n, philox, out=None):
     return torch.from_numpy(np.where(live, vals, 0).astype(np.int64))
 
 
+def sample_hops_weighted(csr, ids, B, fans, philox):
+    """Every hop of a weighted frontier (include/gsage.h, gsage_sample_hops_weighted: one launch): ids is the
+    concatenated buffer [hop 0 | hop 1 | ... | hop L] (int64, B (1 + n1 + n1 n2 + ...) entries) with hop 0 filled; hop k
+    is written as sample_csr_weighted(hop k - 1, fans[k - 1]) under call index call_base + k - 1 and
+    g0 = rank * |hop k|.  philox: dict(seed, call_base, call_ctr, optional rank).  Returns ids.
+    CPU tensors: the host definition of the per-hop draw, hop after hop (host mode)."""
+    fans = [int(n) for n in fans]
+    assert 1 <= len(fans) <= 5 and all(n > 0 for n in fans), "sample_hops_weighted: 1..5 hops of n_samples > 0"
+    if csr.edge_cdf is None:
+        raise ValueError("sample_hops_weighted: the adjacency carries no edge weights (DeviceCSR.with_weights)")
+    B = int(B)
+    sizes = [B]
+    for n in fans:
+        sizes.append(sizes[-1] * n)
+    assert ids.dtype == torch.int64 and ids.dim() == 1 and ids.is_contiguous() and ids.numel() == sum(sizes)
+    seed, base, rank = int(philox["seed"]), int(philox.get("call_base", 0)), int(philox.get("rank", 0))
+    ctr = philox.get("call_ctr")
+    if ids.is_cuda:
+        d = nat.HopsDesc()
+        d.rowptr, d.col, d.n_rows = csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.n_rows
+        d.ids, d.B, d.n_hops = ids.data_ptr(), B, len(fans)
+        for k in range(5):
+            d.fan[k] = fans[k] if k < len(fans) else 1
+        d.max_deg, d.seed, d.call_base, d.rank = 1, seed, base, rank
+        d.call_ctr = ctr.data_ptr() if ctr is not None else None
+        d.err_flag = csr.err_flag.data_ptr()
+        nat.check(nat.lib().gsage_sample_hops_weighted(ctypes.addressof(d), _ptr(csr.edge_cdf), _stream()),
+                  "sample_hops_weighted")
+        return ids
+    off = 0
+    for k, n in enumerate(fans):
+        ph = {"seed": seed, "call_base": base + k, "g0": rank * sizes[k + 1]}
+        if ctr is not None:
+            ph["call_ctr"] = ctr
+        ids[off + sizes[k]:off + sizes[k] + sizes[k + 1]] = sample_csr_weighted(csr, ids[off:off + sizes[k]], n, ph)
+        off += sizes[k]
+    return ids
+
+
 # =============================================================================================
 # Importance neighbourhoods: visit counts of short random walks and their top-T (csrc/gsage_importance.hip)
 # =============================================================================================

@@ -86,9 +86,13 @@ list of launches on engine.FusedUnsupMeanTrainStep -- batch builder, sampler, en
 update -- and is an error, with the engine's sentence, where that engine does not cover the run.
 
 --sampler-class sparse_weighted_neighbor_sampler: neighbours drawn in proportion to edge weights (a problem file with
-`adj_weight` / `train_adj_weight`; include/gsage.h, "Weighted adjacency").  Always Philox; the module path runs it (said
-on stderr); --full-neighbour-eval / --save-embeddings compute the weight-normalised mean (mean and mean-pool models);
---unsupervised is refused: its walks are unweighted.
+`adj_weight` / `train_adj_weight`; include/gsage.h, "Weighted adjacency").  Always Philox; under --engine auto / eager
+the module path runs it (said on stderr, with the name of the engine --engine fused would select); --engine fused (opt-in,
+mean aggregators, the identity prep over a bf16 / fp32 table, one process) runs training on
+engine.FusedWeightedMeanTrainStep -- the mean engine behind one sampler launch that draws every hop from the edge
+weights (gsage_sample_hops_weighted), queue mode included -- and the validation / test folds on the same class; what
+that engine does not cover is an error with its sentence.  --full-neighbour-eval / --save-embeddings compute the
+weight-normalised mean (mean and mean-pool models); --unsupervised is refused: its walks are unweighted.
 
 --importance-walks R (with --importance-len L, --importance-top T, --importance-seed S; default off: nothing changes):
 after the problem is loaded, the training and the evaluation adjacency are each replaced by gs.importance_adj of
@@ -255,11 +259,12 @@ class FusedEvaluator(object):
     fold cut into the reference's chunks (problem.py:141-153 with shuffle=False, batch_size 512 as train.py:32 calls
     it), the validation sampler's frontier drawn from the generator -- and in the order -- the reference's evaluation
     would draw from, no autograd, no per-op launches, the metric on the device.  One engine per fold (their chunk
-    sizes differ), built on first use; a model / store no engine covers keeps the module path (said once)."""
+    sizes differ), built on first use; a model / store no engine covers keeps the module path (said once) --
+    strict=True (an engine the run asked for by name: the weighted one): what the engine refuses is an error."""
 
-    def __init__(self, cls, model, problem, wide_head=False):
+    def __init__(self, cls, model, problem, wide_head=False, strict=False):
         self.cls, self.model, self.problem, self.wide_head = cls, model, problem, bool(wide_head)
-        self.engines, self.off = {}, False
+        self.engines, self.off, self.strict = {}, False, bool(strict)
 
     def _fold(self, mode, batch_size=512):
         nodes = self.problem.nodes[mode]
@@ -289,6 +294,8 @@ class FusedEvaluator(object):
                 eng = self.engines[mode] = self.cls(model, problem.feats, problem.loss_fn, ids[0], tg, eval_only=True,
                                                     **kw)
             except Exception as e:
+                if self.strict:
+                    raise SystemExit('gsage: --engine fused: evaluation on %s: %s' % (self.cls.__name__, e))
                 self.off = True
                 print('gsage: evaluation stays on the module path (%s: %s)' % (type(e).__name__, e), file=sys.stderr)
         return eng
@@ -307,6 +314,8 @@ class FusedEvaluator(object):
         try:
             preds = eng.evaluate_fold(ids, live)
         except Exception as e:            # (e.g. a validation fan-out the forward-only engine's kernels refuse)
+            if self.strict:
+                raise SystemExit('gsage: --engine fused: evaluation on %s: %s' % (self.cls.__name__, e))
             self.off = True
             self.engines.pop(mode, None)
             print('gsage: evaluation falls back to the module path (%s: %s)' % (type(e).__name__, e), file=sys.stderr)
@@ -643,8 +652,15 @@ def choose_engine(args, problem, model, ddp):
             return give_up('chunks of fewer than two training nodes')
         return cls
     if isinstance(model.train_sampler, gs.nn_modules.SparseWeightedNeighborSampler):
-        return give_up('no fused engine covers the weighted sampler (SparseWeightedNeighborSampler)')
-    cls = gs.engine.fused_engine_for(model, problem.feats, explain=True, ddp=ddp)
+        cls = gs.engine.FusedWeightedMeanTrainStep     # opt-in: --engine fused, or the module path
+        if args.engine != 'fused':
+            return give_up('no fused engine covers the weighted sampler (SparseWeightedNeighborSampler) '
+                           '(--engine fused selects %s)' % cls.__name__)
+        why = cls.why_not(model, problem.feats, ddp)
+        if why is not None:
+            return give_up('%s: %s' % (cls.__name__, why))
+    else:
+        cls = gs.engine.fused_engine_for(model, problem.feats, explain=True, ddp=ddp)
     if cls is None:
         return give_up('no fused engine covers this model')
     if ddp is not None and args.rng != 'philox':
@@ -734,7 +750,8 @@ def train_fused(args, problem, model, ddp, start_time, cls):
         fold_eval = lambda mode='val': full_neighbour_evaluate(model, problem, mode=mode,      # noqa: E731
                                                                closure=args.eval_closure)
     elif os.environ.get("GSAGE_FUSED_EVAL", "1") == "1":
-        fold_eval = FusedEvaluator(cls, model, problem, wide_head=args.wide_head).prepare('val')
+        fold_eval = FusedEvaluator(cls, model, problem, wide_head=args.wide_head,
+                                   strict=cls is gs.engine.FusedWeightedMeanTrainStep).prepare('val')
     else:
         fold_eval = lambda mode='val': evaluate(model, problem, mode=mode)                     # noqa: E731
     # The per-batch line (train.py:150-158) without a host sync per step: batch b is scored on the device right behind
