@@ -1136,6 +1136,31 @@ int gsage_head_skipgram_live(const float *E, int64_t lde, int32_t B, int32_t Q, 
                              float neg_weight, const int32_t *n_valid, void *dE, int dE_dtype, int64_t ldd, float *loss,
                              float *aff, float *scratch, void *stream);
 
+/* gsage_unsup_batch_weighted -- gsage_unsup_batch over a weighted adjacency ("Weighted adjacency" below): one launch,
+ * the same outputs (ids, pair_w), the same call / g / err_flag conventions, shards concatenate to the one-rank draw.
+ * edge_cdf: the adjacency's table from gsage_edge_cdf_build (uint64 [nnz], aligned with col).  Only the walk's steps
+ * differ: each is drawn in proportion to the edge quanta, under a role tag of its own.
+ *   Positive of seed i (g = g0 + i):
+ *     t_i  = 1 + ((P(g, 0x4C000000)[0] * walk_len) >> 32)                        (the lengths of the unweighted batch)
+ *     v    = seeds[i];  for j = 0 .. t_i - 1:
+ *              beg = rowptr[v], end = rowptr[v + 1];   T_v = end > beg ? edge_cdf[end - 1] : 0
+ *              T_v == 0 (an empty row, or one without a drawable edge): the walk ends at v
+ *              w    = P(g, 0x5A000000 | (j >> 1));   r64 = (uint64)w[2 (j & 1)] << 32 | w[2 (j & 1) + 1]
+ *              x    = (r64 * T_v) >> 64                                           (128-bit product)
+ *              v    = col[first e in [beg, end) with edge_cdf[e] > x]             (never an edge of quantum 0)
+ *     ids[B + i] = v;  pair_w[i] = (v == seeds[i]) ? 0 : 1;  ids[i] = seeds[i];  ids outside [0, n_rows) as above.
+ *   Negatives: exactly gsage_unsup_batch's (tag 0x4E000000, the double table) -- the same Q ids for the same table,
+ *   seed and call.  The model's table gives weight 0 to a row with T_v == 0 (ops.neg_cdf(weighted=True)).
+ *   A wave per walk (four to a workgroup): the 64 lanes read a row of at most 64 edges in one round trip and ballot;
+ *   a longer row is narrowed to one sixty-fourth per round trip of 64 evenly spaced probes, ceil(log64(deg)) in all.
+ *   The table is non-decreasing inside a row, so the entry found does not depend on the probe pattern.
+ *   edge_cdf == NULL is GSAGE_EINVAL before anything is launched; walk_len, Q, B, cdf_total as for gsage_unsup_batch.
+ *   Additive; the ABI version is unchanged. */
+int gsage_unsup_batch_weighted(const int64_t *rowptr, const int32_t *col, const uint64_t *edge_cdf, int64_t n_rows,
+                               const int64_t *seeds, int64_t B, int32_t walk_len, int64_t Q, const double *cdf,
+                               double cdf_total, uint64_t seed, const uint64_t *call_ctr, uint64_t call_base, uint64_t g0,
+                               int64_t *ids, float *pair_w, int32_t *err_flag, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Weighted adjacency (csrc/gsage_weighted.hip, csrc/gsage_fullgraph.hip): edge-weight neighbour sampling and the
  * weight-normalised mean of layer-wise inference.  Additive; the ABI version is unchanged.  No reference counterpart.

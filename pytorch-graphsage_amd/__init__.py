@@ -19,9 +19,12 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
     store.WeightedAdj         edge weights: sparse_weighted_neighbor_sampler, weight-normalised full-neighbourhood mean
     store.importance_adj      any adjacency -> its importance-weighted one: visit counts of short random walks, the
                               top-T most-visited nodes per row (DeviceCSR.importance, csrc/gsage_importance.hip)
-    models.GSUnsupervised     label-free training: random-walk positives, degree^0.75 negatives, skip-gram head
+    models.GSUnsupervised     label-free training: random-walk positives, degree^0.75 negatives, skip-gram head;
+                              weighted_walks=True: over a weighted adjacency the walks draw every step by edge weight
+                              (ops.unsup_batch(weighted=True), gsage_unsup_batch_weighted)
     engine/                   the whole train_step as recorded launches (captured autograd path; fused mean /
-                              pool / attention engines on a shared base)
+                              pool / attention engines on a shared base; opt-in: the weighted mean engine and the
+                              unsupervised engines, FusedUnsupMeanTrainStep / FusedUnsupWeightedMeanTrainStep)
 """
 from . import _native, dist, engine, helpers, infer, nn_modules, ops, optim, problem, store        # noqa: F401
 from .helpers import set_seeds, to_numpy                            # noqa: F401

@@ -4,17 +4,23 @@
 // The builder is latency, not bandwidth: a lane per seed walks a chain of at most 16 dependent (rowptr -> col) loads,
 // a lane per negative walks a binary search of log2(n_rows) dependent loads; both roles share the launch.
 //
+// The weighted builder (steps drawn from a weighted adjacency's per-edge table) gives a walk to a WAVE: a step has to
+// find the first table entry above its draw, and the 64 lanes probe 64 entries of the row per round trip -- one round
+// for a row of at most 64 edges, ceil(log64(deg)) for a longer one -- instead of a lane's log2(deg) dependent probes.
+//
 // The head is k_head_ce (gsage_head.hip) with the normalised negatives in the role of fc.weight and the loss
 // exchanged: B x Q x D = 512 x 20 x 256 is 2.6 MFLOP, so the cost is launches and dependent phases, not flops.  A
 // workgroup keeps its 16 normalised seed rows in LDS, streams the negatives' rows from L2 (64 x 1024 floats do not fit
 // beside them), and leaves one partial of d z_neg per workgroup for the second launch to sum in a fixed order.
 #include "gsage_common.h"
+#include "gsage_weighted_dev.h"
 
 namespace gsage {
 
 constexpr uint32_t UNSUP_TAG_LEN = 0x4C000000u;     // walk length
 constexpr uint32_t UNSUP_TAG_STEP = 0x53000000u;    // | (step >> 2): walk steps, four to a Philox block
 constexpr uint32_t UNSUP_TAG_NEG = 0x4E000000u;     // negatives
+constexpr uint32_t UNSUP_TAG_WSTEP = 0x5A000000u;   // | (step >> 1): weighted walk steps, two to a Philox block
 constexpr int UNSUP_WALK_MAX = 16;
 
 struct UnsupParams {
@@ -22,6 +28,7 @@ struct UnsupParams {
     const int32_t *col;
     const int64_t *seeds;
     const double *cdf;
+    const uint64_t *edge_cdf;                           // the weighted builder's per-edge table (else unused)
     const uint64_t *call_ctr;
     int64_t *ids;
     float *pair_w;
@@ -37,6 +44,22 @@ __device__ __forceinline__ philox4 unsup_philox(const UnsupParams &p, uint64_t c
 {
     return philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), (uint32_t)call, (uint32_t)(call >> 32), p.seed_lo,
                          p.seed_hi ^ tag);
+}
+
+// the negatives' role of both builders: the workgroups behind the walk workgroups, a lane per negative
+__device__ __forceinline__ void unsup_negative(const UnsupParams &p, uint64_t call)
+{
+    const int64_t q = (int64_t)((int)blockIdx.x - p.walk_blocks) * 256 + threadIdx.x;
+    if (q >= p.Q) return;
+    const philox4 r = unsup_philox(p, (uint64_t)q, call, UNSUP_TAG_NEG);
+    const uint64_t u53 = ((uint64_t)r.v[0] << 21) | (uint64_t)(r.v[1] >> 11);
+    const double x = ((double)u53 * 0x1p-53) * p.cdf_total;
+    int64_t lo = 0, hi = p.n_rows - 1;                          // first i with cdf[i] > x, clamped to the last row
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (p.cdf[mid] > x) hi = mid; else lo = mid + 1;
+    }
+    p.ids[2 * p.B + q] = lo;
 }
 
 // blocks [0, walk_blocks): a lane per seed;  the rest: a lane per negative
@@ -80,19 +103,109 @@ k_unsup_batch(const UnsupParams p)
         p.pair_w[i] = v == s ? 0.f : 1.f;
         return;
     }
-    const int64_t q = (int64_t)((int)blockIdx.x - p.walk_blocks) * 256 + threadIdx.x;
-    if (q >= p.Q) return;
-    const philox4 r = unsup_philox(p, (uint64_t)q, call, UNSUP_TAG_NEG);
-    const uint64_t u53 = ((uint64_t)r.v[0] << 21) | (uint64_t)(r.v[1] >> 11);
-    const double x = ((double)u53 * 0x1p-53) * p.cdf_total;
-    int64_t lo = 0, hi = p.n_rows - 1;                          // first i with cdf[i] > x, clamped to the last row
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (p.cdf[mid] > x) hi = mid; else lo = mid + 1;
-    }
-    p.ids[2 * p.B + q] = lo;
+    unsup_negative(p, call);
 }
 
+
+// ---- weighted walks: a wave per walk ---------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t wave_uniform(int64_t x)             // a value every lane holds, made provably so
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+__device__ __forceinline__ uint64_t wave_lane_u64(uint64_t x, int src)   // lane src's x
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, src, 64);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), src, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// One weighted step by the whole wave (beg, end, r64 wave-uniform, end > beg): T = cdf[end - 1]; T == 0 -> -1 (no
+// drawable edge); else the first edge e of the row with cdf[e] > x, x = (r64 * T) >> 64.  cdf is non-decreasing inside
+// a row and cdf[end - 1] = T > x, so the answer exists.  A range of at most 64 entries: a lane per entry, one ballot.
+// A longer range [lo, hi] with cdf[hi] > x: lane l probes lo + floor((hi - lo)(l + 1) / 64) -- ascending, lane 63 is hi
+// itself, which in the first round is the row's last entry and yields T -- and the first probe above x bounds the
+// sixty-fourth of the range that holds the answer.
+__device__ __forceinline__ int64_t wave_cdf_step(const uint64_t *__restrict__ cdf, int64_t beg, int64_t end, uint64_t r64,
+                                                 int lane)
+{
+    int64_t lo = beg, hi = end - 1;
+    uint64_t x = 0;
+    bool have_x = false;
+    while (hi - lo >= 64) {
+        const int64_t span = hi - lo;
+        const uint64_t c = cdf[lo + ((span * (int64_t)(lane + 1)) >> 6)];
+        if (!have_x) {
+            const uint64_t T = wave_lane_u64(c, 63);
+            if (T == 0) return -1;
+            x = __umul64hi(r64, T);
+            have_x = true;
+        }
+        const int k = __ffsll((unsigned long long)__ballot(c > x)) - 1;       // (lane 63's probe is above x: k >= 0)
+        hi = lo + ((span * (int64_t)(k + 1)) >> 6);
+        if (k > 0) lo = lo + ((span * (int64_t)k) >> 6) + 1;
+    }
+    const int n = (int)(hi - lo) + 1;                                          // 1 .. 64 entries left
+    const uint64_t c = lane < n ? cdf[lo + lane] : 0ull;
+    if (!have_x) {
+        const uint64_t T = wave_lane_u64(c, n - 1);
+        if (T == 0) return -1;
+        x = __umul64hi(r64, T);
+    }
+    return lo + (__ffsll((unsigned long long)__ballot(lane < n && c > x)) - 1);
+}
+
+// blocks [0, walk_blocks): a wave per seed (four to a workgroup), every branch wave-uniform;  the rest: a lane per
+// negative.  Lane 0 writes the walk's three words.
+__global__ void __launch_bounds__(256)
+k_unsup_batch_weighted(const UnsupParams p)
+{
+    const uint64_t call = p.call_base + (p.call_ctr ? *p.call_ctr : 0ull);
+    if ((int)blockIdx.x >= p.walk_blocks) {
+        unsup_negative(p, call);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (i >= p.B) return;
+    const int64_t s = wave_uniform(p.seeds[i]);
+    const uint64_t g = p.g0 + (uint64_t)i;
+    if ((uint64_t)s >= (uint64_t)p.n_rows) {
+        if (lane == 0) {
+            if (p.err_flag) *p.err_flag = 1;
+            p.ids[i] = 0;
+            p.ids[p.B + i] = 0;
+            p.pair_w[i] = 0.f;
+        }
+        return;
+    }
+    const uint32_t wl = unsup_philox(p, g, call, UNSUP_TAG_LEN).v[0];
+    const int t = 1 + (int)(((uint64_t)wl * (uint64_t)(uint32_t)p.walk_len) >> 32);
+    int64_t v = s;
+    philox4 r = {};
+    bool bad = false;
+    for (int j = 0; j < t; ++j) {
+        const int64_t beg = wave_uniform(p.rowptr[v]), end = wave_uniform(p.rowptr[v + 1]);
+        if (end <= beg) break;
+        if ((j & 1) == 0) r = unsup_philox(p, g, call, UNSUP_TAG_WSTEP | (uint32_t)(j >> 1));
+        const int64_t e = wave_uniform(wave_cdf_step(p.edge_cdf, beg, end, philox_r64(r, (j & 1) != 0), lane));
+        if (e < 0) break;
+        v = wave_uniform((int64_t)p.col[e]);
+        if ((uint64_t)v >= (uint64_t)p.n_rows) {
+            bad = true;
+            v = 0;
+            break;
+        }
+    }
+    if (lane == 0) {
+        if (bad && p.err_flag) *p.err_flag = 1;
+        p.ids[i] = s;
+        p.ids[p.B + i] = v;
+        p.pair_w[i] = v == s ? 0.f : 1.f;
+    }
+}
 
 // ---- skip-gram head ------------------------------------------------------------------------------------------------
 constexpr int SG_QMAX = 64;        // negatives
@@ -416,9 +529,31 @@ int gsage_unsup_batch(const int64_t *rowptr, const int32_t *col, int64_t n_rows,
     p.rowptr = rowptr; p.col = col; p.seeds = seeds; p.cdf = cdf; p.call_ctr = call_ctr; p.ids = ids; p.pair_w = pair_w;
     p.err_flag = err_flag; p.n_rows = n_rows; p.B = B; p.Q = Q; p.call_base = call_base; p.g0 = g0;
     p.cdf_total = cdf_total; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
-    p.walk_len = walk_len; p.walk_blocks = (int32_t)ceil_div(B, 256);
+    p.walk_len = walk_len; p.walk_blocks = (int32_t)ceil_div(B, 256); p.edge_cdf = nullptr;
     launch(k_unsup_batch, dim3((unsigned)(p.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("unsup_batch");
+}
+
+int gsage_unsup_batch_weighted(const int64_t *rowptr, const int32_t *col, const uint64_t *edge_cdf, int64_t n_rows,
+                               const int64_t *seeds, int64_t B, int32_t walk_len, int64_t Q, const double *cdf,
+                               double cdf_total, uint64_t seed, const uint64_t *call_ctr, uint64_t call_base, uint64_t g0,
+                               int64_t *ids, float *pair_w, int32_t *err_flag, void *stream)
+{
+    GSAGE_REQUIRE(rowptr && col && seeds && cdf && ids && pair_w, "unsup_batch_weighted: null pointer");
+    GSAGE_REQUIRE(edge_cdf, "unsup_batch_weighted: the adjacency carries no edge weights (edge_cdf is NULL)");
+    GSAGE_REQUIRE(n_rows > 0 && B > 0 && B < (1LL << 31) && Q > 0 && Q < (1LL << 31), "unsup_batch_weighted: bad sizes");
+    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= UNSUP_WALK_MAX, "unsup_batch_weighted: needs 1 <= walk_len <= %d",
+                  UNSUP_WALK_MAX);
+    GSAGE_REQUIRE(cdf_total > 0.0 && cdf_total <= 1.7976931348623157e308,
+                  "unsup_batch_weighted: the negatives' weights sum to %g (every row has weight 0?)", cdf_total);
+    UnsupParams p;
+    p.rowptr = rowptr; p.col = col; p.seeds = seeds; p.cdf = cdf; p.edge_cdf = edge_cdf; p.call_ctr = call_ctr;
+    p.ids = ids; p.pair_w = pair_w; p.err_flag = err_flag; p.n_rows = n_rows; p.B = B; p.Q = Q; p.call_base = call_base;
+    p.g0 = g0; p.cdf_total = cdf_total; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
+    p.walk_len = walk_len; p.walk_blocks = (int32_t)ceil_div(B, 4);              // a wave per walk, four to a workgroup
+    launch(k_unsup_batch_weighted, dim3((unsigned)(p.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream,
+           p);
+    return check_launch("unsup_batch_weighted");
 }
 
 int64_t gsage_head_skipgram_scratch(int32_t B, int32_t Q, int32_t D)

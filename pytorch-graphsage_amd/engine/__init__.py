@@ -9,6 +9,10 @@ engine -- the whole train_step (reference models.py:97-104) as recorded launches
   attn.FusedAttnTrainStep      attention aggregators, optionally over trainable node embeddings (configs[3])
   unsup.FusedUnsupMeanTrainStep  GSUnsupervised under mean aggregators: builder, encoder, skip-gram head, update
                                (opt-in: train.py --unsupervised --engine fused; not one of ENGINES, whose call takes targets)
+  unsup.FusedUnsupWeightedMeanTrainStep  FusedUnsupMeanTrainStep over a weighted adjacency: the builder's walk steps
+                               (gsage_unsup_batch_weighted) and every hop (gsage_sample_hops_weighted) drawn from the
+                               per-edge cdf table (opt-in: train.py --unsupervised --weighted-walks --engine fused; not
+                               one of ENGINES)
   weighted.FusedWeightedMeanTrainStep  the mean engine over a weighted adjacency: every hop drawn from the per-edge
                                cdf table by one sampler launch of its own (gsage_sample_hops_weighted), everything
                                behind it the mean engine's (opt-in: train.py --engine fused with the weighted sampler;
@@ -23,7 +27,7 @@ from .common import FusedTrainStep, _PrepDesc, _ReduceDesc   # noqa: F401
 from .mean import FusedMeanTrainStep
 from .pool import FusedPoolTrainStep
 from .attn import FusedAttnTrainStep
-from .unsup import FusedUnsupMeanTrainStep                   # noqa: F401
+from .unsup import FusedUnsupMeanTrainStep, FusedUnsupWeightedMeanTrainStep   # noqa: F401
 from .weighted import FusedWeightedMeanTrainStep             # noqa: F401
 
 ENGINES = (FusedMeanTrainStep, FusedPoolTrainStep, FusedAttnTrainStep)

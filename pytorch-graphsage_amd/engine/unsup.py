@@ -5,7 +5,12 @@ its fused seed level, the skip-gram head with a live-seed count, backward, final
 
 The encoder sees one batch of R = 2B + Q rows [seeds | positives | negatives]: that IS the base engine's batch
 (self.B = R; size / off / fan follow), so every launch between the sampler and the update is the mean engine's own.
+
+FusedUnsupWeightedMeanTrainStep: the same step over a weighted adjacency (GSUnsupervised(weighted_walks=True)): the
+builder's steps and every hop of the frontier are drawn from the adjacency's per-edge table.
 """
+import ctypes
+
 import torch
 
 from .. import _native as nat
@@ -13,6 +18,7 @@ from .. import ops
 from ..nn_modules import MeanAggregator, NodeEmbeddingPrep, SparseUniformNeighborSampler, \
     SparseWeightedNeighborSampler, UniformNeighborSampler, _split_activation
 from .mean import FusedMeanTrainStep
+from .weighted import FusedWeightedMeanTrainStep
 
 
 class FusedUnsupMeanTrainStep(FusedMeanTrainStep):
@@ -205,3 +211,86 @@ class FusedUnsupMeanTrainStep(FusedMeanTrainStep):
         self.model._batch_calls[1] += 1
         self._ctr_host = want + 1
         return self.loss.view(())
+
+
+class FusedUnsupWeightedMeanTrainStep(FusedUnsupMeanTrainStep):
+    """FusedUnsupMeanTrainStep for a GSUnsupervised(weighted_walks=True) whose samplers are
+    SparseWeightedNeighborSampler: same constructor, same `__call__(seeds)`.  Two launches differ:
+
+        builder       gsage_unsup_batch_weighted: every step of a walk drawn from the adjacency's edge_cdf
+        K1w           gsage_sample_hops_weighted, a launch of its own (as in FusedWeightedMeanTrainStep)
+
+    Step t builds the batch the model's `build_batch` would build at that point of its stream and draws hop k with the
+    call index a SparseWeightedNeighborSampler consumes on the module path, so both paths see the same id batch, the
+    same pair_w and the same frontier.  Opt-in (train.py --unsupervised --weighted-walks --engine fused): not one of
+    engine.ENGINES."""
+
+    TIMED = dict(FusedUnsupMeanTrainStep.TIMED, sampler=(14, 15))
+
+    @classmethod
+    def why_not(cls, model, feats, ddp=None, pipelined=False, eval_only=False):
+        """None, or one sentence: what of (model, feats, mode) this engine does not cover -- the sentences of
+        FusedUnsupMeanTrainStep and FusedWeightedMeanTrainStep, the model's first, the feature store's last."""
+        from ..models import GSUnsupervised
+        if not isinstance(model, GSUnsupervised):
+            return "a model that is not GSUnsupervised (%s: the supervised engines train it)" % type(model).__name__
+        if not getattr(model, "weighted_walks", False):
+            return ("a GSUnsupervised with weighted_walks=False: its walks take uniform steps "
+                    "(FusedUnsupMeanTrainStep runs them over a uniform sampler)")
+        layers = list(model.agg_layers.children())
+        if not layers or any(type(l) is not MeanAggregator for l in layers):
+            return ("aggregators other than mean (%s): the pool, attention and LSTM aggregators have no unsupervised "
+                    "engine" % ", ".join(sorted({type(l).__name__ for l in layers})))
+        if isinstance(model.prep, NodeEmbeddingPrep):
+            return "the node_embedding prep (a trainable table under the skip-gram loss has no fused form)"
+        for s in (model.train_sampler, model.val_sampler):
+            if not isinstance(s, SparseWeightedNeighborSampler):
+                return ("a train / validation sampler that is not SparseWeightedNeighborSampler (%s: "
+                        "FusedUnsupMeanTrainStep covers the uniform sparse sampler)" % type(s).__name__)
+        if ddp is not None:
+            return "a data-parallel handle: the unsupervised engine runs in one process"
+        if pipelined:
+            return "pipelined=True: the unsupervised engine runs one batch at a time"
+        if eval_only:
+            return "eval_only=True: there is no evaluation engine for the unsupervised model (model.evaluate runs it)"
+        why = cls._why_not_common(model, feats, (MeanAggregator,), "mean", sampler=False)
+        if why:
+            return why
+        if not all(l.output_dim_ % 8 == 0 for l in layers):
+            return "output dims that are not multiples of 8"
+        post = _split_activation(layers[-1].activation)[1]
+        probe = torch.linspace(-2.0, 2.0, 12).view(3, 4)
+        if post is not None and not torch.equal(post(probe), probe):
+            return "an activation on the last layer other than the identity"
+        if int(model.output_dim) > 1024 or not 1 <= int(model.n_negatives) <= 64:
+            return "an embedding wider than 1024 or more than 64 negatives (the skip-gram head's limits)"
+        return cls._why_not_input(model, feats, None, concat_ok=False, fp8_ok=False)
+
+    # ---- stages ----------------------------------------------------------------------------------------------------
+    def _stage_batch(self, s):
+        """gsage_unsup_batch_weighted: the seed buffer -> the first R ids of the frontier buffer + pair_w"""
+        csr, cdf, m = self.walk_csr, self.cdf, self.model
+        self._time_next(*self.TIMED["builder"])
+        nat.check(nat.lib().gsage_unsup_batch_weighted(
+            csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.edge_cdf.data_ptr(), csr.n_rows, self.seeds.data_ptr(),
+            self.Bs, m.walk_len, self.Q, cdf.data_ptr(), cdf._gsage_total, int(getattr(self.sampler, "seed", 0)),
+            self.batch_ctr.data_ptr(), self._call_base, 0, self.ids_set[s].data_ptr(), self.pair_w.data_ptr(),
+            csr.err_flag.data_ptr(), ops._stream()), "unsup_batch_weighted")
+
+    def _stage_sample(self, s, ids=None, ahead=False, counters=None):
+        """K1w: every hop in one launch, drawn from the adjacency's edge_cdf (FusedWeightedMeanTrainStep's stage)"""
+        d = self._hops_desc(self.ids_set[s] if ids is None else ids, ahead, counters)
+        self._time_next(*self.TIMED["sampler"])
+        nat.check(nat.lib().gsage_sample_hops_weighted(ctypes.addressof(d), self.csr.edge_cdf.data_ptr(), ops._stream()),
+                  "sample_hops_weighted")
+
+    _k1_own_launch = FusedWeightedMeanTrainStep._k1_own_launch
+    _k1_in_k5 = FusedWeightedMeanTrainStep._k1_in_k5
+    _k1_in_tail = FusedWeightedMeanTrainStep._k1_in_tail
+    _k1_early = FusedWeightedMeanTrainStep._k1_early
+
+    def load_epoch(self, *a, **k):
+        raise ValueError("FusedUnsupWeightedMeanTrainStep runs one batch per call: there is no queue mode")
+
+    def step_queue(self, *a, **k):
+        raise ValueError("FusedUnsupWeightedMeanTrainStep runs one batch per call: there is no queue mode")

@@ -19,6 +19,7 @@ import os
 
 from . import ops
 from .lr import LRSchedule
+from .nn_modules import UniformNeighborSampler
 from .optim import FlatAdam
 from .store import DenseAdj, DeviceCSR, FeatureStore
 
@@ -206,22 +207,35 @@ class GSUnsupervised(_SageModel):
 
     A step encodes [seeds (B) | positives (B) | negatives (Q)] in ONE pass of the module path.  The walks run on the
     adjacency the step's sampler walks (train_adj for training, adj for evaluation) and draw from Philox under the
-    neighbour sampler's seed with role tags of their own, whatever --rng the neighbour sampler uses."""
+    neighbour sampler's seed with role tags of their own, whatever --rng the neighbour sampler uses.
+
+    weighted_walks=True (a sampler over a weighted adjacency: SparseWeightedNeighborSampler): every step of a walk is
+    drawn in proportion to the edge weights (gsage_unsup_batch_weighted), so the positives follow the neighbourhoods the
+    encoder aggregates over, in training and in evaluate alike, and a row without a drawable edge is never a negative.
+    False: uniform steps over the stored edges, whatever the sampler."""
 
     def __init__(self, input_dim, n_nodes, layer_specs, aggregator_class, prep_class, sampler_class, adj, train_adj,
                  lr_init=0.01, weight_decay=0.0, lr_schedule='constant', epochs=10, walk_len=5, n_negatives=20,
-                 neg_weight=1.0):
+                 neg_weight=1.0, weighted_walks=False):
         super(GSUnsupervised, self).__init__()
         assert 1 <= walk_len <= 16 and 1 <= n_negatives <= 64, "GSUnsupervised: walk_len in 1..16, n_negatives in 1..64"
         self.output_dim = self._build_encoder(input_dim, n_nodes, layer_specs, aggregator_class, prep_class,
                                               sampler_class, adj, train_adj)
         self.walk_len, self.n_negatives, self.neg_weight = int(walk_len), int(n_negatives), float(neg_weight)
+        self.weighted_walks = bool(weighted_walks)
+        if self.weighted_walks:
+            for s in (self.train_sampler, self.val_sampler):
+                host = None if isinstance(s, UniformNeighborSampler) else s.csr("cpu")
+                if getattr(host, "edge_cdf", None) is None:
+                    raise ValueError("GSUnsupervised: weighted_walks=True needs a sampler over a weighted adjacency "
+                                     "(SparseWeightedNeighborSampler), not %s" % type(s).__name__)
         self._build_optimizer(lr_init, weight_decay, lr_schedule)
         self._walk = {}                       # (train, device) -> (DeviceCSR, negatives' table)
         self._batch_calls = [0, 0]            # Philox call index of the next batch: evaluation, training
 
     def extra_repr(self):
-        return "walk_len=%d, n_negatives=%d, neg_weight=%g" % (self.walk_len, self.n_negatives, self.neg_weight)
+        return "walk_len=%d, n_negatives=%d, neg_weight=%g%s" % (self.walk_len, self.n_negatives, self.neg_weight,
+                                                                   ", weighted_walks=True" if self.weighted_walks else "")
 
     def forward(self, ids, feats, train=True):
         return F.normalize(self._encode(ids, feats, train), dim=1)
@@ -234,7 +248,10 @@ class GSUnsupervised(_SageModel):
             if isinstance(csr, DenseAdj):     # the dense sampler's [n, K] table read as K edges per row
                 rowptr = torch.arange(csr.n_rows + 1, dtype=torch.int64, device=csr.device) * csr.K
                 csr = DeviceCSR(rowptr, csr.adj.reshape(-1).to(torch.int32), csr.n_rows, csr.K)
-            self._walk[key] = (csr, ops.neg_cdf(csr))
+            if self.weighted_walks and getattr(csr, "edge_cdf", None) is None:
+                raise ValueError("GSUnsupervised: weighted_walks=True, but the sampler's adjacency carries no edge "
+                                 "weights")
+            self._walk[key] = (csr, ops.neg_cdf(csr, weighted=self.weighted_walks))
         return self._walk[key]
 
     def build_batch(self, ids, train=True):
@@ -246,7 +263,7 @@ class GSUnsupervised(_SageModel):
         ph = {"seed": int(getattr(sampler, "seed", 0)), "call_base": self._batch_calls[int(train)],
               "g0": rank * int(ids.shape[0])}
         self._batch_calls[int(train)] += 1
-        return ops.unsup_batch(csr, ids, self.walk_len, self.n_negatives, cdf, ph)
+        return ops.unsup_batch(csr, ids, self.walk_len, self.n_negatives, cdf, ph, weighted=self.weighted_walks)
 
     def _loss_inputs(self, ids, feats, batch, train):
         all_ids, pair_w = batch if batch is not None else self.build_batch(ids, train=train)

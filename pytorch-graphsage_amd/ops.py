@@ -589,6 +589,7 @@ def importance_compact(col, w, deg):
 # Unsupervised batches: random-walk positives + degree^0.75 negatives (csrc/gsage_unsup.hip)
 # =============================================================================================
 UNSUP_TAG_LEN, UNSUP_TAG_STEP, UNSUP_TAG_NEG = 0x4C000000, 0x53000000, 0x4E000000     # include/gsage.h
+UNSUP_TAG_WSTEP = 0x5A000000                                                          # weighted steps, two to a block
 
 
 def _philox4(ctr, key):
@@ -603,20 +604,33 @@ def _philox4(ctr, key):
     return c0, c1, c2, c3
 
 
-def neg_cdf(csr):
+def neg_cdf(csr, weighted=False):
     """The negatives' table of gsage_unsup_batch for `csr`: float64 inclusive running sum of degree^0.75, on the
-    adjacency's device (set-up, once per adjacency).  Its last element is read to the host here, once."""
+    adjacency's device (set-up, once per adjacency).  Its last element is read to the host here, once.
+    weighted=True (the table of gsage_unsup_batch_weighted; csr carries an edge_cdf): a row without a drawable edge
+    (T_v == 0) behaves everywhere as a row of degree 0, so it gets weight 0; every other row keeps degree^0.75 of its
+    stored degree."""
     deg = (csr.rowptr[1:] - csr.rowptr[:-1]).to(torch.float64)
+    if weighted:
+        if csr.edge_cdf is None:
+            raise ValueError("neg_cdf: weighted=True needs an adjacency with edge weights (DeviceCSR.with_weights)")
+        if csr.nnz:
+            last = (csr.rowptr[1:] - 1).clamp(min=0)           # (an empty row reads some entry: its degree is 0 anyway)
+            deg = torch.where(csr.edge_cdf[last] != 0, deg, torch.zeros_like(deg))
     cdf = torch.cumsum(deg.clamp(min=0).pow(0.75), 0).contiguous()
     cdf._gsage_total = float(cdf[-1].item())
     return cdf
 
 
-def unsup_batch(csr, seeds, walk_len, Q, cdf, philox):
+def unsup_batch(csr, seeds, walk_len, Q, cdf, philox, weighted=False):
     """The id batch of one unsupervised step (include/gsage.h, gsage_unsup_batch): -> (ids int64 [2B + Q] =
     [seeds | random-walk positives | negatives], pair_w fp32 [B]: 0 where a walk ended on its own seed).
     cdf: neg_cdf(csr) (any float64 inclusive running sum of row weights will do); philox: dict(seed, call_base,
-    g0, call_ctr) as for sample_csr.  CPU tensors: the same definition in numpy / Python integers (host mode)."""
+    g0, call_ctr) as for sample_csr.  weighted=True: every step is drawn in proportion to the edge quanta of
+    csr.edge_cdf (gsage_unsup_batch_weighted; cdf: neg_cdf(csr, weighted=True)).
+    CPU tensors: the same definition in numpy / Python integers (host mode)."""
+    if weighted and csr.edge_cdf is None:
+        raise ValueError("unsup_batch: weighted=True needs an adjacency with edge weights (DeviceCSR.with_weights)")
     seeds = seeds.contiguous().view(-1)
     B, Q, walk_len = int(seeds.shape[0]), int(Q), int(walk_len)
     total = getattr(cdf, "_gsage_total", None)
@@ -628,6 +642,12 @@ def unsup_batch(csr, seeds, walk_len, Q, cdf, philox):
         assert cdf.dtype == torch.float64 and cdf.is_cuda and cdf.is_contiguous() and cdf.numel() == csr.n_rows
         ids = torch.empty(2 * B + Q, dtype=torch.int64, device=seeds.device)
         pair_w = torch.empty(B, dtype=torch.float32, device=seeds.device)
+        if weighted:
+            nat.check(nat.lib().gsage_unsup_batch_weighted(
+                _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.edge_cdf), csr.n_rows, _ptr(seeds), B, walk_len, Q, _ptr(cdf),
+                total, seed, _ptr(ctr), base, g0, _ptr(ids), _ptr(pair_w), _ptr(csr.err_flag), _stream()),
+                "unsup_batch_weighted")
+            return ids, pair_w
         nat.check(nat.lib().gsage_unsup_batch(_ptr(csr.rowptr), _ptr(csr.col), csr.n_rows, _ptr(seeds), B, walk_len, Q,
                                               _ptr(cdf), total, seed, _ptr(ctr), base, g0, _ptr(ids), _ptr(pair_w),
                                               _ptr(csr.err_flag), _stream()), "unsup_batch")
@@ -641,6 +661,7 @@ def unsup_batch(csr, seeds, walk_len, Q, cdf, philox):
     clo, chi = call & 0xFFFFFFFF, call >> 32
     klo, khi = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
     rp, col, sd, n_rows = csr.rowptr.numpy(), csr.col.numpy(), seeds.numpy(), csr.n_rows
+    ecdf = csr.edge_cdf.numpy().view(np.uint64) if weighted else None
     if sd.min() < 0 or sd.max() >= n_rows:
         raise IndexError("unsup_batch: node id out of range of the adjacency")
     ids = np.zeros(2 * B + Q, dtype=np.int64)
@@ -655,10 +676,19 @@ def unsup_batch(csr, seeds, walk_len, Q, cdf, philox):
             deg = int(rp[v + 1]) - beg
             if deg <= 0:
                 break
-            if j & 3 == 0:
-                r = _philox4(c, (klo, khi ^ (UNSUP_TAG_STEP | (j >> 2))))
-            word = r[j & 3]
-            v = int(col[beg + ((word * deg) >> 32 if deg <= 0xFFFFFFFF else word)])
+            if weighted:
+                T = int(ecdf[beg + deg - 1])
+                if T == 0:
+                    break
+                if j & 1 == 0:
+                    r = _philox4(c, (klo, khi ^ (UNSUP_TAG_WSTEP | (j >> 1))))
+                x = (((r[2 * (j & 1)] << 32) | r[2 * (j & 1) + 1]) * T) >> 64
+                v = int(col[beg + int(np.searchsorted(ecdf[beg:beg + deg], np.uint64(x), side="right"))])
+            else:
+                if j & 3 == 0:
+                    r = _philox4(c, (klo, khi ^ (UNSUP_TAG_STEP | (j >> 2))))
+                word = r[j & 3]
+                v = int(col[beg + ((word * deg) >> 32 if deg <= 0xFFFFFFFF else word)])
             if v < 0 or v >= n_rows:
                 raise IndexError("unsup_batch: node id out of range of the adjacency")
         ids[i], ids[B + i], pair_w[i] = sd[i], v, 0.0 if v == sd[i] else 1.0

@@ -92,7 +92,18 @@ mean aggregators, the identity prep over a bf16 / fp32 table, one process) runs 
 engine.FusedWeightedMeanTrainStep -- the mean engine behind one sampler launch that draws every hop from the edge
 weights (gsage_sample_hops_weighted), queue mode included -- and the validation / test folds on the same class; what
 that engine does not cover is an error with its sentence.  --full-neighbour-eval / --save-embeddings compute the
-weight-normalised mean (mean and mean-pool models); --unsupervised is refused: its walks are unweighted.
+weight-normalised mean (mean and mean-pool models); --unsupervised is refused unless --weighted-walks is given (its
+walks would otherwise take uniform steps over a graph the encoder reads by weight).
+
+--weighted-walks (default off: nothing changes; with --unsupervised and the weighted sampler, asked for by name or
+reached through --importance-walks): the positives' random walks draw every step in proportion to the edge weights
+(models.GSUnsupervised(weighted_walks=True), gsage_unsup_batch_weighted), on the training graph and -- in the
+validation / test lines -- on the evaluation graph, and a row without a drawable edge is never a negative.  The module
+path runs it under --engine auto / eager; --engine fused runs engine.FusedUnsupWeightedMeanTrainStep -- the weighted
+builder and gsage_sample_hops_weighted in front of the unsupervised mean engine -- or exits with that engine's
+sentence.  --save-embeddings / --save-neighbours / --link-eval / --probe then compute the weight-normalised mean, as
+after a supervised weighted run.  Without --unsupervised, or with a sampler that is not the weighted one, the flag is
+an error.
 
 --importance-walks R (with --importance-len L, --importance-top T, --importance-seed S; default off: nothing changes):
 after the problem is loaded, the training and the evaluation adjacency are each replaced by gs.importance_adj of
@@ -354,7 +365,8 @@ def parse_args(argv=None):
     parser.add_argument('--engine', type=str, default='auto', choices=['auto', 'eager', 'fused'],
                         help='auto: a fused engine where one covers the run, else the module path (said on stderr); '
                              'eager: the module path; fused: an engine or an error.  --unsupervised runs on the module '
-                             'path unless --engine fused asks for FusedUnsupMeanTrainStep (needs --rng philox)')
+                             'path unless --engine fused asks for FusedUnsupMeanTrainStep (needs --rng philox; with '
+                             '--weighted-walks: FusedUnsupWeightedMeanTrainStep)')
     parser.add_argument('--feature-dtype', type=str, default='native', choices=['native', 'fp8'])
     parser.add_argument('--wide-head', action="store_true",
                         help='fuse the multilabel head (2..128 labels) and cross-entropy over 65..128 classes '
@@ -378,6 +390,9 @@ def parse_args(argv=None):
     parser.add_argument('--walk-len', type=int, default=5)
     parser.add_argument('--n-negatives', type=int, default=20)
     parser.add_argument('--neg-weight', type=float, default=1.0)
+    parser.add_argument('--weighted-walks', action="store_true",
+                        help='with --unsupervised and the weighted sampler: the walks draw every step in proportion to '
+                             'the edge weights (gsage_unsup_batch_weighted)')
     parser.add_argument('--importance-walks', type=int, default=0,
                         help='rebuild both adjacencies from this many random walks per node (gs.importance_adj) and '
                              'train with the weighted sampler; 0 (default): off')
@@ -444,7 +459,7 @@ def build_model(args, problem):
         weight_decay=args.weight_decay)
     if args.unsupervised:
         return gs.GSUnsupervised(walk_len=args.walk_len, n_negatives=args.n_negatives, neg_weight=args.neg_weight,
-                                 **common)
+                                 weighted_walks=args.weighted_walks, **common)
     return GSSupervised(n_classes=problem.n_classes, **common)
 
 
@@ -480,6 +495,8 @@ def main(argv=None, problem=None):
 
     if args.unsupervised and args.wide_head:
         raise SystemExit('gsage: --unsupervised: --wide-head fuses a supervised head; there is none')
+    if args.weighted_walks and not args.unsupervised:
+        raise SystemExit('gsage: --weighted-walks: the walks belong to --unsupervised training (add --unsupervised)')
     if args.unsupervised and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("GSAGE_FORCE_DDP", "0") == "1"):
         raise SystemExit('gsage: --unsupervised: data-parallel training is not supported (run a single process)')
     ddp = gs.dist.init_from_env(args.cuda)            # no-op outside torch.distributed.run
@@ -496,8 +513,12 @@ def main(argv=None, problem=None):
         if not (isinstance(problem.adj, gs.store.WeightedAdj) and isinstance(problem.train_adj, gs.store.WeightedAdj)):
             raise SystemExit('gsage: --sampler-class sparse_weighted_neighbor_sampler: this problem has no edge weights '
                              '(adj_weight / train_adj_weight)')
-        if args.unsupervised:
-            raise SystemExit('gsage: --unsupervised: the weighted sampler is not supported (random walks are unweighted)')
+        if args.unsupervised and not args.weighted_walks:
+            raise SystemExit('gsage: --unsupervised: the weighted sampler is not supported (random walks are unweighted; '
+                             '--weighted-walks draws their steps from the edge weights)')
+    elif args.weighted_walks:
+        raise SystemExit('gsage: --weighted-walks: needs the weighted sampler (--sampler-class '
+                         'sparse_weighted_neighbor_sampler, or --importance-walks), not %s' % args.sampler_class)
     if args.feature_dtype == 'fp8':
         if problem.feats is None:
             raise SystemExit('gsage: --feature-dtype fp8: this problem has no feature table')
@@ -516,7 +537,7 @@ def main(argv=None, problem=None):
             raise SystemExit('gsage: --unsupervised: --full-neighbour-eval scores logits; there are none')
         if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
             try:
-                gs.infer.check_supported(model)
+                gs.infer.check_supported(model, model.val_sampler.csr('cpu') if weighted else None)
             except ValueError as e:
                 raise SystemExit('gsage: --save-embeddings / --save-neighbours / --link-eval / --probe: %s' % e)
         set_seeds(args.seed ** 2)
@@ -587,8 +608,8 @@ def evaluate_unsupervised(model, problem, mode='val'):
 
 def train_unsupervised(args, problem, model):
     """The --unsupervised run, one JSON line per batch: GSUnsupervised.train_step on the module path, or -- with
-    --engine fused -- the same step on engine.FusedUnsupMeanTrainStep (the batches are the reference's chunks either
-    way; the engine pads the short ones and gives the padding no loss)."""
+    --engine fused -- the same step on engine.FusedUnsupMeanTrainStep (--weighted-walks: FusedUnsupWeightedMeanTrainStep;
+    the batches are the reference's chunks either way; the engine pads the short ones and gives the padding no loss)."""
     cls = choose_engine(args, problem, model, None)    # (None: says on stderr that the module path runs)
     eng = None
     if cls is not None:
@@ -643,10 +664,10 @@ def choose_engine(args, problem, model, ddp):
     if args.unsupervised:                           # the engine is opt-in: --engine fused, or the module path
         if args.engine != 'fused':
             return give_up('unsupervised model')
-        cls = gs.engine.FusedUnsupMeanTrainStep
+        cls = gs.engine.FusedUnsupWeightedMeanTrainStep if args.weighted_walks else gs.engine.FusedUnsupMeanTrainStep
         why = cls.why_not(model, problem.feats, ddp)
         if why is not None:
-            return give_up(why)
+            return give_up('%s: %s' % (cls.__name__, why) if args.weighted_walks else why)
         nodes = problem.nodes['train']
         if nodes.shape[0] // (nodes.shape[0] // args.batch_size + 1) < 2:
             return give_up('chunks of fewer than two training nodes')
