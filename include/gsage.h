@@ -1222,6 +1222,49 @@ int gsage_segment_reduce_weighted(const void *table, int dtype, int64_t ld, int6
                                   int out_dtype, int64_t out_ld, int act, int32_t *err_flag, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Distinct neighbours (csrc/gsage_distinct.hip): neighbour sampling WITHOUT replacement over a device CSR.  Additive;
+ * the ABI version is unchanged.  No reference counterpart (its sparse sampler computes row[sel % deg]).
+ *
+ * One sampler call with n samples per parent, 1 <= n <= 256.  The global sample index is g = g0 + i*n + j (parent i,
+ * slot j in 0..n-1), the call index call = call_base + (call_ctr ? *call_ctr : 0)   (as gsage_sample_csr_philox):
+ *     w(g) = philox4x32_10({lo(g>>2), hi(g>>2), lo(call), hi(call)}, {lo(seed), hi(seed) ^ 0x44000000})[g & 3]
+ * -- the uniform sampler's addressing under a key tag of its own: neither the uniform nor the weighted stream.
+ * For parent v = ids[i] with beg = rowptr[v], deg = rowptr[v+1] - beg and w_j = w(g0 + i*n + j):
+ *     v outside [0, n_rows)   all n outputs are 0 and *err_flag (may be NULL) is set to 1
+ *     deg <= 0                all n outputs are the dummy 0
+ *     deg >= 2^32             the outputs are 0 and *err_flag is set to 1 (so that the arithmetic below is 64-bit exact)
+ *     deg <= n                every neighbour, balanced:   r = (w_0 * deg) >> 32;   out[j] = col[beg + (j + r) % deg]
+ *                             -- every stored edge appears floor(n/deg) or ceil(n/deg) times, the edges with the extra
+ *                             copy a cyclic window with a uniform start: each edge is expected n/deg times, the plain
+ *                             mean over the slots is an unbiased estimate of the row's mean and, when deg divides n, IS
+ *                             the row's mean
+ *     deg >  n                n distinct edges, uniformly random as an ordered tuple: a partial Fisher-Yates shuffle
+ *                             over a virtual array a[x] = x,
+ *                                 for j in 0..n-1:   t_j = j + ((w_j * (deg - j)) >> 32)          in [j, deg)
+ *                                                    off[j] = a[t_j];   a[t_j] = a[j]             (a[j] read first)
+ *                                 out[j] = col[beg + off[j]]
+ *                             Per slot, from t_0 .. t_j alone: x = t_j, bound = j; repeat { the largest i < bound with
+ *                             t_i == x; none: stop; else x = i, bound = i }; off[j] = x.
+ * "Distinct" means distinct STORED EDGES: a row that stores a column twice can return it twice.
+ *
+ * gsage_sample_csr_distinct -- one launch per hop: out int64 [M * n].  n outside 1..256, a negative size or a null
+ * pointer give GSAGE_EINVAL without a launch; M == 0 returns GSAGE_OK without one.
+ *
+ * gsage_sample_hops_distinct -- every hop of a frontier in ONE launch: gsage_sample_hops' descriptor, geometry (a
+ * 256-lane workgroup walks the sub-tree of its seeds, the previous hop in LDS) and queue fields.  Hop k uses call index
+ * call_base + (call_ctr ? *call_ctr : 0) + (k - 1) and g0 = rank * |hop k|: the frontier is bit-identical to n_hops
+ * launches of gsage_sample_csr_distinct.  seed_queue / batch_idx / batch_base / n_batches as in gsage_sample_hops.
+ * max_deg is ignored.  hops == NULL, sel != NULL, dense_adj != NULL, n_hops outside 1..5, a fan-out outside 1..256 and a
+ * frontier that does not fit the LDS (16 bytes per id of the widest hop of a workgroup's seeds, plus 2 KiB) give
+ * GSAGE_EINVAL without a launch (and without a GPU), the message naming the argument; B == 0 returns GSAGE_OK without
+ * one.  Both entries can be recorded in a command list.
+ * ---------------------------------------------------------------------------------------- */
+int gsage_sample_csr_distinct(const int64_t *rowptr, const int32_t *col, int64_t n_rows, const int64_t *ids, int64_t M,
+                              int32_t n, uint64_t seed, const uint64_t *call_ctr, uint64_t call_base, uint64_t g0,
+                              int64_t *out, int32_t *err_flag, void *stream);
+int gsage_sample_hops_distinct(const gsage_hops_desc *hops, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance neighbourhoods (csrc/gsage_importance.hip): a node's most-visited nodes under short random walks become
  * its neighbourhood, the visit counts its edge weights (the construction PinSAGE introduced).  What turns ANY
  * adjacency into a weighted one for everything under "Weighted adjacency".  Additive; the ABI version is unchanged.

@@ -193,6 +193,8 @@ SIGNATURES = {
     "gsage_edge_cdf_build": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "gsage_sample_csr_weighted": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _u64, _vp, _u64, _u64, _vp, _vp, _vp]),
     "gsage_sample_hops_weighted": (_int, [_vp, _vp, _vp]),
+    "gsage_sample_csr_distinct": (_int, [_vp, _vp, _i64, _vp, _i64, _i32, _u64, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "gsage_sample_hops_distinct": (_int, [_vp, _vp]),
     "gsage_segment_reduce_weighted": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                              _i32, _vp, _i64, _vp, _int, _i64, _int, _vp, _vp]),
     "gsage_importance_walks": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _u64, _vp, _vp, _vp, _vp, _vp]),

@@ -17,6 +17,10 @@ engine -- the whole train_step (reference models.py:97-104) as recorded launches
                                cdf table by one sampler launch of its own (gsage_sample_hops_weighted), everything
                                behind it the mean engine's (opt-in: train.py --engine fused with the weighted sampler;
                                not one of ENGINES: fused_engine_for / why_no_fused_engine answer as without it)
+  distinct.FusedDistinctMeanTrainStep  the mean engine over the distinct-draw sampler: every hop drawn without
+                               replacement by one sampler launch of its own (gsage_sample_hops_distinct), everything
+                               behind it the mean engine's (opt-in: train.py --engine fused with the distinct sampler;
+                               not one of ENGINES)
 
 `fused_engine_for(model, feats)` picks the engine that covers a model, or explains why none does.
 """
@@ -29,6 +33,7 @@ from .pool import FusedPoolTrainStep
 from .attn import FusedAttnTrainStep
 from .unsup import FusedUnsupMeanTrainStep, FusedUnsupWeightedMeanTrainStep   # noqa: F401
 from .weighted import FusedWeightedMeanTrainStep             # noqa: F401
+from .distinct import FusedDistinctMeanTrainStep             # noqa: F401
 
 ENGINES = (FusedMeanTrainStep, FusedPoolTrainStep, FusedAttnTrainStep)
 

@@ -236,6 +236,64 @@ class SparseWeightedNeighborSampler(object):
         return self._static_calls
 
 
+class SparseDistinctNeighborSampler(object):
+    """CSR neighbour sampling WITHOUT replacement (no reference counterpart; include/gsage.h, "Distinct neighbours"): a
+    row of degree <= n_samples returns every stored edge floor(n / deg) or ceil(n / deg) times -- the plain mean over
+    the slots is the row's mean when deg divides n, and an unbiased estimate of it otherwise -- a longer row n_samples
+    distinct stored edges, uniformly random; a row of degree 0 the dummy node 0.  adj: a scipy matrix in the
+    reference's sparse convention, or a store.WeightedAdj whose weights are ignored (as the uniform sampler ignores
+    them).  Same call signature, `shard`, begin_capture / calls_in_capture, csr(device) and use_device_csr as
+    SparseUniformNeighborSampler, of which it is deliberately NOT a subclass: the engines accept a model by isinstance,
+    and the uniform K1 must not run a model that asked for distinct draws.  It always draws from Philox and says so
+    once when the class-wide default asks for "compat".  1 <= n_samples <= 256."""
+
+    _said_philox = False
+
+    def __init__(self, adj, rng=None, seed=0):
+        if isinstance(adj, WeightedAdj):
+            adj = adj.adj
+        if (rng or SparseUniformNeighborSampler.rng_default) != "philox" and not SparseDistinctNeighborSampler._said_philox:
+            SparseDistinctNeighborSampler._said_philox = True
+            print("gsage: the distinct sampler always draws from Philox (--rng compat has no meaning for it)",
+                  file=sys.stderr)
+        self.adj = adj
+        self._host = DeviceCSR.from_scipy(adj, torch.device("cpu"))
+        self._dev = {}
+        self.rng = "philox"
+        self.seed = int(seed)
+        self.calls = 0                # host-side call index (eager)
+        self.call_ctr = None          # device counter tensor (inside a captured graph)
+        self.shard = (0, 1)           # (rank, world): offsets the global sample index
+
+    degrees = SparseUniformNeighborSampler.degrees
+    csr = SparseUniformNeighborSampler.csr
+    use_device_csr = SparseUniformNeighborSampler.use_device_csr
+
+    def __call__(self, ids, n_samples=128):
+        assert n_samples > 0, 'SparseDistinctNeighborSampler: n_samples must be set explicitly'
+        ids = ids.contiguous().view(-1)
+        csr = self.csr(ids.device)
+        rank, _ = self.shard
+        ph = {"seed": self.seed, "g0": rank * int(ids.shape[0]) * n_samples}
+        if self.call_ctr is not None:
+            ph["call_ctr"] = self.call_ctr
+            ph["call_base"] = self._static_calls
+            self._static_calls += 1
+        else:
+            ph["call_base"] = self.calls
+            self.calls += 1
+        return ops.sample_csr_distinct(csr, ids, n_samples, ph)
+
+    _static_calls = 0
+
+    def begin_capture(self, counter):
+        self.call_ctr = counter
+        self._static_calls = 0
+
+    def calls_in_capture(self):
+        return self._static_calls
+
+
 sampler_lookup = {
     "uniform_neighbor_sampler": UniformNeighborSampler,
     "sparse_uniform_neighbor_sampler": SparseUniformNeighborSampler,
@@ -245,6 +303,7 @@ sampler_lookup = {
 # surface: tests/test_host_mode.py pins it); find_sampler() resolves a --sampler-class name over both
 sampler_extensions = {
     "sparse_weighted_neighbor_sampler": SparseWeightedNeighborSampler,
+    "sparse_distinct_neighbor_sampler": SparseDistinctNeighborSampler,
 }
 
 

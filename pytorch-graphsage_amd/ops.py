@@ -444,6 +444,117 @@ def sample_hops_weighted(csr, ids, B, fans, philox):
 
 
 # =============================================================================================
+# Distinct neighbours: sampling without replacement (csrc/gsage_distinct.hip)
+# =============================================================================================
+DISTINCT_TAG = 0x44000000                                                             # include/gsage.h
+DISTINCT_N_MAX = 256
+
+
+def _philox_words_host(seed, tag, call, g0, count):
+    """uint64 [count]: word g & 3 of Philox block g >> 2 for g = g0 .. g0 + count - 1 under the key
+    {lo(seed), hi(seed) ^ tag} (the uniform sampler's addressing, include/gsage.h)"""
+    g = np.arange(count, dtype=np.uint64) + np.uint64(g0 & 0xFFFFFFFFFFFFFFFF)
+    blk = g >> np.uint64(2)
+    mask, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    call &= 0xFFFFFFFFFFFFFFFF
+    c = [blk & mask, blk >> s32, np.full(count, call & 0xFFFFFFFF, dtype=np.uint64),
+         np.full(count, call >> 32, dtype=np.uint64)]
+    k0, k1 = seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ tag
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> s32) ^ c[1] ^ np.uint64(k0)) & mask, p1 & mask, ((p0 >> s32) ^ c[3] ^ np.uint64(k1)) & mask, p0 & mask]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return np.stack(c, axis=1)[np.arange(count), (g & np.uint64(3)).astype(np.int64)]
+
+
+def sample_csr_distinct(csr, ids, n, philox, out=None):
+    """SparseDistinctNeighborSampler.__call__ (include/gsage.h, "Distinct neighbours", gsage_sample_csr_distinct): n
+    neighbours of every id WITHOUT replacement -- a row of degree <= n returns every stored edge floor(n / deg) or
+    ceil(n / deg) times (the row rotated by a uniform r), a longer row n distinct stored edges (n steps of a
+    Fisher-Yates shuffle); a row of degree 0 yields the dummy 0.  csr: a store.DeviceCSR (edge weights, if any, are
+    not read); philox: dict(seed, call_base, g0, call_ctr) as for sample_csr.  Returns LongTensor [M*n] on the ids'
+    device.  CPU tensors: the same definition in numpy (host mode)."""
+    n = int(n)
+    assert 1 <= n <= DISTINCT_N_MAX, "SparseDistinctNeighborSampler: n_samples must be in 1..%d" % DISTINCT_N_MAX
+    ids = ids.contiguous().view(-1)
+    M = int(ids.shape[0])
+    seed, base, g0 = int(philox["seed"]), int(philox.get("call_base", 0)), int(philox.get("g0", 0))
+    ctr = philox.get("call_ctr")
+    if ids.is_cuda:
+        if out is None:
+            out = torch.empty(M * n, dtype=torch.int64, device=ids.device)
+        assert out.dtype == torch.int64 and out.numel() == M * n and out.is_contiguous()
+        nat.check(nat.lib().gsage_sample_csr_distinct(_ptr(csr.rowptr), _ptr(csr.col), csr.n_rows, _ptr(ids), M, n, seed,
+                                                      _ptr(ctr), base, g0, _ptr(out), _ptr(csr.err_flag), _stream()),
+                  "sample_csr_distinct")
+        return out
+    # ---- host mode
+    idn = ids.numpy()
+    if idn.size and (idn.min() < 0 or idn.max() >= csr.n_rows):
+        raise IndexError("sampler: node id out of range of the adjacency")
+    if M == 0 or csr.nnz == 0:
+        return torch.zeros(M * n, dtype=torch.int64)
+    call = base + (int(ctr.item()) if ctr is not None else 0)
+    w = _philox_words_host(seed, DISTINCT_TAG, call, g0, M * n).reshape(M, n)
+    rp, col = csr.rowptr.numpy(), csr.col.numpy()
+    beg, deg = rp[idn], (rp[idn + 1] - rp[idn]).astype(np.uint64)
+    s32, slot = np.uint64(32), np.arange(n, dtype=np.uint64)
+    off = np.zeros((M, n), dtype=np.uint64)
+    short = (deg > 0) & (deg <= n)
+    if short.any():                                    # every neighbour: the row rotated by r = (w_0 deg) >> 32
+        d = deg[short]
+        off[short] = (slot[None, :] + ((w[short, 0] * d) >> s32)[:, None]) % d[:, None]
+    rows = np.flatnonzero(deg > n)
+    if rows.size:                                      # n distinct edges: the shuffle's per-slot form, all rows at once
+        t = slot[None, :] + ((w[rows] * (deg[rows, None] - slot[None, :])) >> s32)
+        for j in range(n):
+            x = t[:, j].copy()
+            for i in range(j - 1, -1, -1):
+                x[t[:, i] == x] = i
+            off[rows, j] = x
+    vals = col[np.minimum(beg[:, None] + off.astype(np.int64), col.shape[0] - 1)].astype(np.int64)
+    return torch.from_numpy(np.where(deg[:, None] > 0, vals, 0).reshape(-1))
+
+
+def sample_hops_distinct(csr, ids, B, fans, philox):
+    """Every hop of a distinct-draw frontier (include/gsage.h, gsage_sample_hops_distinct: one launch): ids is the
+    concatenated buffer [hop 0 | hop 1 | ... | hop L] (int64, B (1 + n1 + n1 n2 + ...) entries) with hop 0 filled; hop k
+    is written as sample_csr_distinct(hop k - 1, fans[k - 1]) under call index call_base + k - 1 and
+    g0 = rank * |hop k|.  philox: dict(seed, call_base, call_ctr, optional rank).  Returns ids.
+    CPU tensors: the host definition of the per-hop draw, hop after hop (host mode)."""
+    fans = [int(n) for n in fans]
+    assert 1 <= len(fans) <= 5 and all(1 <= n <= DISTINCT_N_MAX for n in fans), \
+        "sample_hops_distinct: 1..5 hops of n_samples in 1..%d" % DISTINCT_N_MAX
+    B = int(B)
+    sizes = [B]
+    for n in fans:
+        sizes.append(sizes[-1] * n)
+    assert ids.dtype == torch.int64 and ids.dim() == 1 and ids.is_contiguous() and ids.numel() == sum(sizes)
+    seed, base, rank = int(philox["seed"]), int(philox.get("call_base", 0)), int(philox.get("rank", 0))
+    ctr = philox.get("call_ctr")
+    if ids.is_cuda:
+        d = nat.HopsDesc()
+        d.rowptr, d.col, d.n_rows = csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.n_rows
+        d.ids, d.B, d.n_hops = ids.data_ptr(), B, len(fans)
+        for k in range(5):
+            d.fan[k] = fans[k] if k < len(fans) else 1
+        d.max_deg, d.seed, d.call_base, d.rank = 1, seed, base, rank
+        d.call_ctr = ctr.data_ptr() if ctr is not None else None
+        d.err_flag = csr.err_flag.data_ptr()
+        nat.check(nat.lib().gsage_sample_hops_distinct(ctypes.addressof(d), _stream()), "sample_hops_distinct")
+        return ids
+    off = 0
+    for k, n in enumerate(fans):
+        ph = {"seed": seed, "call_base": base + k, "g0": rank * sizes[k + 1]}
+        if ctr is not None:
+            ph["call_ctr"] = ctr
+        ids[off + sizes[k]:off + sizes[k] + sizes[k + 1]] = sample_csr_distinct(csr, ids[off:off + sizes[k]], n, ph)
+        off += sizes[k]
+    return ids
+
+
+# =============================================================================================
 # Importance neighbourhoods: visit counts of short random walks and their top-T (csrc/gsage_importance.hip)
 # =============================================================================================
 IMPORTANCE_TAG = 0x49000000                                                           # include/gsage.h

@@ -95,6 +95,18 @@ that engine does not cover is an error with its sentence.  --full-neighbour-eval
 weight-normalised mean (mean and mean-pool models); --unsupervised is refused unless --weighted-walks is given (its
 walks would otherwise take uniform steps over a graph the encoder reads by weight).
 
+--sampler-class sparse_distinct_neighbor_sampler: neighbours drawn WITHOUT replacement (include/gsage.h, "Distinct
+neighbours"; sparse problems): a node with no more neighbours than the fan-out gets every one of them, balanced -- its
+sampled mean is its exact mean whenever its degree divides the fan-out -- and a node with more gets that many distinct
+ones.  Edge weights, if the problem has any, are ignored, as under the uniform sampler.  Always Philox; fan-outs of at
+most 256.  Under --engine auto / eager the module path runs it (said on stderr, with the name of the engine --engine
+fused would select); --engine fused (opt-in, mean aggregators, the identity prep over a bf16 / fp32 table, one process)
+runs training on engine.FusedDistinctMeanTrainStep -- the mean engine behind one sampler launch that draws every hop
+(gsage_sample_hops_distinct), queue mode included -- and the validation / test folds on the same class; what that
+engine does not cover is an error with its sentence.  --unsupervised runs on the module path (the sampler only supplies
+the frontier; --engine fused exits with the unsupervised engine's sentence); --importance-walks is refused (that run is
+a weighted one).
+
 --weighted-walks (default off: nothing changes; with --unsupervised and the weighted sampler, asked for by name or
 reached through --importance-walks): the positives' random walks draw every step in proportion to the edge weights
 (models.GSUnsupervised(weighted_walks=True), gsage_unsup_batch_weighted), on the training graph and -- in the
@@ -417,6 +429,9 @@ def importance_graphs(args, problem):
     if args.sampler_class == 'uniform_neighbor_sampler' or not gs.problem._is_sparse(problem.adj):
         raise SystemExit('gsage: --importance-walks: random walks need the stored edges of a sparse problem, not the dense '
                          'sampler\'s pre-sampled table (use --sampler-class sparse_uniform_neighbor_sampler)')
+    if args.sampler_class == 'sparse_distinct_neighbor_sampler':
+        raise SystemExit('gsage: --importance-walks: the run is a weighted one (the visit counts are the edge weights), '
+                         'and the distinct sampler (sparse_distinct_neighbor_sampler) ignores edge weights')
     if args.sampler_class == 'sparse_uniform_neighbor_sampler':
         print('gsage: --importance-walks: --sampler-class sparse_uniform_neighbor_sampler becomes '
               'sparse_weighted_neighbor_sampler (the visit counts are the edge weights)', file=sys.stderr)
@@ -519,6 +534,9 @@ def main(argv=None, problem=None):
     elif args.weighted_walks:
         raise SystemExit('gsage: --weighted-walks: needs the weighted sampler (--sampler-class '
                          'sparse_weighted_neighbor_sampler, or --importance-walks), not %s' % args.sampler_class)
+    if args.sampler_class == 'sparse_distinct_neighbor_sampler' and not gs.problem._is_sparse(problem.adj):
+        raise SystemExit('gsage: --sampler-class sparse_distinct_neighbor_sampler: distinct draws need the stored edges '
+                         'of a sparse problem, not the dense sampler\'s pre-sampled table')
     if args.feature_dtype == 'fp8':
         if problem.feats is None:
             raise SystemExit('gsage: --feature-dtype fp8: this problem has no feature table')
@@ -672,11 +690,15 @@ def choose_engine(args, problem, model, ddp):
         if nodes.shape[0] // (nodes.shape[0] // args.batch_size + 1) < 2:
             return give_up('chunks of fewer than two training nodes')
         return cls
-    if isinstance(model.train_sampler, gs.nn_modules.SparseWeightedNeighborSampler):
-        cls = gs.engine.FusedWeightedMeanTrainStep     # opt-in: --engine fused, or the module path
+    own = [(what, scls, cls) for what, scls, cls in
+           (('weighted', gs.nn_modules.SparseWeightedNeighborSampler, gs.engine.FusedWeightedMeanTrainStep),
+            ('distinct', gs.nn_modules.SparseDistinctNeighborSampler, gs.engine.FusedDistinctMeanTrainStep))
+           if isinstance(model.train_sampler, scls)]
+    if own:
+        what, scls, cls = own[0]                       # opt-in: --engine fused, or the module path
         if args.engine != 'fused':
-            return give_up('no fused engine covers the weighted sampler (SparseWeightedNeighborSampler) '
-                           '(--engine fused selects %s)' % cls.__name__)
+            return give_up('no fused engine covers the %s sampler (%s) (--engine fused selects %s)'
+                           % (what, scls.__name__, cls.__name__))
         why = cls.why_not(model, problem.feats, ddp)
         if why is not None:
             return give_up('%s: %s' % (cls.__name__, why))
@@ -772,7 +794,8 @@ def train_fused(args, problem, model, ddp, start_time, cls):
                                                                closure=args.eval_closure)
     elif os.environ.get("GSAGE_FUSED_EVAL", "1") == "1":
         fold_eval = FusedEvaluator(cls, model, problem, wide_head=args.wide_head,
-                                   strict=cls is gs.engine.FusedWeightedMeanTrainStep).prepare('val')
+                                   strict=cls in (gs.engine.FusedWeightedMeanTrainStep,
+                                                  gs.engine.FusedDistinctMeanTrainStep)).prepare('val')
     else:
         fold_eval = lambda mode='val': evaluate(model, problem, mode=mode)                     # noqa: E731
     # The per-batch line (train.py:150-158) without a host sync per step: batch b is scored on the device right behind
