@@ -1309,6 +1309,93 @@ int gsage_importance_compact(const int32_t *out_col, const float *out_w, const i
                              void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Biased walks (csrc/gsage_walk_dev.h, csrc/gsage_unsup.hip, csrc/gsage_importance.hip): node2vec's second-order
+ * steps -- a return parameter p and an in-out parameter q -- for the positives of "Unsupervised GraphSAGE" and the
+ * walks of "Importance neighbourhoods", and a restart probability for the latter.  Additive; the ABI version is
+ * unchanged.  No reference counterpart.
+ *
+ * Parameters.  p, q: doubles, finite, in [1/8, 8];  restart: a double in [0, 1).
+ * Thresholds, computed once on the host in double arithmetic (classes c = return, near, far):
+ *     a       = (1.0 / p, 1.0, 1.0 / q);   a_max = max(a)
+ *     theta_c = a_c == a_max ? 2^32 : (uint64)floor((a_c / a_max) * 4294967296.0)
+ *     theta_restart = (uint64)floor(restart * 4294967296.0)
+ *   e.g. (p, q) = (4, 0.25): theta = (2^28, 2^30, 2^32).  The kernels receive these integers.
+ *
+ * A FIRST-ORDER step from node v is the step of the entry being biased, given the draw's random words:
+ *     builder, uniform     word (32 bits):  off = deg <= 2^32 - 1 ? (word * deg) >> 32 : word;   x = col[beg + off]
+ *     builder, weighted    r64:  x = col[first e of the row with edge_cdf[e] > (r64 * T_v) >> 64]
+ *     importance, uniform  r64:  x = col[beg + ((r64 * deg) >> 64)]
+ *     importance, weighted r64:  x = col[first e of the row with cdf[e] > (r64 * T_v) >> 64]
+ *   A dead end (deg <= 0, or T_v == 0 under a table) ends the walk before any word is looked at, as in those entries.
+ *
+ * A SECOND-ORDER step from v with the previous node t known: rejection sampling over the first-order step.
+ *     for round k = 0 .. 31:
+ *         x = the first-order step from v under round k's proposal words
+ *         x outside [0, n_rows): the error of the legacy entry (below), whether or not the round would have accepted
+ *         class(x) = return  if x == t
+ *                    near    else if x occurs among the STORED columns of row t -- col[rowptr[t] .. rowptr[t+1]), at
+ *                            any position, under any weight (an edge of quantum 0 counts), however often it repeats
+ *                    far     otherwise
+ *         accept iff (round k's 32-bit acceptance word) < theta_class(x);   an accepted x is the step
+ *     no round accepts: the step is the x of round 31.
+ *   The bias of that last rule is the probability that 32 rounds reject, (1 - accept)^32 with accept the mean of
+ *   theta_class / 2^32 over the proposal distribution: at most 1.3e-4 on a clique at p = 4, q = 0.25 (accept = 1/4 + O(1/n),
+ *   0.75^32 = 1.0e-4 .. 1.3e-4), far less elsewhere.  A node whose only neighbour is t takes it either way.  A dead-end
+ *   row proposes nothing: the walk ends.  Steps WITHOUT a previous node -- the first step of a walk, the first step
+ *   after a restart -- are first-order steps under round 0's proposal words, with no acceptance test.
+ *
+ * Words.  Round 0's PROPOSAL words are the words the legacy entry uses for that step; everything else comes from
+ * Philox blocks no other role addresses.
+ *   builder, step j (0-based) of seed g, with P(c, tag) of "Unsupervised GraphSAGE":
+ *     round 0 proposal     uniform:  P(g, 0x53000000 | (j >> 2))[j & 3];   weighted:  r64 of P(g, 0x5A000000 | (j >> 1)), half j & 1
+ *     Bk = P(g, 0x42000000 | (j << 8) | k)             (j <= 15, k <= 31: tags 0x42000000 .. 0x42000F1F, used by nothing else)
+ *     round k >= 1 proposal   uniform:  Bk[0];   weighted:  r64 = (uint64)Bk[0] << 32 | Bk[1]
+ *     round k acceptance word Bk[2]    (k = 0 included; Bk[3], and B0[0..1], are unused)
+ *   importance, step s of walk r of source v, key {lo(seed), hi(seed) ^ 0x49000000}:
+ *     round 0 proposal     r64 of philox4x32_10({lo(v), r, s >> 1, 0}, key), half s & 1            (the legacy block)
+ *     Nk = philox4x32_10({lo(v), r, s, 1 + k}, key)    (the legacy blocks have 0 in the fourth counter word)
+ *     round k >= 1 proposal   r64 = (uint64)Nk[0] << 32 | Nk[1]
+ *     round k acceptance word Nk[2];   the restart word of step s is N0[3]
+ *
+ * gsage_unsup_batch_biased -- gsage_unsup_batch (edge_cdf == NULL: uniform proposals) or gsage_unsup_batch_weighted
+ * (edge_cdf != NULL) with second-order steps: walk lengths t_i, dead ends, pair_w, negatives, call / g0 / err_flag and
+ * the outputs are those entries'; step 0 of every walk is first-order, steps j >= 1 are second-order with t the node
+ * the walk stood on before v.  A seed outside [0, n_rows) is handled as there; a PROPOSAL outside [0, n_rows) raises
+ * *err_flag and ends the walk at node 0.  One launch: a wave per walk, four to a workgroup, the negatives' workgroups
+ * behind them.  The acceptance word is looked at first: below min(theta_near, theta_far) it accepts any x != t, at or
+ * above their maximum it rejects it, and only between the two are the stored columns of row t read (64 per load, by
+ * the wave); with q = 1 no row is ever read.
+ *
+ * gsage_importance_walks_biased -- gsage_importance_walks with second-order steps and restarts; counting, the total
+ * order, the outputs, the limits and the size classes are that entry's.  Walk r of source v: u = v, no previous node;
+ *     for s = 0 .. L - 1 (the walk not ended):
+ *         s >= 1 and N0[3] < theta_restart:  u = v, the previous node is forgotten, nothing is counted, the step is
+ *                                            consumed -- the walk goes on with step s + 1
+ *         else  row u is a dead end: the walk ends
+ *               x = a first-order step (no previous node) or a second-order step (t = the previous node) from u
+ *               x outside [0, n_rows): *err_flag is raised, the walk ends, nothing is counted
+ *               the previous node becomes u;  u = x;  u != v: one visit of u
+ *   One launch, a walk per lane; the lanes step together, and the membership queries of a round are answered by the
+ *   whole wave one after another (64 stored columns of row t per load).
+ *
+ * CONSEQUENCE.  With p = q = 1 every class threshold is 2^32, round 0 always accepts and its proposal is the legacy
+ * word: the results are gsage_unsup_batch's / gsage_unsup_batch_weighted's / gsage_importance_walks', bit for bit.
+ * With restart = 0, theta_restart = 0 and no walk restarts.
+ *
+ * p or q outside [1/8, 8] (NaN included), restart outside [0, 1), null pointers and the legacy entries' size checks
+ * give GSAGE_EINVAL without a launch and without a GPU; the message names the argument.  Both entries can be recorded
+ * in a command list.
+ * ---------------------------------------------------------------------------------------- */
+int gsage_unsup_batch_biased(const int64_t *rowptr, const int32_t *col, const uint64_t *edge_cdf, int64_t n_rows,
+                             const int64_t *seeds, int64_t B, int32_t walk_len, int64_t Q, const double *cdf,
+                             double cdf_total, uint64_t seed, const uint64_t *call_ctr, uint64_t call_base, uint64_t g0,
+                             double p, double q, int64_t *ids, float *pair_w, int32_t *err_flag, void *stream);
+int gsage_importance_walks_biased(const int64_t *rowptr, const int32_t *col, const uint64_t *cdf, int64_t n_rows,
+                                  const int64_t *ids, int64_t M, int32_t n_walks, int32_t walk_len, int32_t top,
+                                  uint64_t seed, double p, double q, double restart, int32_t *out_col, float *out_w,
+                                  int32_t *out_deg, int32_t *err_flag, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * k-hop closure blocks (csrc/gsage_block.hip, csrc/gsage_fullgraph.hip): full-neighbourhood inference for a query
  * set (infer.closure / infer.query).  Additive; the ABI version is unchanged.  No reference counterpart.
  *

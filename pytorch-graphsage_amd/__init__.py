@@ -18,10 +18,12 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
                               the val / test folds (ops.probe_pass, csrc/gsage_probe.hip)
     store.WeightedAdj         edge weights: sparse_weighted_neighbor_sampler, weight-normalised full-neighbourhood mean
     store.importance_adj      any adjacency -> its importance-weighted one: visit counts of short random walks, the
-                              top-T most-visited nodes per row (DeviceCSR.importance, csrc/gsage_importance.hip)
+                              top-T most-visited nodes per row (DeviceCSR.importance, csrc/gsage_importance.hip);
+                              p=, q=, restart=: node2vec-biased walks with restarts (gsage_importance_walks_biased)
     models.GSUnsupervised     label-free training: random-walk positives, degree^0.75 negatives, skip-gram head;
                               weighted_walks=True: over a weighted adjacency the walks draw every step by edge weight
-                              (ops.unsup_batch(weighted=True), gsage_unsup_batch_weighted)
+                              (ops.unsup_batch(weighted=True), gsage_unsup_batch_weighted); walk_p=, walk_q=: node2vec's
+                              return / in-out parameters (ops.unsup_batch(p=, q=), gsage_unsup_batch_biased)
     nn_modules.SparseDistinctNeighborSampler   neighbours WITHOUT replacement (sparse_distinct_neighbor_sampler in
                               sampler_extensions; ops.sample_csr_distinct, csrc/gsage_distinct.hip): every neighbour of a
                               short row, n distinct ones of a long row

@@ -186,6 +186,8 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _vp]),
     "gsage_unsup_batch_weighted": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i64, _vp, ctypes.c_double, _u64, _vp,
                                           _u64, _u64, _vp, _vp, _vp, _vp]),
+    "gsage_unsup_batch_biased": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i64, _vp, ctypes.c_double, _u64, _vp,
+                                        _u64, _u64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "gsage_head_skipgram": (_int, [_vp, _i64, _i32, _i32, _i32, _vp, _f32, _vp, _int, _i64, _vp, _vp, _vp, _vp]),
     "gsage_head_skipgram_scratch": (_i64, [_i32, _i32, _i32]),
     "gsage_head_skipgram_live": (_int, [_vp, _i64, _i32, _i32, _i32, _vp, _f32, _vp, _vp, _int, _i64, _vp, _vp, _vp,
@@ -198,6 +200,8 @@ SIGNATURES = {
     "gsage_segment_reduce_weighted": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                              _i32, _vp, _i64, _vp, _int, _i64, _int, _vp, _vp]),
     "gsage_importance_walks": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gsage_importance_walks_biased": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _u64, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     "gsage_importance_compact": (_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "gsage_closure_span": (_i64, []),
     "gsage_closure_seed_count": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),

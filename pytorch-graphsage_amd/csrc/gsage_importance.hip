@@ -19,6 +19,7 @@
 //   workgroup (template parameter), the sorts' loops run over n itself (launch argument): 100 landings sort 128 slots.
 //   gsage_importance_compact  the padded rows packed into a CSR: one lane per padded entry.
 #include "gsage_common.h"
+#include "gsage_walk_dev.h"
 #include "gsage_weighted_dev.h"
 
 namespace gsage {
@@ -49,6 +50,39 @@ __device__ __forceinline__ void wave_bitonic_sort(T *s, int n, int lane)
             lds_barrier();
         }
     }
+}
+
+// steps 2-4 for source i: the landings in s_id[0 .. n) -> the source's padded row (every lane of the wave calls it)
+__device__ __forceinline__ void importance_rank(uint32_t *s_id, uint64_t *s_key, int n, int32_t top, int lane, int64_t i,
+                                                int32_t *__restrict__ out_col, float *__restrict__ out_w,
+                                                int32_t *__restrict__ out_deg)
+{
+    lds_barrier();
+    wave_bitonic_sort<uint32_t, false>(s_id, n, lane);
+    for (int t = lane; t < n; t += 64) {
+        const uint32_t id = s_id[t];
+        uint64_t key = 0;
+        if (id != EMPTY_SLOT && (t == 0 || s_id[t - 1] != id)) {
+            int lo = t + 1, hi = n;                   // first slot in (t, n] that holds another id
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s_id[mid] > id) hi = mid;
+                else lo = mid + 1;
+            }
+            key = ((uint64_t)(uint32_t)(lo - t) << 32) | (uint64_t)(EMPTY_SLOT - id);
+        }
+        s_key[t] = key;
+    }
+    lds_barrier();
+    wave_bitonic_sort<uint64_t, true>(s_key, n, lane);
+    const uint64_t key = lane < top ? s_key[lane] : 0ull;         // top <= 64 <= n
+    const bool live = key != 0;
+    if (lane < top) {
+        out_col[i * top + lane] = live ? (int32_t)(EMPTY_SLOT - (uint32_t)key) : 0;
+        out_w[i * top + lane] = live ? (float)(uint32_t)(key >> 32) : 0.f;
+    }
+    const int k = __popcll(__ballot(live));
+    if (lane == 0) out_deg[i] = k;
 }
 
 template <int P>
@@ -95,32 +129,102 @@ k_importance_walks(const int64_t *__restrict__ rowptr, const int32_t *__restrict
                 }
             }
         }
+        importance_rank(s_id, s_key, n, top, lane, i, out_col, out_w, out_deg);
+        lds_barrier();                                    // the keys are read: the next source may overwrite them
+    }
+}
+
+// The walks of "Biased walks" (include/gsage.h): second-order steps by rejection, restarts.  A walk per lane, as above,
+// but the lanes move in lock step -- step s, round k -- so that the wave can answer the membership queries together:
+// every lane whose acceptance word falls between the near and the far threshold hands its (previous node, proposal)
+// to the whole wave in turn, and the 64 lanes scan that row 64 stored columns per trip (wave_row_contains).  Every
+// loop is wave-uniform and bounded: the walks' chunks, the steps, 32 rounds, the 64 bits of a ballot, a row's length.
+template <int P>
+__global__ void __launch_bounds__(64)
+k_importance_walks_biased(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                          const uint64_t *__restrict__ cdf, int64_t n_rows, const int64_t *__restrict__ ids, int64_t M,
+                          int32_t n_walks, int32_t walk_len, int32_t top, int32_t n, uint32_t seed_lo, uint32_t seed_hi,
+                          const WalkBias b, int32_t *__restrict__ out_col, float *__restrict__ out_w,
+                          int32_t *__restrict__ out_deg, int32_t *err_flag)
+{
+    __shared__ uint32_t s_id[P];
+    __shared__ uint64_t s_key[P];
+    const int lane = threadIdx.x;
+    const uint32_t k1 = seed_hi ^ IMPORTANCE_TAG;
+    for (int64_t i = blockIdx.x; i < M; i += gridDim.x) {
+        const int64_t v = ids[i];
+        for (int t = lane; t < n; t += 64) s_id[t] = EMPTY_SLOT;
         lds_barrier();
-        wave_bitonic_sort<uint32_t, false>(s_id, n, lane);
-        for (int t = lane; t < n; t += 64) {
-            const uint32_t id = s_id[t];
-            uint64_t key = 0;
-            if (id != EMPTY_SLOT && (t == 0 || s_id[t - 1] != id)) {
-                int lo = t + 1, hi = n;                   // first slot in (t, n] that holds another id
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (s_id[mid] > id) hi = mid;
-                    else lo = mid + 1;
+        if ((uint64_t)v >= (uint64_t)n_rows) {            // (uniform over the wave) an empty row
+            if (lane == 0 && err_flag) *err_flag = 1;
+        } else {
+            for (int r0 = 0; r0 < n_walks; r0 += 64) {
+                const int r = r0 + lane;
+                bool alive = r < n_walks;
+                int64_t u = v, prev = -1;                 // prev < 0: no previous node, the step is first-order
+                philox4 w = {{0u, 0u, 0u, 0u}};
+                for (int s = 0; s < walk_len; ++s) {
+                    if (!(s & 1))
+                        w = philox4x32_10((uint32_t)v, (uint32_t)r, (uint32_t)(s >> 1), 0u, seed_lo, k1);
+                    philox4 nb0 = {{0u, 0u, 0u, 0u}};     // N(s, 0): round 0's acceptance word, the restart word
+                    if (!b.neutral || (b.restart != 0 && s >= 1))
+                        nb0 = philox4x32_10((uint32_t)v, (uint32_t)r, (uint32_t)s, 1u, seed_lo, k1);
+                    bool moving = alive;
+                    if (s >= 1 && moving && (uint64_t)nb0.v[3] < b.restart) {     // back on the source, nothing counted
+                        u = v;
+                        prev = -1;
+                        moving = false;
+                    }
+                    int64_t beg = 0, end = 0;
+                    uint64_t Tu = 0;
+                    if (moving) {
+                        beg = rowptr[u];
+                        end = rowptr[u + 1];
+                        if (end > beg && cdf) Tu = cdf[end - 1];
+                        if (end <= beg || (cdf && Tu == 0)) alive = moving = false;       // the walk ends
+                    }
+                    bool pending = moving;
+                    int64_t x = -1;
+                    for (int k = 0; k < WALK_ROUNDS; ++k) {
+                        if (__ballot(pending) == 0ull) break;
+                        philox4 nb = nb0;
+                        bool scan = false;
+                        if (pending) {
+                            if (k > 0) nb = philox4x32_10((uint32_t)v, (uint32_t)r, (uint32_t)s, (uint32_t)(1 + k), seed_lo, k1);
+                            const uint64_t r64 = k == 0 ? philox_r64(w, (s & 1) != 0) : ((uint64_t)nb.v[0] << 32) | nb.v[1];
+                            const int64_t e = cdf ? cdf_first_above(cdf, beg, end, __umul64hi(r64, Tu))
+                                                  : beg + (int64_t)__umul64hi(r64, (uint64_t)(end - beg));
+                            x = (int64_t)col[e];
+                            if ((uint64_t)x >= (uint64_t)n_rows) {    // a stored id outside the graph: the walk ends
+                                if (err_flag) *err_flag = 1;
+                                alive = moving = pending = false;
+                            } else if (prev < 0 || b.neutral) {
+                                pending = false;                      // a first-order step
+                            } else {
+                                const int a = walk_accept_early(b, nb.v[2], x == prev);
+                                if (a > 0) pending = false;
+                                scan = a < 0;
+                            }
+                        }
+                        uint64_t todo = __ballot(scan);               // the lanes only the row of prev can answer
+                        while (todo != 0ull) {
+                            const int src = __ffsll((unsigned long long)todo) - 1;
+                            todo &= todo - 1;
+                            const int64_t tq = (int64_t)__shfl((int)prev, src, 64);       // (ids are int32)
+                            const int32_t xq = __shfl((int)x, src, 64);
+                            const bool near_ = wave_row_contains(col, rowptr[tq], rowptr[tq + 1], xq, lane);
+                            if (lane == src && walk_accept_scanned(b, nb.v[2], near_)) pending = false;
+                        }
+                    }
+                    if (moving) {                         // (still pending after 32 rounds: round 31's proposal)
+                        prev = u;
+                        u = x;
+                        if (u != v) s_id[r * walk_len + s] = (uint32_t)u;
+                    }
                 }
-                key = ((uint64_t)(uint32_t)(lo - t) << 32) | (uint64_t)(EMPTY_SLOT - id);
             }
-            s_key[t] = key;
         }
-        lds_barrier();
-        wave_bitonic_sort<uint64_t, true>(s_key, n, lane);
-        const uint64_t key = lane < top ? s_key[lane] : 0ull;         // top <= 64 <= n
-        const bool live = key != 0;
-        if (lane < top) {
-            out_col[i * top + lane] = live ? (int32_t)(EMPTY_SLOT - (uint32_t)key) : 0;
-            out_w[i * top + lane] = live ? (float)(uint32_t)(key >> 32) : 0.f;
-        }
-        const int k = __popcll(__ballot(live));
-        if (lane == 0) out_deg[i] = k;
+        importance_rank(s_id, s_key, n, top, lane, i, out_col, out_w, out_deg);
         lds_barrier();                                    // the keys are read: the next source may overwrite them
     }
 }
@@ -183,6 +287,42 @@ int gsage_importance_walks(const int64_t *rowptr, const int32_t *col, const uint
         launch(k_importance_walks<4096>, dim3(importance_grid(M, 2048)), dim3(64), 0, st, rowptr, col, cdf, n_rows, ids,
                M, n_walks, walk_len, top, n, lo, hi, out_col, out_w, out_deg, err_flag);
     return check_launch("importance_walks");
+}
+
+int gsage_importance_walks_biased(const int64_t *rowptr, const int32_t *col, const uint64_t *cdf, int64_t n_rows,
+                                  const int64_t *ids, int64_t M, int32_t n_walks, int32_t walk_len, int32_t top,
+                                  uint64_t seed, double p, double q, double restart, int32_t *out_col, float *out_w,
+                                  int32_t *out_deg, int32_t *err_flag, void *stream)
+{
+    GSAGE_REQUIRE(p >= 0.125 && p <= 8.0, "importance_walks_biased: p must be in [1/8, 8] (got %g)", p);
+    GSAGE_REQUIRE(q >= 0.125 && q <= 8.0, "importance_walks_biased: q must be in [1/8, 8] (got %g)", q);
+    GSAGE_REQUIRE(restart >= 0.0 && restart < 1.0, "importance_walks_biased: restart must be in [0, 1) (got %g)", restart);
+    GSAGE_REQUIRE(n_walks >= 1, "importance_walks_biased: n_walks must be >= 1");
+    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= 16, "importance_walks_biased: walk_len must be in 1..16");
+    GSAGE_REQUIRE(top >= 1 && top <= 64, "importance_walks_biased: top must be in 1..64");
+    GSAGE_REQUIRE((int64_t)n_walks * walk_len <= IMPORTANCE_MAX_LANDINGS,
+                  "importance_walks_biased: n_walks * walk_len = %lld, more than %d landings per source",
+                  (long long)n_walks * walk_len, IMPORTANCE_MAX_LANDINGS);
+    GSAGE_REQUIRE(M >= 0 && n_rows >= 0 && n_rows < (1LL << 31),
+                  "importance_walks_biased: bad sizes (node ids are int32)");
+    if (M == 0) return GSAGE_OK;
+    GSAGE_REQUIRE(rowptr && col && ids && out_col && out_w && out_deg, "importance_walks_biased: null pointer");
+    WalkBias b;
+    (void)walk_bias_make(p, q, restart, b);               // (the limits were checked above)
+    int n = 64;
+    while (n < n_walks * walk_len) n <<= 1;
+    const hipStream_t st = (hipStream_t)stream;
+    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+    if (n <= 256)
+        launch(k_importance_walks_biased<256>, dim3(importance_grid(M, 16384)), dim3(64), 0, st, rowptr, col, cdf, n_rows,
+               ids, M, n_walks, walk_len, top, n, lo, hi, b, out_col, out_w, out_deg, err_flag);
+    else if (n <= 1024)
+        launch(k_importance_walks_biased<1024>, dim3(importance_grid(M, 8192)), dim3(64), 0, st, rowptr, col, cdf, n_rows,
+               ids, M, n_walks, walk_len, top, n, lo, hi, b, out_col, out_w, out_deg, err_flag);
+    else
+        launch(k_importance_walks_biased<4096>, dim3(importance_grid(M, 2048)), dim3(64), 0, st, rowptr, col, cdf, n_rows,
+               ids, M, n_walks, walk_len, top, n, lo, hi, b, out_col, out_w, out_deg, err_flag);
+    return check_launch("importance_walks_biased");
 }
 
 int gsage_importance_compact(const int32_t *out_col, const float *out_w, const int32_t *out_deg,

@@ -13,6 +13,7 @@
 // workgroup keeps its 16 normalised seed rows in LDS, streams the negatives' rows from L2 (64 x 1024 floats do not fit
 // beside them), and leaves one partial of d z_neg per workgroup for the second launch to sum in a fixed order.
 #include "gsage_common.h"
+#include "gsage_walk_dev.h"
 #include "gsage_weighted_dev.h"
 
 namespace gsage {
@@ -21,6 +22,7 @@ constexpr uint32_t UNSUP_TAG_LEN = 0x4C000000u;     // walk length
 constexpr uint32_t UNSUP_TAG_STEP = 0x53000000u;    // | (step >> 2): walk steps, four to a Philox block
 constexpr uint32_t UNSUP_TAG_NEG = 0x4E000000u;     // negatives
 constexpr uint32_t UNSUP_TAG_WSTEP = 0x5A000000u;   // | (step >> 1): weighted walk steps, two to a Philox block
+constexpr uint32_t UNSUP_TAG_BIAS = 0x42000000u;    // | (step << 8) | round: a biased step's rounds, a block each
 constexpr int UNSUP_WALK_MAX = 16;
 
 struct UnsupParams {
@@ -198,6 +200,106 @@ k_unsup_batch_weighted(const UnsupParams p)
             v = 0;
             break;
         }
+    }
+    if (lane == 0) {
+        if (bad && p.err_flag) *p.err_flag = 1;
+        p.ids[i] = s;
+        p.ids[p.B + i] = v;
+        p.pair_w[i] = v == s ? 0.f : 1.f;
+    }
+}
+
+// ---- biased walks: second-order steps by rejection, a wave per walk -------------------------------------------------------
+struct UnsupBiasedParams {
+    UnsupParams u;
+    WalkBias b;
+};
+
+// include/gsage.h, "Biased walks".  blocks [0, walk_blocks): a wave per seed (four to a workgroup), every value that
+// steers a branch made wave-uniform;  the rest: a lane per negative.  edge_cdf == NULL: uniform proposals.  Round 0
+// proposes with the word the first-order builder would use; the acceptance word is looked at before the row of the
+// previous node is, and most rounds never need that row.  Lane 0 writes the walk's three words.
+__global__ void __launch_bounds__(256)
+k_unsup_batch_biased(const UnsupBiasedParams bp)
+{
+    const UnsupParams &p = bp.u;
+    const WalkBias &b = bp.b;
+    const uint64_t call = p.call_base + (p.call_ctr ? *p.call_ctr : 0ull);
+    if ((int)blockIdx.x >= p.walk_blocks) {
+        unsup_negative(p, call);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (i >= p.B) return;
+    const int64_t s = wave_uniform(p.seeds[i]);
+    const uint64_t g = p.g0 + (uint64_t)i;
+    if ((uint64_t)s >= (uint64_t)p.n_rows) {
+        if (lane == 0) {
+            if (p.err_flag) *p.err_flag = 1;
+            p.ids[i] = 0;
+            p.ids[p.B + i] = 0;
+            p.pair_w[i] = 0.f;
+        }
+        return;
+    }
+    const uint32_t wl = unsup_philox(p, g, call, UNSUP_TAG_LEN).v[0];
+    const int t = 1 + (int)(((uint64_t)wl * (uint64_t)(uint32_t)p.walk_len) >> 32);
+    const bool weighted = p.edge_cdf != nullptr;
+    int64_t v = s, prev = -1;
+    philox4 r = {};
+    bool bad = false;
+    for (int j = 0; j < t; ++j) {
+        const int64_t beg = wave_uniform(p.rowptr[v]), end = wave_uniform(p.rowptr[v + 1]);
+        if (end <= beg) break;
+        const int64_t deg = end - beg;
+        if (weighted) {
+            if ((j & 1) == 0) r = unsup_philox(p, g, call, UNSUP_TAG_WSTEP | (uint32_t)(j >> 1));
+        } else {
+            if ((j & 3) == 0) r = unsup_philox(p, g, call, UNSUP_TAG_STEP | (uint32_t)(j >> 2));
+        }
+        const bool second = j > 0 && !b.neutral;               // a previous node, and thresholds that can reject
+        int64_t x = -1;
+        bool dead = false;
+        for (int k = 0; k < WALK_ROUNDS; ++k) {
+            philox4 nb = {};
+            if (second) nb = unsup_philox(p, g, call, UNSUP_TAG_BIAS | ((uint32_t)j << 8) | (uint32_t)k);
+            int64_t e;
+            if (weighted) {
+                const uint64_t r64 = k == 0 ? philox_r64(r, (j & 1) != 0) : ((uint64_t)nb.v[0] << 32) | nb.v[1];
+                e = wave_uniform(wave_cdf_step(p.edge_cdf, beg, end, r64, lane));
+                if (e < 0) {                                   // T_v == 0: the walk ends at v
+                    dead = true;
+                    break;
+                }
+            } else {
+                const int w4 = j & 3;                          // selects, not r.v[j & 3]: no scratch
+                const uint32_t w0 = w4 == 0 ? r.v[0] : w4 == 1 ? r.v[1] : w4 == 2 ? r.v[2] : r.v[3];
+                const uint32_t word = k == 0 ? w0 : nb.v[0];
+                const uint64_t off = (deg <= 0xffffffffLL) ? ((uint64_t)word * (uint64_t)deg) >> 32 : (uint64_t)word;
+                e = beg + (int64_t)off;
+            }
+            x = wave_uniform((int64_t)p.col[e]);
+            if ((uint64_t)x >= (uint64_t)p.n_rows) {
+                bad = true;
+                break;
+            }
+            if (!second) break;
+            const uint32_t aw = __builtin_amdgcn_readfirstlane(nb.v[2]);
+            int a = walk_accept_early(b, aw, x == prev);
+            if (a < 0) {
+                const int64_t tb = wave_uniform(p.rowptr[prev]), te = wave_uniform(p.rowptr[prev + 1]);
+                a = walk_accept_scanned(b, aw, wave_row_contains(p.col, tb, te, (int32_t)x, lane)) ? 1 : 0;
+            }
+            if (a) break;                                      // (no round accepts: x is round 31's proposal)
+        }
+        if (dead) break;
+        if (bad) {
+            v = 0;
+            break;
+        }
+        prev = v;
+        v = x;
     }
     if (lane == 0) {
         if (bad && p.err_flag) *p.err_flag = 1;
@@ -554,6 +656,31 @@ int gsage_unsup_batch_weighted(const int64_t *rowptr, const int32_t *col, const 
     launch(k_unsup_batch_weighted, dim3((unsigned)(p.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream,
            p);
     return check_launch("unsup_batch_weighted");
+}
+
+int gsage_unsup_batch_biased(const int64_t *rowptr, const int32_t *col, const uint64_t *edge_cdf, int64_t n_rows,
+                             const int64_t *seeds, int64_t B, int32_t walk_len, int64_t Q, const double *cdf,
+                             double cdf_total, uint64_t seed, const uint64_t *call_ctr, uint64_t call_base, uint64_t g0,
+                             double p, double q, int64_t *ids, float *pair_w, int32_t *err_flag, void *stream)
+{
+    GSAGE_REQUIRE(p >= 0.125 && p <= 8.0, "unsup_batch_biased: p must be in [1/8, 8] (got %g)", p);
+    GSAGE_REQUIRE(q >= 0.125 && q <= 8.0, "unsup_batch_biased: q must be in [1/8, 8] (got %g)", q);
+    GSAGE_REQUIRE(rowptr && col && seeds && cdf && ids && pair_w, "unsup_batch_biased: null pointer");
+    GSAGE_REQUIRE(n_rows > 0 && B > 0 && B < (1LL << 31) && Q > 0 && Q < (1LL << 31), "unsup_batch_biased: bad sizes");
+    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= UNSUP_WALK_MAX, "unsup_batch_biased: needs 1 <= walk_len <= %d",
+                  UNSUP_WALK_MAX);
+    GSAGE_REQUIRE(cdf_total > 0.0 && cdf_total <= 1.7976931348623157e308,
+                  "unsup_batch_biased: the negatives' weights sum to %g (every row has weight 0?)", cdf_total);
+    UnsupBiasedParams bp;
+    (void)walk_bias_make(p, q, 0.0, bp.b);                                        // (the limits were checked above)
+    UnsupParams &u = bp.u;
+    u.rowptr = rowptr; u.col = col; u.seeds = seeds; u.cdf = cdf; u.edge_cdf = edge_cdf; u.call_ctr = call_ctr;
+    u.ids = ids; u.pair_w = pair_w; u.err_flag = err_flag; u.n_rows = n_rows; u.B = B; u.Q = Q; u.call_base = call_base;
+    u.g0 = g0; u.cdf_total = cdf_total; u.seed_lo = (uint32_t)seed; u.seed_hi = (uint32_t)(seed >> 32);
+    u.walk_len = walk_len; u.walk_blocks = (int32_t)ceil_div(B, 4);              // a wave per walk, four to a workgroup
+    launch(k_unsup_batch_biased, dim3((unsigned)(u.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream,
+           bp);
+    return check_launch("unsup_batch_biased");
 }
 
 int64_t gsage_head_skipgram_scratch(int32_t B, int32_t Q, int32_t D)

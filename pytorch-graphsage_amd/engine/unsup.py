@@ -8,6 +8,9 @@ The encoder sees one batch of R = 2B + Q rows [seeds | positives | negatives]: t
 
 FusedUnsupWeightedMeanTrainStep: the same step over a weighted adjacency (GSUnsupervised(weighted_walks=True)): the
 builder's steps and every hop of the frontier are drawn from the adjacency's per-edge table.
+
+Both record gsage_unsup_batch_biased as their builder when the model's walk_p / walk_q are not neutral (include/gsage.h,
+"Biased walks"): the same buffers and call index; nothing else of the step changes.
 """
 import ctypes
 
@@ -143,9 +146,21 @@ class FusedUnsupMeanTrainStep(FusedMeanTrainStep):
         self._warm_reset = tuple(self._warm_reset) + (self.batch_ctr,)
 
     # ---- stages ----------------------------------------------------------------------------------------------------
+    def _stage_batch_biased(self, s, edge_cdf):
+        """gsage_unsup_batch_biased (the model's walk_p / walk_q are not neutral): the same buffers, the same stream"""
+        csr, cdf, m = self.walk_csr, self.cdf, self.model
+        self._time_next(*self.TIMED["builder"])
+        nat.check(nat.lib().gsage_unsup_batch_biased(
+            csr.rowptr.data_ptr(), csr.col.data_ptr(), edge_cdf, csr.n_rows, self.seeds.data_ptr(), self.Bs, m.walk_len,
+            self.Q, cdf.data_ptr(), cdf._gsage_total, int(getattr(self.sampler, "seed", 0)), self.batch_ctr.data_ptr(),
+            self._call_base, 0, float(m.walk_p), float(m.walk_q), self.ids_set[s].data_ptr(), self.pair_w.data_ptr(),
+            csr.err_flag.data_ptr(), ops._stream()), "unsup_batch_biased")
+
     def _stage_batch(self, s):
         """gsage_unsup_batch: the seed buffer -> the first R ids of the frontier buffer + pair_w"""
         csr, cdf, m = self.walk_csr, self.cdf, self.model
+        if getattr(m, "biased_walks", False):
+            return self._stage_batch_biased(s, None)
         self._time_next(*self.TIMED["builder"])
         nat.check(nat.lib().gsage_unsup_batch(
             csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.n_rows, self.seeds.data_ptr(), self.Bs, m.walk_len, self.Q,
@@ -270,6 +285,8 @@ class FusedUnsupWeightedMeanTrainStep(FusedUnsupMeanTrainStep):
     def _stage_batch(self, s):
         """gsage_unsup_batch_weighted: the seed buffer -> the first R ids of the frontier buffer + pair_w"""
         csr, cdf, m = self.walk_csr, self.cdf, self.model
+        if getattr(m, "biased_walks", False):
+            return self._stage_batch_biased(s, csr.edge_cdf.data_ptr())
         self._time_next(*self.TIMED["builder"])
         nat.check(nat.lib().gsage_unsup_batch_weighted(
             csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.edge_cdf.data_ptr(), csr.n_rows, self.seeds.data_ptr(),

@@ -212,17 +212,22 @@ class GSUnsupervised(_SageModel):
     weighted_walks=True (a sampler over a weighted adjacency: SparseWeightedNeighborSampler): every step of a walk is
     drawn in proportion to the edge weights (gsage_unsup_batch_weighted), so the positives follow the neighbourhoods the
     encoder aggregates over, in training and in evaluate alike, and a row without a drawable edge is never a negative.
-    False: uniform steps over the stored edges, whatever the sampler."""
+    False: uniform steps over the stored edges, whatever the sampler.
+
+    walk_p, walk_q (in [1/8, 8]): node2vec's return and in-out parameters -- every step of a walk after its first is a
+    second-order step (include/gsage.h, "Biased walks", gsage_unsup_batch_biased); composes with weighted_walks (the
+    proposals are then drawn by edge weight).  1, 1: the plain walks, the entries and the bits of before."""
 
     def __init__(self, input_dim, n_nodes, layer_specs, aggregator_class, prep_class, sampler_class, adj, train_adj,
                  lr_init=0.01, weight_decay=0.0, lr_schedule='constant', epochs=10, walk_len=5, n_negatives=20,
-                 neg_weight=1.0, weighted_walks=False):
+                 neg_weight=1.0, weighted_walks=False, walk_p=1.0, walk_q=1.0):
         super(GSUnsupervised, self).__init__()
         assert 1 <= walk_len <= 16 and 1 <= n_negatives <= 64, "GSUnsupervised: walk_len in 1..16, n_negatives in 1..64"
         self.output_dim = self._build_encoder(input_dim, n_nodes, layer_specs, aggregator_class, prep_class,
                                               sampler_class, adj, train_adj)
         self.walk_len, self.n_negatives, self.neg_weight = int(walk_len), int(n_negatives), float(neg_weight)
         self.weighted_walks = bool(weighted_walks)
+        self.walk_p, self.walk_q, _ = ops.walk_bias_check(walk_p, walk_q, 0.0, "GSUnsupervised")
         if self.weighted_walks:
             for s in (self.train_sampler, self.val_sampler):
                 host = None if isinstance(s, UniformNeighborSampler) else s.csr("cpu")
@@ -234,8 +239,13 @@ class GSUnsupervised(_SageModel):
         self._batch_calls = [0, 0]            # Philox call index of the next batch: evaluation, training
 
     def extra_repr(self):
-        return "walk_len=%d, n_negatives=%d, neg_weight=%g%s" % (self.walk_len, self.n_negatives, self.neg_weight,
-                                                                   ", weighted_walks=True" if self.weighted_walks else "")
+        bias = ", walk_p=%g, walk_q=%g" % (self.walk_p, self.walk_q) if self.biased_walks else ""
+        return "walk_len=%d, n_negatives=%d, neg_weight=%g%s%s" % (
+            self.walk_len, self.n_negatives, self.neg_weight, ", weighted_walks=True" if self.weighted_walks else "", bias)
+
+    @property
+    def biased_walks(self):
+        return (self.walk_p, self.walk_q) != (1.0, 1.0)
 
     def forward(self, ids, feats, train=True):
         return F.normalize(self._encode(ids, feats, train), dim=1)
@@ -263,7 +273,8 @@ class GSUnsupervised(_SageModel):
         ph = {"seed": int(getattr(sampler, "seed", 0)), "call_base": self._batch_calls[int(train)],
               "g0": rank * int(ids.shape[0])}
         self._batch_calls[int(train)] += 1
-        return ops.unsup_batch(csr, ids, self.walk_len, self.n_negatives, cdf, ph, weighted=self.weighted_walks)
+        return ops.unsup_batch(csr, ids, self.walk_len, self.n_negatives, cdf, ph, weighted=self.weighted_walks,
+                               p=self.walk_p, q=self.walk_q)
 
     def _loss_inputs(self, ids, feats, batch, train):
         all_ids, pair_w = batch if batch is not None else self.build_batch(ids, train=train)

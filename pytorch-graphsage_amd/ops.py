@@ -12,6 +12,7 @@ done by the HIP kernels behind include/gsage.h.  Dispatch rule (no silent fallba
 Reference call sites each operator replaces are cited per function.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -586,8 +587,38 @@ def _philox4_np(c, k0, k1):
     return c
 
 
-def _importance_host(csr, idn, R, L, T, seed):
+# ---- biased walks (include/gsage.h, "Biased walks"): node2vec's return / in-out parameters, restarts
+WALK_BIAS_TAG = 0x42000000                            # | (step << 8) | round: the builder's rounds, a Philox block each
+WALK_ROUNDS = 32
+WALK_PQ_MIN, WALK_PQ_MAX = 0.125, 8.0
+
+
+def walk_bias_check(p, q, restart=0.0, who="unsup_batch_biased"):
+    """ValueError for p, q or restart outside the limits of the biased entries (the library's own sentences)."""
+    p, q, restart = float(p), float(q), float(restart)
+    if not WALK_PQ_MIN <= p <= WALK_PQ_MAX:                                          # (False for NaN)
+        raise ValueError("%s: p must be in [1/8, 8] (got %g)" % (who, p))
+    if not WALK_PQ_MIN <= q <= WALK_PQ_MAX:
+        raise ValueError("%s: q must be in [1/8, 8] (got %g)" % (who, q))
+    if not 0.0 <= restart < 1.0:
+        raise ValueError("%s: restart must be in [0, 1) (got %g)" % (who, restart))
+    return p, q, restart
+
+
+def walk_thresholds(p, q, restart=0.0):
+    """-> (theta_return, theta_near, theta_far, theta_restart): the integers the biased kernels compare 32-bit words
+    with, from the same double arithmetic as the library's host code."""
+    p, q, restart = walk_bias_check(p, q, restart, "walk_thresholds")
+    a = (1.0 / p, 1.0, 1.0 / q)
+    a_max = max(a)
+    th = tuple(1 << 32 if x == a_max else int(math.floor((x / a_max) * 4294967296.0)) for x in a)
+    return th + (int(math.floor(restart * 4294967296.0)),)
+
+
+def _importance_host(csr, idn, R, L, T, seed, bias=None):
     """gsage_importance_walks in numpy: every (source, walk) pair is one element, the steps are the loop.
+    bias: None, or walk_thresholds(p, q, restart) -- gsage_importance_walks_biased: up to 32 rounds per step over the
+    elements still without an accepted proposal; "x is stored in row t" is a search in the sorted (row, column) keys.
     -> (col int32 [M, T], w fp32 [M, T], deg int32 [M], err)"""
     rp, col, n_rows = csr.rowptr.numpy(), csr.col.numpy(), csr.n_rows
     cdf = csr.edge_cdf.numpy().view(np.uint64) if csr.edge_cdf is not None else None
@@ -600,6 +631,14 @@ def _importance_host(csr, idn, R, L, T, seed):
         return out_col, out_w, out_deg, err
     k0, k1 = seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ IMPORTANCE_TAG
     s32 = np.uint64(32)
+    th_ret = th_near = th_far = 1 << 32
+    th_restart = 0
+    if bias is not None:
+        th_ret, th_near, th_far, th_restart = bias
+    second = min(th_ret, th_near, th_far) < (1 << 32)         # thresholds that can reject
+    if second:
+        row_of = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(rp[:n_rows + 1]))
+        edge_keys = np.unique((row_of << 32) | (col.astype(np.int64) & 0xFFFFFFFF))
     per = max(1, (1 << 21) // R)                          # sources per piece: the working arrays stay at ~2 M elements
     for o in range(0, M, per):
         v = idn[o:o + per]
@@ -608,21 +647,34 @@ def _importance_host(csr, idn, R, L, T, seed):
         r = np.tile(np.arange(R, dtype=np.uint64), m)
         alive = np.repeat(in_range[o:o + per], R)
         u = np.where(alive, vv, 0)
+        prev = np.full(m * R, -1, dtype=np.int64)
         c0, zero = vv.astype(np.uint64) & np.uint64(0xFFFFFFFF), np.zeros(m * R, dtype=np.uint64)
         land_src, land_id = [], []
         for s in range(L):
             if not s & 1:
                 w = _philox4_np([c0, r, np.full(m * R, s >> 1, dtype=np.uint64), zero], k0, k1)
             r64 = (w[2] << s32) | w[3] if s & 1 else (w[0] << s32) | w[1]
+            moving = alive
+            nb0 = None
+            if second or (th_restart and s >= 1):
+                nb0 = _philox4_np([c0, r, np.full(m * R, s, dtype=np.uint64), zero + np.uint64(1)], k0, k1)
+            if th_restart and s >= 1:                     # back on the source: nothing counted, the step is consumed
+                again = moving & (nb0[3] < np.uint64(th_restart))
+                u, prev, moving = np.where(again, vv, u), np.where(again, -1, prev), moving & ~again
             beg, end = rp[u], rp[u + 1]
             if cdf is None:
-                go = alive & (end > beg)
-                e = beg + _mulhi64(r64, np.where(go, end - beg, 0).astype(np.uint64)).astype(np.int64)
+                go = moving & (end > beg)
+                Tu = None
             else:
                 Tu = np.where(end > beg, cdf[np.maximum(end, 1) - 1], np.uint64(0)).astype(np.uint64)
-                go = alive & (Tu > 0)
-                x = _mulhi64(r64, Tu)
-                lo, hi = np.where(go, beg, 0), np.where(go, end - 1, 0)      # cdf[end - 1] = T_u > x
+                go = moving & (Tu > 0)
+
+            def propose(idx, rr):
+                """the first-order step of elements idx (all of them in go) under the draws rr -> edge index"""
+                if cdf is None:
+                    return beg[idx] + _mulhi64(rr, (end[idx] - beg[idx]).astype(np.uint64)).astype(np.int64)
+                x = _mulhi64(rr, Tu[idx])
+                lo, hi = beg[idx].copy(), end[idx] - 1                             # cdf[end - 1] = T_u > x
                 while True:
                     act = lo < hi
                     if not act.any():
@@ -631,13 +683,38 @@ def _importance_host(csr, idn, R, L, T, seed):
                     gt = cdf[mid] > x
                     hi = np.where(act & gt, mid, hi)
                     lo = np.where(act & ~gt, mid + 1, lo)
-                e = lo
-            nu = col[np.where(go, e, 0)].astype(np.int64)
-            inside = (nu >= 0) & (nu < n_rows)
-            err = err or bool((go & ~inside).any())
-            alive = go & inside
-            u = np.where(alive, nu, 0)
-            counted = alive & (u != vv)
+                return lo
+
+            x = np.zeros(m * R, dtype=np.int64)
+            pending = go.copy()
+            for k in range(WALK_ROUNDS if second else 1):
+                idx = np.flatnonzero(pending)
+                if idx.size == 0:
+                    break
+                if k == 0:
+                    rr, acc = r64[idx], (nb0[2][idx] if second else None)
+                else:
+                    nb = _philox4_np([c0[idx], r[idx], np.full(idx.size, s, dtype=np.uint64),
+                                      np.full(idx.size, 1 + k, dtype=np.uint64)], k0, k1)
+                    rr, acc = (nb[0] << s32) | nb[1], nb[2]
+                nx = col[propose(idx, rr)].astype(np.int64)
+                inside = (nx >= 0) & (nx < n_rows)
+                err = err or not bool(inside.all())
+                x[idx] = nx
+                go[idx[~inside]] = False                  # a stored id outside the graph: the walk ends, not counted
+                done = ~inside
+                if second:
+                    t = prev[idx]
+                    key = (np.maximum(t, 0) << 32) | np.where(inside, nx, 0)
+                    at = np.minimum(np.searchsorted(edge_keys, key), edge_keys.shape[0] - 1)
+                    th = np.where(nx == t, th_ret, np.where(edge_keys[at] == key, th_near, th_far)).astype(np.uint64)
+                    done = done | (t < 0) | (acc < th)
+                else:
+                    done = np.ones(idx.size, dtype=bool)
+                pending[idx[done]] = False                # (still pending after the last round: that round's proposal)
+            alive = np.where(moving, go, alive)
+            prev, u = np.where(go, u, prev), np.where(go, x, u)
+            counted = go & (u != vv)
             land_src.append(src[counted])
             land_id.append(u[counted])
         uniq, count = np.unique((np.concatenate(land_src) << 32) | np.concatenate(land_id), return_counts=True)
@@ -652,14 +729,19 @@ def _importance_host(csr, idn, R, L, T, seed):
     return out_col, out_w, out_deg, err
 
 
-def importance_walks(csr, ids, n_walks, walk_len, top, seed):
+def importance_walks(csr, ids, n_walks, walk_len, top, seed, p=1.0, q=1.0, restart=0.0, _biased=None):
     """Importance neighbourhoods (include/gsage.h, gsage_importance_walks): from every source in ids (LongTensor [M]
     on csr.device), n_walks random walks of walk_len steps -- weighted steps exactly when csr.edge_cdf is not None --
     and the `top` most-visited nodes, visit count descending then id ascending.
+    p, q (in [1/8, 8]) and restart (in [0, 1)): node2vec's return and in-out parameters and a restart probability
+    (include/gsage.h, "Biased walks", gsage_importance_walks_biased); the neutral values 1, 1, 0 call the entry this
+    function always called (_biased=True: the biased entry all the same -- the same bits).
     -> (col int32 [M, top], w fp32 [M, top] = the counts, deg int32 [M]); entries at and beyond deg are 0.
     An id outside the graph (a source, or a stored neighbour a walk reaches) raises csr.err_flag: csr.check().
     CPU tensors: the same definition in numpy (host mode), the same bits."""
     n_walks, walk_len, top, seed = int(n_walks), int(walk_len), int(top), int(seed) & 0xFFFFFFFFFFFFFFFF
+    p, q, restart = walk_bias_check(p, q, restart, "importance_walks_biased")
+    biased = (p, q, restart) != (1.0, 1.0, 0.0) if _biased is None else bool(_biased)
     importance_check(n_walks, walk_len, top)
     ids = ids.contiguous().view(-1)
     assert ids.dtype == torch.int64 and ids.device == csr.rowptr.device
@@ -668,11 +750,18 @@ def importance_walks(csr, ids, n_walks, walk_len, top, seed):
         col = torch.empty(M, top, dtype=torch.int32, device=ids.device)
         w = torch.empty(M, top, dtype=torch.float32, device=ids.device)
         deg = torch.empty(M, dtype=torch.int32, device=ids.device)
+        if biased:
+            nat.check(nat.lib().gsage_importance_walks_biased(
+                _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.edge_cdf), csr.n_rows, _ptr(ids), M, n_walks, walk_len, top,
+                seed, p, q, restart, _ptr(col), _ptr(w), _ptr(deg), _ptr(csr.err_flag), _stream()),
+                "importance_walks_biased")
+            return col, w, deg
         nat.check(nat.lib().gsage_importance_walks(_ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.edge_cdf), csr.n_rows,
                                                    _ptr(ids), M, n_walks, walk_len, top, seed, _ptr(col), _ptr(w),
                                                    _ptr(deg), _ptr(csr.err_flag), _stream()), "importance_walks")
         return col, w, deg
-    col, w, deg, err = _importance_host(csr, ids.numpy(), n_walks, walk_len, top, seed)
+    col, w, deg, err = _importance_host(csr, ids.numpy(), n_walks, walk_len, top, seed,
+                                        walk_thresholds(p, q, restart) if biased else None)
     if err:
         csr.err_flag.fill_(1)
     return torch.from_numpy(col), torch.from_numpy(w), torch.from_numpy(deg)
@@ -733,15 +822,20 @@ def neg_cdf(csr, weighted=False):
     return cdf
 
 
-def unsup_batch(csr, seeds, walk_len, Q, cdf, philox, weighted=False):
+def unsup_batch(csr, seeds, walk_len, Q, cdf, philox, weighted=False, p=1.0, q=1.0, _biased=None):
     """The id batch of one unsupervised step (include/gsage.h, gsage_unsup_batch): -> (ids int64 [2B + Q] =
     [seeds | random-walk positives | negatives], pair_w fp32 [B]: 0 where a walk ended on its own seed).
     cdf: neg_cdf(csr) (any float64 inclusive running sum of row weights will do); philox: dict(seed, call_base,
     g0, call_ctr) as for sample_csr.  weighted=True: every step is drawn in proportion to the edge quanta of
     csr.edge_cdf (gsage_unsup_batch_weighted; cdf: neg_cdf(csr, weighted=True)).
+    p, q (in [1/8, 8]): node2vec's return and in-out parameters -- every step after a walk's first is a second-order
+    step (include/gsage.h, "Biased walks", gsage_unsup_batch_biased); p = q = 1 calls the entries this function
+    always called (_biased=True: the biased entry all the same -- the same bits).
     CPU tensors: the same definition in numpy / Python integers (host mode)."""
     if weighted and csr.edge_cdf is None:
         raise ValueError("unsup_batch: weighted=True needs an adjacency with edge weights (DeviceCSR.with_weights)")
+    p, q, _ = walk_bias_check(p, q, 0.0, "unsup_batch_biased")
+    biased = (p, q) != (1.0, 1.0) if _biased is None else bool(_biased)
     seeds = seeds.contiguous().view(-1)
     B, Q, walk_len = int(seeds.shape[0]), int(Q), int(walk_len)
     total = getattr(cdf, "_gsage_total", None)
@@ -753,6 +847,12 @@ def unsup_batch(csr, seeds, walk_len, Q, cdf, philox, weighted=False):
         assert cdf.dtype == torch.float64 and cdf.is_cuda and cdf.is_contiguous() and cdf.numel() == csr.n_rows
         ids = torch.empty(2 * B + Q, dtype=torch.int64, device=seeds.device)
         pair_w = torch.empty(B, dtype=torch.float32, device=seeds.device)
+        if biased:
+            nat.check(nat.lib().gsage_unsup_batch_biased(
+                _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.edge_cdf) if weighted else None, csr.n_rows, _ptr(seeds), B,
+                walk_len, Q, _ptr(cdf), total, seed, _ptr(ctr), base, g0, p, q, _ptr(ids), _ptr(pair_w),
+                _ptr(csr.err_flag), _stream()), "unsup_batch_biased")
+            return ids, pair_w
         if weighted:
             nat.check(nat.lib().gsage_unsup_batch_weighted(
                 _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.edge_cdf), csr.n_rows, _ptr(seeds), B, walk_len, Q, _ptr(cdf),
@@ -775,13 +875,15 @@ def unsup_batch(csr, seeds, walk_len, Q, cdf, philox, weighted=False):
     ecdf = csr.edge_cdf.numpy().view(np.uint64) if weighted else None
     if sd.min() < 0 or sd.max() >= n_rows:
         raise IndexError("unsup_batch: node id out of range of the adjacency")
+    th_ret, th_near, th_far, _ = walk_thresholds(p, q) if biased else (1 << 32, 1 << 32, 1 << 32, 0)
+    rejecting = min(th_ret, th_near, th_far) < (1 << 32)
     ids = np.zeros(2 * B + Q, dtype=np.int64)
     pair_w = np.zeros(B, dtype=np.float32)
     for i in range(B):
         g = (g0 + i) & 0xFFFFFFFFFFFFFFFF
         c = (g & 0xFFFFFFFF, g >> 32, clo, chi)
         t = 1 + ((_philox4(c, (klo, khi ^ UNSUP_TAG_LEN))[0] * walk_len) >> 32)
-        v, r = int(sd[i]), None
+        v, prev, r = int(sd[i]), -1, None
         for j in range(t):
             beg = int(rp[v])
             deg = int(rp[v + 1]) - beg
@@ -793,21 +895,35 @@ def unsup_batch(csr, seeds, walk_len, Q, cdf, philox, weighted=False):
                     break
                 if j & 1 == 0:
                     r = _philox4(c, (klo, khi ^ (UNSUP_TAG_WSTEP | (j >> 1))))
-                x = (((r[2 * (j & 1)] << 32) | r[2 * (j & 1) + 1]) * T) >> 64
-                v = int(col[beg + int(np.searchsorted(ecdf[beg:beg + deg], np.uint64(x), side="right"))])
-            else:
-                if j & 3 == 0:
-                    r = _philox4(c, (klo, khi ^ (UNSUP_TAG_STEP | (j >> 2))))
-                word = r[j & 3]
-                v = int(col[beg + ((word * deg) >> 32 if deg <= 0xFFFFFFFF else word)])
-            if v < 0 or v >= n_rows:
-                raise IndexError("unsup_batch: node id out of range of the adjacency")
+            elif j & 3 == 0:
+                r = _philox4(c, (klo, khi ^ (UNSUP_TAG_STEP | (j >> 2))))
+            second = rejecting and j > 0                       # a second-order step: up to 32 rounds of rejection
+            for k in range(WALK_ROUNDS if second else 1):
+                nb = _philox4(c, (klo, khi ^ (WALK_BIAS_TAG | (j << 8) | k))) if second else None
+                if weighted:
+                    r64 = (r[2 * (j & 1)] << 32) | r[2 * (j & 1) + 1] if k == 0 else (nb[0] << 32) | nb[1]
+                    x = (r64 * T) >> 64
+                    x = int(col[beg + int(np.searchsorted(ecdf[beg:beg + deg], np.uint64(x), side="right"))])
+                else:
+                    word = r[j & 3] if k == 0 else nb[0]
+                    x = int(col[beg + ((word * deg) >> 32 if deg <= 0xFFFFFFFF else word)])
+                if x < 0 or x >= n_rows:
+                    raise IndexError("unsup_batch: node id out of range of the adjacency")
+                if not second:
+                    break
+                if x == prev:
+                    th = th_ret
+                else:
+                    th = th_near if bool((col[int(rp[prev]):int(rp[prev + 1])] == x).any()) else th_far
+                if nb[2] < th:
+                    break
+            prev, v = v, x
         ids[i], ids[B + i], pair_w[i] = sd[i], v, 0.0 if v == sd[i] else 1.0
     cn = cdf.numpy()
-    for q in range(Q):
-        r = _philox4((q & 0xFFFFFFFF, q >> 32, clo, chi), (klo, khi ^ UNSUP_TAG_NEG))
+    for q_ in range(Q):
+        r = _philox4((q_ & 0xFFFFFFFF, q_ >> 32, clo, chi), (klo, khi ^ UNSUP_TAG_NEG))
         x = np.float64((r[0] << 21) | (r[1] >> 11)) * np.float64(2.0 ** -53) * np.float64(total)
-        ids[2 * B + q] = min(int(np.searchsorted(cn, x, side="right")), n_rows - 1)
+        ids[2 * B + q_] = min(int(np.searchsorted(cn, x, side="right")), n_rows - 1)
     return torch.from_numpy(ids), torch.from_numpy(pair_w)
 
 

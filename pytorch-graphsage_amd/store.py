@@ -132,15 +132,16 @@ class DeviceCSR(object):
         self.edge_cdf = ops.edge_cdf(self.rowptr, w, self.n_rows)
         return self
 
-    def _importance_rows(self, n_walks, walk_len, top, seed, chunk):
+    def _importance_rows(self, n_walks, walk_len, top, seed, chunk, p=1.0, q=1.0, restart=0.0):
         """(rowptr int64 [n_rows + 1], col int32 [nnz], counts fp32 [nnz]) of importance(), on this adjacency's device"""
         from . import ops
         ops.importance_check(int(n_walks), int(walk_len), int(top))
+        ops.walk_bias_check(p, q, restart, "importance_walks_biased")
         chunk = max(int(chunk), 1)
         degs, cols, counts = [], [], []
         for o in range(0, self.n_rows, chunk):
             ids = torch.arange(o, min(o + chunk, self.n_rows), dtype=torch.int64, device=self.device)
-            c, w, d = ops.importance_walks(self, ids, n_walks, walk_len, top, seed)
+            c, w, d = ops.importance_walks(self, ids, n_walks, walk_len, top, seed, p=p, q=q, restart=restart)
             c, w = ops.importance_compact(c, w, d)        # (the padded buffers of a chunk end here)
             degs.append(d)
             cols.append(c)
@@ -153,16 +154,17 @@ class DeviceCSR(object):
         torch.cumsum(torch.cat(degs), 0, dtype=torch.int64, out=rowptr[1:])
         return rowptr, torch.cat(cols), torch.cat(counts)
 
-    def importance(self, n_walks=50, walk_len=2, top=16, seed=0, chunk=1 << 20):
+    def importance(self, n_walks=50, walk_len=2, top=16, seed=0, chunk=1 << 20, p=1.0, q=1.0, restart=0.0):
         """The importance-weighted adjacency of this one (include/gsage.h, "Importance neighbourhoods"): from every
         row, n_walks random walks of walk_len steps (weighted steps when this adjacency carries an edge_cdf); the row's
         new neighbours are its `top` most-visited nodes, most visited first, and the visit counts are the edge weights.
         -> a new DeviceCSR over the same n_rows with max_deg = top and its edge_cdf (with_weights(counts)).  Built
         `chunk` rows at a time: the padded [chunk, top] buffers are all that exists beside the result.  IndexError
         (check()) when a stored neighbour id lies outside the graph.  n_walks in 1.., walk_len in 1..16, top in 1..64,
-        n_walks * walk_len <= 4096.  The defaults reach the toy results of the tests; nobody has tuned them on a real
-        graph."""
-        rowptr, col, counts = self._importance_rows(n_walks, walk_len, top, seed, chunk)
+        n_walks * walk_len <= 4096.  p, q in [1/8, 8] and restart in [0, 1): node2vec's return and in-out parameters and
+        a restart probability for the walks (include/gsage.h, "Biased walks"); 1, 1, 0 are the plain walks.  The
+        defaults reach the toy results of the tests; nobody has tuned them on a real graph."""
+        rowptr, col, counts = self._importance_rows(n_walks, walk_len, top, seed, chunk, p, q, restart)
         return DeviceCSR(rowptr, col, self.n_rows, int(top)).with_weights(counts)
 
     @staticmethod
@@ -234,14 +236,15 @@ class DeviceCSR(object):
         return DeviceCSR(rowptr, col, n_rows, max_deg if max_deg is not None else int(deg_hi))
 
 
-def importance_adj(adj, n_walks=50, walk_len=2, top=16, seed=0, device=None):
+def importance_adj(adj, n_walks=50, walk_len=2, top=16, seed=0, device=None, p=1.0, q=1.0, restart=0.0):
     """Any sparse adjacency -> its importance-weighted one (DeviceCSR.importance), as the WeightedAdj a weighted problem
     would hand to the samplers.  adj: a scipy matrix in the reference's sparse convention, or a WeightedAdj (its walks
     then step in proportion to the edge weights).  -> WeightedAdj in the same convention: shape (n_rows, top), row v in
     columns 0..k_v - 1, data the neighbour ids most visited first, weight the visit counts.  Accepted as it is by
     sparse_weighted_neighbor_sampler, by full-neighbourhood inference (mean and mean-pool models, as for any weighted
     graph) and by DeviceCSR.from_scipy.  device: where the walks run -- default the GPU when there is one, else host
-    mode (the same rows).  The defaults reach the toy results of the tests; nobody has tuned them on a real graph."""
+    mode (the same rows).  p, q, restart: as for DeviceCSR.importance (biased walks, restarts).  The defaults reach the
+    toy results of the tests; nobody has tuned them on a real graph."""
     from scipy import sparse
     if device is None:
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -249,7 +252,7 @@ def importance_adj(adj, n_walks=50, walk_len=2, top=16, seed=0, device=None):
         csr = DeviceCSR.from_scipy(adj.adj, device, weight=adj.weight)
     else:
         csr = DeviceCSR.from_scipy(adj, device)
-    rowptr, col, counts = csr._importance_rows(n_walks, walk_len, top, seed, 1 << 20)
+    rowptr, col, counts = csr._importance_rows(n_walks, walk_len, top, seed, 1 << 20, p, q, restart)
     indptr = rowptr.cpu().numpy()
     out = sparse.csr_matrix((col.cpu().numpy().astype(np.int64), row_positions(indptr), indptr),
                             shape=(csr.n_rows, int(top)))

@@ -124,6 +124,16 @@ nodes as neighbours, the visit counts as edge weights; the training graph's walk
 run is a weighted one: --sampler-class sparse_uniform_neighbor_sampler is switched to the weighted sampler (said on
 stderr), the dense sampler is refused, and everything the weighted sampler refuses or redirects stays as it is.  The
 defaults of L and T (2, 16) reach the toy results of the tests; nobody has tuned them on a real graph.
+
+--walk-p P / --walk-q Q (with --unsupervised; default 1, 1: nothing changes) and --importance-p P / --importance-q Q /
+--importance-restart A (with --importance-walks; default 1, 1, 0: nothing changes): biased walks (include/gsage.h,
+"Biased walks").  P and Q, each in [1/8, 8], are node2vec's return and in-out parameters: every step of a walk after its
+first is drawn in second order -- back to the previous node with weight 1/P, to a node the previous node stores as a
+neighbour with weight 1, elsewhere with weight 1/Q (gsage_unsup_batch_biased for the positives, under --weighted-walks
+on top of the edge weights, on the module path and on the fused unsupervised engines alike;
+gsage_importance_walks_biased for the neighbourhoods).  A in [0, 1) sends a neighbourhood's walk back to its source
+before a step with that probability (personalised-PageRank visit counts).  Values outside the limits, --walk-p / --walk-q
+without --unsupervised and --importance-p / -q / -restart without --importance-walks are errors.
 """
 from __future__ import division, print_function
 
@@ -411,6 +421,14 @@ def parse_args(argv=None):
     parser.add_argument('--importance-len', type=int, default=2)
     parser.add_argument('--importance-top', type=int, default=16)
     parser.add_argument('--importance-seed', type=int, default=0)
+    parser.add_argument('--walk-p', type=float, default=1.0,
+                        help='with --unsupervised: node2vec return parameter of the walks, in [1/8, 8]')
+    parser.add_argument('--walk-q', type=float, default=1.0,
+                        help='with --unsupervised: node2vec in-out parameter of the walks, in [1/8, 8]')
+    parser.add_argument('--importance-p', type=float, default=1.0)
+    parser.add_argument('--importance-q', type=float, default=1.0)
+    parser.add_argument('--importance-restart', type=float, default=0.0,
+                        help='with --importance-walks: probability in [0, 1) that a step puts the walk back on its node')
 
     args = parser.parse_args(argv)
     args.cuda = not args.no_cuda
@@ -438,7 +456,8 @@ def importance_graphs(args, problem):
         args.sampler_class = 'sparse_weighted_neighbor_sampler'
     device = torch.device('cuda' if args.cuda else 'cpu')
     kw = dict(n_walks=args.importance_walks, walk_len=args.importance_len, top=args.importance_top,
-              seed=args.importance_seed, device=device)
+              seed=args.importance_seed, device=device, p=args.importance_p, q=args.importance_q,
+              restart=args.importance_restart)
     t0 = time()
     try:
         same = problem.train_adj is problem.adj
@@ -474,7 +493,8 @@ def build_model(args, problem):
         weight_decay=args.weight_decay)
     if args.unsupervised:
         return gs.GSUnsupervised(walk_len=args.walk_len, n_negatives=args.n_negatives, neg_weight=args.neg_weight,
-                                 weighted_walks=args.weighted_walks, **common)
+                                 weighted_walks=args.weighted_walks, walk_p=args.walk_p, walk_q=args.walk_q,
+                                 **common)
     return GSSupervised(n_classes=problem.n_classes, **common)
 
 
@@ -512,6 +532,17 @@ def main(argv=None, problem=None):
         raise SystemExit('gsage: --unsupervised: --wide-head fuses a supervised head; there is none')
     if args.weighted_walks and not args.unsupervised:
         raise SystemExit('gsage: --weighted-walks: the walks belong to --unsupervised training (add --unsupervised)')
+    if (args.walk_p, args.walk_q) != (1.0, 1.0) and not args.unsupervised:
+        raise SystemExit('gsage: --walk-p / --walk-q: the walks belong to --unsupervised training (add --unsupervised)')
+    if (args.importance_p, args.importance_q, args.importance_restart) != (1.0, 1.0, 0.0) and not args.importance_walks:
+        raise SystemExit('gsage: --importance-p / --importance-q / --importance-restart: there are no walks to bias '
+                         '(add --importance-walks R)')
+    for flag, val in (('--walk-p', args.walk_p), ('--walk-q', args.walk_q), ('--importance-p', args.importance_p),
+                      ('--importance-q', args.importance_q)):
+        if not gs.ops.WALK_PQ_MIN <= val <= gs.ops.WALK_PQ_MAX:
+            raise SystemExit('gsage: %s must be in [1/8, 8] (got %g)' % (flag, val))
+    if not 0.0 <= args.importance_restart < 1.0:
+        raise SystemExit('gsage: --importance-restart must be in [0, 1) (got %g)' % args.importance_restart)
     if args.unsupervised and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("GSAGE_FORCE_DDP", "0") == "1"):
         raise SystemExit('gsage: --unsupervised: data-parallel training is not supported (run a single process)')
     ddp = gs.dist.init_from_env(args.cuda)            # no-op outside torch.distributed.run
