@@ -1577,6 +1577,50 @@ int gsage_probe_pass(const void *table, int dtype, int64_t ldx, int64_t N, const
                      const void *targets, int task, int64_t ldy, const float *W, const float *bias, int32_t C,
                      int32_t D, int32_t splits, float *partial, float *loss_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Graph propagation (csrc/gsage_propagate.hip): one step of label / residual propagation over a CSR adjacency
+ * (propagate.py: label propagation, Correct and Smooth, SGC / APPNP-style feature smoothing).  Additive; the ABI
+ * version is unchanged.  All values are fp32.
+ *
+ *     acc[v, c]  = sum over e in [rowptr[v], rowptr[v+1]) of y[col[e], c]
+ *                  in stored-edge order within a slice and slice order within a row;
+ *                  an empty row gives 0, NOT the dummy;
+ *                  an id outside [0, n_rows) contributes 0 and raises *err_flag (int32, may be NULL)
+ *     out[v, c]  = min(max(beta * base[v, c] + alpha * (a[v] * acc[v, c]), lo), hi)
+ *                  for c < C;  lo = -inf and hi = +inf switch the clamp off
+ *     yout[v, c] = b[v] * out[v, c]      (b == NULL: yout = out; a == NULL: a[v] = 1)
+ *
+ * y is the PRE-SCALED iterate b (.) x: the neighbour loop is a plain sum of 16-byte row chunks with no per-neighbour
+ * scale fetch, and the kernel produces the next iteration's y in its own epilogue.  out or yout may be NULL, not both.
+ * y must not alias out or yout (the caller ping-pongs two buffers).  base may be NULL only with beta == 0.
+ *
+ * gsage_propagate_scales fills a and b (fp32 [n_rows] each) from the row degrees deg[v] = rowptr[v+1] - rowptr[v]:
+ *     norm = GSAGE_PROP_SYM:  a = b = deg^-1/2, and 0 where deg == 0
+ *     norm = GSAGE_PROP_ROW:  a = 1 / deg (0 where deg == 0), b = 1
+ *     norm = GSAGE_PROP_COL:  a = 1, b = 1 / deg (0 where deg == 0)
+ * On an adjacency that stores both directions of every edge, "sym" is D^-1/2 A D^-1/2.  On any other adjacency it is
+ * the definition above applied to the stored rows: the scales are those of the stored rows' degrees, nothing is
+ * symmetrised.  One launch.
+ *
+ * Plan, partials and schedule are gsage_segment_reduce's (order / slices / long_rows over slice_len, partials fp32
+ * [n_slices, ldp], unused if n_slices == 0): a team of 8 / 16 / 32 / 64 lanes per short row or slice, one 16-byte chunk
+ * (4 columns) per lane, 8 neighbour rows in flight per lane; the merge of a long row's slices applies a, base, alpha,
+ * beta, the clamp and b exactly as the short-row path does.  Two launches per call, whatever the graph; no
+ * floating-point atomics: the same inputs give the same bits.  Recordable in a command list.
+ *
+ * Limits (GSAGE_EINVAL, with a message, before anything is launched): 1 <= C <= 1024; y, base, out, yout 16-byte
+ * aligned with ldy, ldb, ldo, ldyo multiples of 4 floats and >= round_up(C, 4) (columns >= C are read from y and base
+ * but never stored); ldp >= gsage_segment_reduce_ldp(C); lo <= hi; 1 <= n_rows < 2^31; slice_len a positive multiple of 8.
+ * ---------------------------------------------------------------------------------------- */
+enum { GSAGE_PROP_SYM = 0, GSAGE_PROP_ROW = 1, GSAGE_PROP_COL = 2 };
+int gsage_propagate_scales(const int64_t *rowptr, int64_t n_rows, int norm, float *a, float *b, void *stream);
+int gsage_propagate(const float *y, int64_t ldy, const float *base, int64_t ldb, const float *a, const float *b,
+                    float alpha, float beta, float lo, float hi, int64_t C,
+                    const int64_t *rowptr, const int32_t *col, int64_t n_rows,
+                    const int32_t *order, int64_t n_short, const int64_t *slices, int64_t n_slices,
+                    const int64_t *long_rows, int64_t n_long, int32_t slice_len, float *partials, int64_t ldp,
+                    float *out, int64_t ldo, float *yout, int64_t ldyo, int32_t *err_flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

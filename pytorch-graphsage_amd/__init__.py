@@ -16,6 +16,9 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
                               among all rows, MRR and hits@k (ops.rank_ip, csrc/gsage_rank.hip); infer.linear_probe /
                               probe_eval: a linear classifier fitted on the frozen embeddings, micro / macro F1 of
                               the val / test folds (ops.probe_pass, csrc/gsage_probe.hip)
+    propagate.py              propagation over the graph after the encoder has run: gs.propagate (one fused step of
+                              csrc/gsage_propagate.hip per iteration), gs.label_propagation, gs.correct_and_smooth,
+                              gs.correct_smooth_eval
     store.WeightedAdj         edge weights: sparse_weighted_neighbor_sampler, weight-normalised full-neighbourhood mean
     store.importance_adj      any adjacency -> its importance-weighted one: visit counts of short random walks, the
                               top-T most-visited nodes per row (DeviceCSR.importance, csrc/gsage_importance.hip);
@@ -39,10 +42,13 @@ from .infer import (LinearProbe, embeddings, full_neighbour, held_out_edges, lin
 from .lr import LRSchedule                                          # noqa: F401
 from .models import GSSupervised, GSUnsupervised                                # noqa: F401
 from .nn_modules import aggregator_lookup, find_sampler, prep_lookup, sampler_extensions, sampler_lookup   # noqa: F401
+# (gs.propagate is the FUNCTION; its module is sys.modules[gs.propagate.__module__])
+from .propagate import correct_and_smooth, correct_smooth_eval, label_propagation, propagate   # noqa: F401
 from .problem import DeviceMetrics, NodeProblem, ProblemLosses, ProblemMetrics, batch_metric   # noqa: F401
 from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef, WeightedAdj, importance_adj  # noqa: F401
 
 __all__ = ["GSSupervised", "GSUnsupervised", "NodeProblem", "aggregator_lookup", "prep_lookup", "sampler_lookup",
            "set_seeds", "to_numpy", "LRSchedule", "FeatureStore", "DeviceCSR", "RowRef", "ops", "full_neighbour",
            "embeddings", "query", "nearest", "link_rank", "link_metrics", "held_out_edges", "LinearProbe", "linear_probe",
-           "probe_eval", "WeightedAdj", "find_sampler", "sampler_extensions", "importance_adj"]
+           "probe_eval", "WeightedAdj", "find_sampler", "sampler_extensions", "importance_adj",
+           "propagate", "label_propagation", "correct_and_smooth", "correct_smooth_eval"]

@@ -2283,3 +2283,97 @@ def wide_head(E, W, b, targets, task, n_valid=None, dE_dtype=None):
                                 dE.stride(0), _ptr(dW), _ptr(db), _ptr(loss), _ptr(scratch), None, 0, _stream()),
               "head_wide")
     return preds, loss[0], dE, dW, db
+
+
+# =============================================================================================
+# Graph propagation: one step of label / residual propagation over a CSR adjacency (csrc/gsage_propagate.hip)
+# =============================================================================================
+PROP_NORMS = {"sym": 0, "row": 1, "col": 2}
+PROP_C_MAX = 1024
+
+
+def propagate_norm(norm):
+    if norm not in PROP_NORMS:
+        raise ValueError("propagate: norm must be one of %s, not %r" % (sorted(PROP_NORMS), norm))
+    return PROP_NORMS[norm]
+
+
+def propagate_scales(rowptr, n_rows, norm):
+    """(a, b) fp32 [n_rows] of propagate_step from the row degrees (include/gsage.h, "Graph propagation"): "sym"
+    a = b = deg^-1/2, "row" a = 1 / deg, b = 1, "col" a = 1, b = 1 / deg; 0 where deg == 0.  CUDA: one launch
+    (gsage_propagate_scales); CPU: the same arithmetic in torch."""
+    code, n = propagate_norm(norm), int(n_rows)
+    dev = rowptr.device
+    if rowptr.is_cuda:
+        a, b = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+        nat.check(nat.lib().gsage_propagate_scales(_ptr(rowptr), n, code, _ptr(a), _ptr(b), _stream()), "propagate_scales")
+        return a, b
+    deg = (rowptr[1:n + 1] - rowptr[:n]).float()
+    one, zero = torch.ones(n), torch.zeros(n)
+    inv = torch.where(deg > 0, 1.0 / deg.clamp(min=1), zero)
+    if code == 0:
+        s = torch.where(deg > 0, 1.0 / torch.sqrt(deg.clamp(min=1)), zero)
+        return s, s.clone()
+    return (inv, one) if code == 1 else (one, inv)
+
+
+def _propagate_step_host(adj, y, base, a, b, alpha, beta, lo, hi, C, out, yout):
+    n = int(adj.n_rows)
+    rowptr, col = adj.rowptr[:n + 1], adj.col.long()
+    deg = rowptr[1:] - rowptr[:-1]
+    dst = torch.repeat_interleave(torch.arange(n, dtype=torch.int64), deg)
+    ok = (col >= 0) & (col < n)
+    if not bool(ok.all()):
+        adj.err_flag.fill_(1)                              # the id contributes nothing
+    acc = torch.zeros(n, C, dtype=torch.float32).index_add_(0, dst[ok], y[col[ok], :C].float())
+    if a is not None:
+        acc = a.view(-1, 1) * acc
+    r = alpha * acc
+    if base is not None:
+        r = beta * base[:n, :C].float() + r
+    r = torch.minimum(torch.maximum(r, torch.tensor(lo)), torch.tensor(hi))
+    if out is not None:
+        out[:n, :C] = r
+    if yout is not None:
+        yout[:n, :C] = r if b is None else b.view(-1, 1) * r
+    return out, yout
+
+
+def propagate_step(adj, plan, y, base, a, b, alpha, beta, lo, hi, C, out=None, yout=None, partials=None):
+    """One propagation step over the rows of `adj` (a store.DeviceCSR) -- include/gsage.h, "Graph propagation":
+
+        acc[v]  = sum of y[u, :C] over the stored neighbours u of v        (an empty row: 0; an id outside the graph: 0,
+                                                                            and adj.err_flag is raised)
+        out[v]  = min(max(beta * base[v] + alpha * a[v] * acc[v], lo), hi)
+        yout[v] = b[v] * out[v]
+
+    y: fp32 [n_rows, >= round_up(C, 4)] (the pre-scaled iterate), base likewise or None with beta == 0; a, b: fp32
+    [n_rows] or None (= 1); out / yout: fp32 [n_rows, >= C] views with 16-byte rows, one of them may be None; `plan`:
+    infer.plan(adj); partials: fp32 [n_slices, gsage_segment_reduce_ldp(C)] scratch (allocated when None).
+    CUDA: gsage_propagate, two launches, no synchronisation, recordable in a command list.  CPU: the same definition in
+    torch (host mode).  -> (out, yout)."""
+    C = int(C)
+    if out is None and yout is None:
+        raise ValueError("propagate_step: out and yout are both None")
+    if base is None and beta != 0:
+        raise ValueError("propagate_step: base is None and beta is not 0")
+    if not y.is_cuda:
+        if not 1 <= C <= PROP_C_MAX:
+            raise ValueError("propagate_step: the width must lie in [1, %d], not %d" % (PROP_C_MAX, C))
+        return _propagate_step_host(adj, y, base, a, b, float(alpha), float(beta), float(lo), float(hi), C, out, yout)
+    n = int(adj.n_rows)
+    for t in (y, base, out, yout):
+        assert t is None or (t.dtype == torch.float32 and t.stride(1) == 1 and int(t.shape[0]) >= n)
+    lib = nat.lib()
+    ldp = int(lib.gsage_segment_reduce_ldp(C))
+    if partials is None and plan["n_slices"]:
+        partials = torch.empty(plan["n_slices"], ldp, dtype=torch.float32, device=y.device)
+
+    def ld(t):
+        return 0 if t is None else t.stride(0)
+    nat.check(lib.gsage_propagate(
+        _ptr(y), ld(y), _ptr(base), ld(base), _ptr(a), _ptr(b), float(alpha), float(beta), float(lo), float(hi), C,
+        _ptr(adj.rowptr), _ptr(adj.col), n, _ptr(plan["order"]), plan["n_short"], _ptr(plan["slices"]), plan["n_slices"],
+        _ptr(plan["long_rows"]), plan["n_long"], plan["slice_len"], _ptr(partials), ldp if partials is None else
+        partials.stride(0), _ptr(out), ld(out), _ptr(yout), ld(yout), _ptr(adj.err_flag), _stream()), "propagate")
+    return out, yout

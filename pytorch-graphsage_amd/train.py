@@ -70,6 +70,19 @@ Retrieval over the embeddings (infer.nearest, opt-in):
   --probe-iters N         Adam iterations (default 100)     --probe-lr F   learning rate (default 0.1)
   --probe-l2 F            Adam's L2 term (default 0).  The defaults reach the toy results of the tests; nobody has
                           tuned them on a real graph.
+  --correct-smooth        after training: Correct and Smooth (gs.correct_smooth_eval, propagate.py) -- the logits of EVERY row by
+                          full-neighbourhood inference over the evaluation adjacency, the train fold's residual errors
+                          propagated over the graph and added back, the result smoothed with the train labels held
+                          (each iteration one fused step of csrc/gsage_propagate.hip); one line {"correct_smooth":
+                          {"fold": "val", "task", "base", "corrected", "smoothed"}}, each score {"micro", "macro"}, is
+                          printed, with --show-test a second one for the test fold.  "base" is what
+                          --full-neighbour-eval prints for the fold.  Supervised classification / multilabel problems
+                          with a sparse unweighted adjacency, one process; --unsupervised is refused (no logits).
+  --cs-iters 50,50        correct, smooth iterations      --cs-alpha 0.8,0.8   their alpha
+  --cs-no-autoscale       hold the labelled residuals instead of rescaling the propagated ones
+  --label-prop            with --correct-smooth: also {"label_prop": {"fold", "task", "micro", "macro"}}, plain label
+                          propagation from the train labels (--cs-iters' / --cs-alpha's second values).  The defaults are
+                          the common published ones; nobody has tuned them on a graph of this project.
   --link-eval-edges M     at most M edges per fold (default 100000), a subsample seeded by --seed when there are more
   --link-eval-ks 1,10,50  the k of hits@k
   --neighbours-k K        how many (default 10, at most 128)
@@ -257,6 +270,38 @@ def probe_eval(problem, args, emb):
         sys.stdout.flush()
 
 
+def cs_settings(args):
+    """(iters, alpha) of --cs-iters / --cs-alpha, or SystemExit with a sentence."""
+    try:
+        iters = tuple(int(v) for v in args.cs_iters.split(','))
+        alpha = tuple(float(v) for v in args.cs_alpha.split(','))
+        ok = len(iters) == 2 and len(alpha) == 2 and all(v >= 0 for v in iters) and all(0.0 <= v <= 1.0 for v in alpha)
+    except ValueError:
+        ok = False
+    if not ok:
+        raise SystemExit('gsage: --cs-iters must be two counts >= 0 (correct,smooth) and --cs-alpha two values in [0, 1]')
+    return iters, alpha
+
+
+def correct_smooth(model, problem, args):
+    """--correct-smooth (and --label-prop) after training: one JSON line per fold (gs.correct_smooth_eval)."""
+    iters, alpha = cs_settings(args)
+    folds = ['val', 'test'] if args.show_test else ['val']
+    try:
+        res = gs.correct_smooth_eval(model, problem, iters=iters, alpha=alpha, autoscale=not args.cs_no_autoscale,
+                                     label_prop=args.label_prop, folds=folds)
+    except (ValueError, IndexError) as e:
+        raise SystemExit('gsage: --correct-smooth: %s' % e)
+    for fold in folds:
+        f1 = res[fold] or {}
+        print(dumps({"correct_smooth": {"fold": fold, "task": res["task"], "base": f1.get("base"),
+                                        "corrected": f1.get("corrected"), "smoothed": f1.get("smoothed")}}))
+        if args.label_prop:
+            lp = f1.get("label_prop") or {"micro": None, "macro": None}
+            print(dumps({"label_prop": {"fold": fold, "task": res["task"], "micro": lp["micro"], "macro": lp["macro"]}}))
+        sys.stdout.flush()
+
+
 def export(model, problem, args):
     """--save-embeddings, --save-neighbours, --link-eval and --probe after training: one embedding pass serves all."""
     emb = None
@@ -408,6 +453,11 @@ def parse_args(argv=None):
     parser.add_argument('--probe-iters', type=int, default=100)
     parser.add_argument('--probe-lr', type=float, default=0.1)
     parser.add_argument('--probe-l2', type=float, default=0.0)
+    parser.add_argument('--correct-smooth', action="store_true")
+    parser.add_argument('--cs-iters', type=str, default='50,50')
+    parser.add_argument('--cs-alpha', type=str, default='0.8,0.8')
+    parser.add_argument('--cs-no-autoscale', action="store_true")
+    parser.add_argument('--label-prop', action="store_true")
     parser.add_argument('--unsupervised', action="store_true")
     parser.add_argument('--walk-len', type=int, default=5)
     parser.add_argument('--n-negatives', type=int, default=20)
@@ -520,6 +570,14 @@ def main(argv=None, problem=None):
             raise SystemExit('gsage: --link-eval: data-parallel launches are not supported (run a single process)')
     if args.probe and (args.probe_iters < 1 or not args.probe_lr > 0 or args.probe_l2 < 0):
         raise SystemExit('gsage: --probe-iters must be >= 1, --probe-lr > 0 and --probe-l2 >= 0')
+    if args.label_prop and not args.correct_smooth:
+        raise SystemExit('gsage: --label-prop goes with --correct-smooth')
+    if args.correct_smooth:
+        cs_settings(args)
+        if args.unsupervised:
+            raise SystemExit('gsage: --correct-smooth: --unsupervised trains no classifier; there are no logits to correct')
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("GSAGE_FORCE_DDP", "0") == "1":
+            raise SystemExit('gsage: --correct-smooth: data-parallel launches are not supported (run a single process)')
     set_seeds(args.seed)
     gs.ops.set_compute_dtype(args.precision)
     gs.nn_modules.SparseUniformNeighborSampler.rng_default = args.rng
@@ -554,6 +612,16 @@ def main(argv=None, problem=None):
         raise SystemExit('gsage: --link-eval: a dense problem file holds neighbour samples, not edges to hold out')
     if args.importance_walks:
         importance_graphs(args, problem)
+    if args.correct_smooth:
+        if problem.task not in ('classification', 'multilabel_classification'):
+            raise SystemExit('gsage: --correct-smooth: labels are propagated as class scores; this problem\'s task is %s'
+                             % problem.task)
+        if not gs.problem._is_sparse(problem.adj):
+            raise SystemExit('gsage: --correct-smooth: a dense problem file holds neighbour samples, not the edges to '
+                             'propagate over')
+        if isinstance(problem.adj, gs.store.WeightedAdj):
+            raise SystemExit('gsage: --correct-smooth: a weighted adjacency is not supported (edge weights are out of '
+                             'scope; importance neighbourhoods included)')
     weighted = args.sampler_class == 'sparse_weighted_neighbor_sampler'
     if weighted:
         if not (isinstance(problem.adj, gs.store.WeightedAdj) and isinstance(problem.train_adj, gs.store.WeightedAdj)):
@@ -591,11 +659,13 @@ def main(argv=None, problem=None):
                 raise SystemExit('gsage: --save-embeddings / --save-neighbours / --link-eval / --probe: %s' % e)
         set_seeds(args.seed ** 2)
         return train_unsupervised(args, problem, model)
-    if args.full_neighbour_eval or args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
+    if args.full_neighbour_eval or args.save_embeddings or args.save_neighbours or args.link_eval or args.probe or \
+            args.correct_smooth:
         try:
             gs.infer.check_supported(model, model.val_sampler.csr('cpu') if weighted else None)
         except ValueError as e:
-            raise SystemExit('gsage: --full-neighbour-eval / --save-embeddings / --save-neighbours / --link-eval / --probe: %s' % e)
+            flags = '--full-neighbour-eval / --save-embeddings / --save-neighbours / --link-eval / --probe'
+            raise SystemExit('gsage: %s%s: %s' % (flags, ' / --correct-smooth' if args.correct_smooth else '', e))
     evaluate_fn = (lambda mode: full_neighbour_evaluate(model, problem, mode=mode, closure=args.eval_closure)) \
         if args.full_neighbour_eval else \
         (lambda mode: evaluate(model, problem, mode=mode))
@@ -637,6 +707,8 @@ def main(argv=None, problem=None):
             print(dumps({"test_f1": evaluate_fn('test')}))
         if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
             export(model, problem, args)
+        if args.correct_smooth:
+            correct_smooth(model, problem, args)
     if ddp is not None:
         ddp.close()
 
@@ -912,6 +984,8 @@ def train_fused(args, problem, model, ddp, start_time, cls):
             print(dumps({"test_f1": test_metric}))
         if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
             export(model, problem, args)
+        if args.correct_smooth:
+            correct_smooth(model, problem, args)
     if ddp is not None:
         ddp.close()
     return step
