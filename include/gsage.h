@@ -1621,6 +1621,68 @@ int gsage_propagate(const float *y, int64_t ldy, const float *base, int64_t ldb,
                     const int64_t *long_rows, int64_t n_long, int32_t slice_len, float *partials, int64_t ldp,
                     float *out, int64_t ldo, float *yout, int64_t ldyo, int32_t *err_flag, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K-means over embeddings (csrc/gsage_kmeans.hip): one assignment-and-accumulate pass of Lloyd's algorithm over
+ * selected rows of a table, and the centroid update (ops.kmeans_pass / ops.kmeans_update / infer.kmeans).  Additive;
+ * the ABI version is unchanged.
+ *
+ * gsage_kmeans_pass.  Given a table X [N, ldx], ids int64 [n], fp32 centroids Cn [K, D] (dense), bias fp32 [K] and
+ * k_live in [1, K]:
+ *     s[i, c]  = sum_d X[ids[i], d] * C~[c, d] + bias[c]                for c < k_live
+ *     a[i]     = the c < k_live with the largest s[i, c]; among equal scores the SMALLEST c
+ *     d2[i]    = max(0, |x_i|^2 - 2 s[i, a[i]])
+ *     sums[c]  = sum over {i : a[i] == c} of X[ids[i], :]  [K, D],     counts[c] = |{i : a[i] == c}|
+ *     inertia  = sum_i d2[i],     changed = |{i : labels_in[i] != a[i]}|   (0 if labels_in == NULL)
+ * With bias[c] = -1/2 |C~[c]|^2 (gsage_kmeans_update writes it) a[i] is the nearest centroid and d2 the squared
+ * distance to it.  Compute mode = the table's dtype: GSAGE_BF16 rows meet C~ = Cn rounded to bf16 (RNE) on
+ * mfma_f32_32x32x16_bf16; GSAGE_F32 rows meet C~ = Cn on the exact mfma_f32_32x32x2f32.  A score is ONE accumulator
+ * chain over d in ascending 16-byte steps, the same in every launch: a[i] does not depend on splits.  |x_i|^2 is fp32
+ * (eight partial sums per row over interleaved 16-byte chunks, then a butterfly).  Scores, the arg-max and its one-hot
+ * never leave the registers (no n x K buffer); the one-hot is the second product's operand as it stands (0 and 1 are
+ * exact in bf16), so sums are fp32 sums of the table's values.
+ *
+ * Outputs:
+ *     partial     fp32 [S][K*D + K + 2]: one row [sums | counts | inertia | changed] per workgroup (a contiguous
+ *                 range of 32-row tiles), unscaled; counts and changed as fp32 integers.  S = splits, or for
+ *                 splits = 0 the count the library chooses: min(ceil(n / 32), 256).  A range that holds no tile
+ *                 (splits > tiles) writes zeros.  Clusters >= k_live get zeros.  NULL: labels / dist only (the second
+ *                 product is skipped) -- then labels_out or dist_out must be given.
+ *     labels_out  int32 [n] = a (may be NULL);   dist_out  fp32 [n] = d2 (may be NULL).
+ *     labels_in   int32 [n] (may be NULL) must not alias labels_out.
+ * No atomics: for fixed (n, K, D, splits) every sum has one order and the result is bit-identical from call to call;
+ * different splits give the same labels, counts and changed, and sums / inertia that agree to fp32 round-off.
+ *
+ * gsage_kmeans_update (one launch; one workgroup of 256 threads per cluster).  With sum_c / count_c the sums over the
+ * S partial rows in buffer order (counts and changed summed as integers):
+ *     count_c > 0:  Cn[c] = sum_c / (float)count_c;  spherical = 1: then Cn[c] /= |Cn[c]| (left alone if the norm is 0)
+ *     count_c == 0: Cn[c] is KEPT
+ *     bias[c] = -1/2 sum_d C~[c, d]^2 (C~: Cn[c] rounded as the mode `dtype` sees it);  spherical = 1: bias[c] = 0
+ *     slot = *index (DEVICE int64, read when the launch runs):  if 0 <= slot < capacity:  inertia_hist[slot] = inertia
+ *     (fp32, the S slots added in buffer order), changed_hist[slot] = changed (int64), empty_hist[slot] = the number of
+ *     c with count_c == 0 (int32);  then *index = slot + 1 -- a replayed command list fills the histories.
+ * The order of every sum over d: thread t adds d = t, t + 256, t + 512, t + 768 in this order (fmaf), the 256 partial
+ * sums are folded by halving (t += t + 128, then t + 64, .. t + 1).
+ * S = 0: only bias is computed, from the given Cn; partial, the histories and index may be NULL and are not touched.
+ *
+ * Limits (GSAGE_EINVAL, the message names the argument; checked on the host before anything touches the GPU):
+ * 1 <= K <= 128; 1 <= D <= 1024; 1 <= n < 2^31; N >= 1; ldx >= D (elements; nothing past a row's D columns is read);
+ * 1 <= k_live <= K; 0 <= splits <= 1024 (update: 0 <= S <= 1024); with partial != NULL a workgroup's range must hold
+ * fewer than 2^24 rows (ceil(ceil(n / 32) / S) * 32 < 2^24: its counts are fp32); capacity >= 1 for S > 0.  ids must
+ * lie in [0, N) (the callers check once; an id outside reads as a zero row).  One launch each; recordable in a command
+ * list.
+ *
+ * gsage_kmeans_pass_scratch (HOST arithmetic, no GPU): the number of FLOATS of `partial` for (n, K, D, splits), -1 for
+ * arguments outside the limits; divided by K*D + K + 2 it is S.
+ * ---------------------------------------------------------------------------------------- */
+int64_t gsage_kmeans_pass_scratch(int64_t n, int32_t K, int32_t D, int32_t splits);
+int gsage_kmeans_pass(const void *table, int dtype, int64_t ldx, int64_t N, const int64_t *ids, int64_t n,
+                      const float *Cn, const float *bias, int32_t K, int32_t D, int32_t k_live,
+                      const int32_t *labels_in, int32_t splits, float *partial, int32_t *labels_out, float *dist_out,
+                      void *stream);
+int gsage_kmeans_update(const float *partial, int32_t S, int32_t K, int32_t D, int dtype, int spherical, float *Cn,
+                        float *bias, float *inertia_hist, int64_t *changed_hist, int32_t *empty_hist, int64_t *index,
+                        int64_t capacity, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

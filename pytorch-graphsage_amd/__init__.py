@@ -15,7 +15,9 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
                               link_metrics / held_out_edges: the exact (filtered) rank of an edge's other endpoint
                               among all rows, MRR and hits@k (ops.rank_ip, csrc/gsage_rank.hip); infer.linear_probe /
                               probe_eval: a linear classifier fitted on the frozen embeddings, micro / macro F1 of
-                              the val / test folds (ops.probe_pass, csrc/gsage_probe.hip)
+                              the val / test folds (ops.probe_pass, csrc/gsage_probe.hip); infer.kmeans /
+                              cluster_metrics / cluster_eval: Lloyd's k-means on the frozen embeddings, NMI and
+                              purity against the labels (ops.kmeans_pass / kmeans_update, csrc/gsage_kmeans.hip)
     propagate.py              propagation over the graph after the encoder has run: gs.propagate (one fused step of
                               csrc/gsage_propagate.hip per iteration), gs.label_propagation, gs.correct_and_smooth,
                               gs.correct_smooth_eval
@@ -37,8 +39,8 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
 """
 from . import _native, dist, engine, helpers, infer, nn_modules, ops, optim, problem, store        # noqa: F401
 from .helpers import set_seeds, to_numpy                            # noqa: F401
-from .infer import (LinearProbe, embeddings, full_neighbour, held_out_edges, linear_probe, link_metrics,   # noqa: F401
-                    link_rank, nearest, probe_eval, query)
+from .infer import (KMeans, LinearProbe, cluster_eval, cluster_metrics, embeddings, full_neighbour,   # noqa: F401
+                    held_out_edges, kmeans, linear_probe, link_metrics, link_rank, nearest, probe_eval, query)
 from .lr import LRSchedule                                          # noqa: F401
 from .models import GSSupervised, GSUnsupervised                                # noqa: F401
 from .nn_modules import aggregator_lookup, find_sampler, prep_lookup, sampler_extensions, sampler_lookup   # noqa: F401
@@ -50,5 +52,5 @@ from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef, WeightedAdj, impor
 __all__ = ["GSSupervised", "GSUnsupervised", "NodeProblem", "aggregator_lookup", "prep_lookup", "sampler_lookup",
            "set_seeds", "to_numpy", "LRSchedule", "FeatureStore", "DeviceCSR", "RowRef", "ops", "full_neighbour",
            "embeddings", "query", "nearest", "link_rank", "link_metrics", "held_out_edges", "LinearProbe", "linear_probe",
-           "probe_eval", "WeightedAdj", "find_sampler", "sampler_extensions", "importance_adj",
+           "probe_eval", "KMeans", "kmeans", "cluster_metrics", "cluster_eval", "WeightedAdj", "find_sampler", "sampler_extensions", "importance_adj",
            "propagate", "label_propagation", "correct_and_smooth", "correct_smooth_eval"]

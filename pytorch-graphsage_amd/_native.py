@@ -221,6 +221,10 @@ SIGNATURES = {
     "gsage_probe_loss_index_next": (_int, [_vp]),
     "gsage_probe_pass": (_int, [_vp, _int, _i64, _i64, _vp, _i64, _vp, _int, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
                                 _vp]),
+    "gsage_kmeans_pass_scratch": (_i64, [_i64, _i32, _i32, _i32]),
+    "gsage_kmeans_pass": (_int, [_vp, _int, _i64, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp,
+                                 _vp]),
+    "gsage_kmeans_update": (_int, [_vp, _i32, _i32, _i32, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gsage_propagate_scales": (_int, [_vp, _i64, _int, _vp, _vp, _vp]),
     "gsage_propagate": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _i64, _vp, _vp, _i64, _vp, _i64,
                                _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),

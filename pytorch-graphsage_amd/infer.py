@@ -932,3 +932,244 @@ def probe_eval(emb, problem, iters=100, lr=0.1, weight_decay=0.0):
     hist = probe.loss_history.cpu()
     out["loss_first"], out["loss_last"] = float(hist[0]), float(hist[-1])
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# k-means over the exported embeddings
+# --------------------------------------------------------------------------------------------
+KMEANS_CHUNK = 10                                  # iterations between two readbacks of `changed`
+
+
+class KMeans(object):
+    """A k-means fit on frozen embeddings (kmeans): centroids fp32 [k, D]; labels int32 [n], in the order of `nodes`,
+    and inertia (fp32 scalar tensor) as the LAST assignment pass saw them -- the centroids are the means of exactly
+    these labels; inertia_history fp32 [n_iter] and changed_history int64 [n_iter], one slot per iteration; n_iter."""
+
+    def __init__(self, centroids, bias, labels, inertia_history, changed_history, n_iter, spherical, seed):
+        self.centroids, self.bias, self.labels = centroids, bias, labels
+        self.inertia_history, self.changed_history = inertia_history, changed_history
+        self.inertia = inertia_history[n_iter - 1]
+        self.n_iter, self.spherical, self.seed = int(n_iter), bool(spherical), seed
+
+    def predict(self, emb, nodes=None):
+        """The nearest centroid of emb[nodes] (every row when nodes is None), int32 [n]: a pass that writes labels only."""
+        N = int(emb.shape[0])
+        ids = torch.arange(N, device=emb.device) if nodes is None else _pair_ids(nodes, emb.device, "KMeans.predict", "node", N)
+        return ops.kmeans_pass(emb, ids, self.centroids, self.bias, accumulate=False)[0]
+
+
+def _kmeans_init(emb, ids, k, init, seed, spherical):
+    """-> (centroids fp32 [k, D], bias fp32 [k]) on emb's device; no host synchronisation for "++"."""
+    dev, f32 = emb.device, torch.float32
+    n, D = int(ids.shape[0]), int(emb.shape[1])
+    bias = torch.zeros(k, dtype=f32, device=dev)
+    if torch.is_tensor(init):
+        if init.dim() != 2 or tuple(init.shape) != (k, D) or not init.is_floating_point():
+            raise ValueError("kmeans: init as a tensor must be float [%d, %d], not %s" % (k, D, tuple(init.shape)))
+        cen = init.detach().to(dev).float().contiguous().clone()
+    elif init == "random":
+        g = torch.Generator().manual_seed(int(seed))
+        uniq = torch.unique(ids)
+        cen = emb[uniq[torch.randperm(int(uniq.shape[0]), generator=g)[:k].to(dev)]].float().contiguous()
+    elif init == "++":
+        # k-means++ (Arthur & Vassilvitskii 2007): the first centre a uniform row, centre j a row drawn in proportion to
+        # the squared distance to the nearest of the j centres so far -- a pass with k_live = j that writes dist only
+        g = torch.Generator().manual_seed(int(seed))
+        cen = torch.zeros(k, D, dtype=f32, device=dev)
+        first = torch.randint(n, (1,), generator=g).to(dev)
+        cen[0] = emb[ids[first]].float()[0]
+        ops.kmeans_update(cen, bias)
+        for j in range(1, k):
+            _, dist = ops.kmeans_pass(emb, ids, cen, bias, k_live=j, want_dist=True, accumulate=False)
+            cs = torch.cumsum(dist.double(), dim=0)
+            u = torch.rand(1, generator=g, dtype=torch.float64).to(dev)
+            at = torch.searchsorted(cs, u * cs[-1], right=True).clamp_(max=n - 1)
+            cen[j] = emb[ids[at]].float()[0]
+            ops.kmeans_update(cen, bias)
+    else:
+        raise ValueError('kmeans: init must be "++", "random" or a [k, D] tensor, not %r' % (init,))
+    if spherical:
+        cen = F.normalize(cen, dim=1).contiguous()
+    ops.kmeans_update(cen, bias, spherical=spherical)
+    return cen, bias
+
+
+class KMeansIteration(object):
+    """One Lloyd iteration on the device -- gsage_kmeans_pass, gsage_kmeans_update: two launches -- recorded once as a
+    command list on two ping-pong label buffers (iteration t reads labels[t % 2] and writes labels[(t + 1) % 2]);
+    replay(k) issues k iterations without a host synchronisation.  Iteration t (counted on the device) writes
+    inertia_history[t], changed_history[t] and empty_history[t], t < capacity."""
+
+    def __init__(self, emb, ids, centroids, bias, capacity, spherical):
+        lib = nat.lib()
+        dev, f32 = emb.device, torch.float32
+        K, D = int(centroids.shape[0]), int(centroids.shape[1])
+        self.E = E = ops.probe_operand(emb, D)
+        self.ids, self.centroids, self.bias = ids, centroids, bias
+        n = int(ids.shape[0])
+        floats, S = ops.kmeans_scratch(n, K, D, 0)
+        self.capacity = int(capacity)
+        self.partial = torch.empty(floats, dtype=f32, device=dev)
+        self.labels = [torch.full((n,), -1, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)]
+        self.inertia_history = torch.zeros(self.capacity, dtype=f32, device=dev)
+        self.changed_history = torch.zeros(self.capacity, dtype=torch.int64, device=dev)
+        self.empty_history = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
+        self.index = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.issued = 0
+        stream = ops._stream()
+        self.cl = []
+        for a in (0, 1):
+            with nat.CommandList.record() as cl:
+                nat.check(lib.gsage_kmeans_pass(ops._ptr(E), ops._code(E.dtype), E.stride(0), int(E.shape[0]), ops._ptr(ids),
+                                                n, centroids.data_ptr(), bias.data_ptr(), K, D, K,
+                                                self.labels[a].data_ptr(), 0, self.partial.data_ptr(),
+                                                self.labels[1 - a].data_ptr(), None, stream), "kmeans_pass")
+                nat.check(lib.gsage_kmeans_update(self.partial.data_ptr(), S, K, D, ops._code(E.dtype), int(bool(spherical)),
+                                                  centroids.data_ptr(), bias.data_ptr(), self.inertia_history.data_ptr(),
+                                                  self.changed_history.data_ptr(), self.empty_history.data_ptr(),
+                                                  self.index.data_ptr(), self.capacity, stream), "kmeans_update")
+            self.cl.append(cl)
+
+    def replay(self, k=1):
+        if self.issued + k > self.capacity:
+            raise ValueError("KMeansIteration: %d iterations asked of a history of %d" % (self.issued + k, self.capacity))
+        stream = ops._stream()
+        for _ in range(k):
+            self.cl[self.issued % 2].replay(stream)
+            self.issued += 1
+
+    def current_labels(self):
+        return self.labels[self.issued % 2]
+
+
+def _kmeans_fit(emb, ids, k, iters, init, seed, spherical):
+    cen, bias = _kmeans_init(emb, ids, k, init, seed, spherical)
+    n = int(ids.shape[0])
+    if emb.is_cuda:
+        fit = KMeansIteration(emb, ids, cen, bias, iters, spherical)
+        while fit.issued < iters:
+            fit.replay(min(KMEANS_CHUNK, iters - fit.issued))
+            if int(fit.changed_history[fit.issued - 1]) == 0:        # the chunk's one 8-byte readback
+                break
+        done = fit.issued
+        km = KMeans(cen, bias, fit.current_labels(), fit.inertia_history[:done], fit.changed_history[:done], done,
+                    spherical, seed)
+        km.empty_history = fit.empty_history[:done]
+        km._fit = fit                                  # the recorded lists and their buffers
+        return km
+    # host mode: the same loop over the float64 definition
+    hist = (torch.zeros(iters), torch.zeros(iters, dtype=torch.int64), torch.zeros(iters, dtype=torch.int32),
+            torch.zeros(1, dtype=torch.int64))
+    labels = torch.full((n,), -1, dtype=torch.int32)
+    done = 0
+    while done < iters:
+        for _ in range(min(KMEANS_CHUNK, iters - done)):
+            res = ops.kmeans_pass(emb, ids, cen, bias, labels_in=labels)
+            labels = res[4]
+            ops.kmeans_update(cen, bias, res.partial, spherical=spherical, history=hist)
+            done += 1
+        if int(hist[1][done - 1]) == 0:
+            break
+    km = KMeans(cen, bias, labels, hist[0][:done], hist[1][:done], done, spherical, seed)
+    km.empty_history = hist[2][:done]
+    return km
+
+
+def kmeans(emb, k, nodes=None, iters=50, init="++", n_init=1, seed=0, spherical=False):
+    """Lloyd's k-means on the rows `nodes` (default: every row) of the frozen embeddings `emb` [N, D] -> KMeans.
+
+    init: "++" (k-means++ on the device, k set-up passes, draws from a CPU torch.Generator seeded with `seed`), "random"
+    (k distinct rows of `nodes`) or a [k, D] tensor.  n_init > 1 repeats the fit with seeds seed, seed + 1, .. and keeps
+    the lowest final inertia (the lowest seed among equals).  spherical: centroids (the initial ones too) are scaled to
+    unit length and the assignment is by inner product.  An empty cluster keeps its centroid.
+    On CUDA one iteration is two launches (csrc/gsage_kmeans.hip: pass, update), recorded once as a command list and
+    replayed in chunks of 10 iterations; after a chunk ONE 8-byte readback of `changed` ends the loop when no label
+    moved -- from then on an iteration reproduces itself bit for bit, so stopping early changes nothing.  CPU tensors:
+    the same loop over ops.kmeans_pass's host definition.  Deterministic: two fits on the same inputs are bit-identical.
+    Refused with a sentence: k > 128, D > 1024, k larger than the number of distinct ids in `nodes`, a table with
+    non-finite values in those rows, ids out of range, iters < 1."""
+    if not torch.is_tensor(emb) or emb.dim() != 2 or not emb.is_floating_point():
+        raise ValueError("kmeans: emb must be a [N, D] float tensor")
+    k, iters, n_init = int(k), int(iters), int(n_init)
+    if iters < 1:
+        raise ValueError("kmeans: iters must be at least 1, not %d" % iters)
+    if n_init < 1:
+        raise ValueError("kmeans: n_init must be at least 1, not %d" % n_init)
+    N, D = int(emb.shape[0]), int(emb.shape[1])
+    ids = ops.kmeans_check(emb, torch.arange(N) if nodes is None else nodes, k, D, who="kmeans")
+    if int(ids.min()) < 0 or int(ids.max()) >= N:
+        raise IndexError("kmeans: node id out of range of the %d embedding rows" % N)
+    distinct = int(torch.unique(ids).shape[0])
+    if k > distinct:
+        raise ValueError("kmeans: k = %d clusters asked of %d distinct rows" % (k, distinct))
+    if not bool(torch.isfinite(emb[ids]).all()):
+        raise ValueError("kmeans: the embeddings of the rows to cluster hold non-finite values")
+    emb = ops.probe_operand(emb, D)                    # rounded to the compute mode once, not once per fit
+    best = _kmeans_fit(emb, ids, k, iters, init, int(seed), spherical)
+    for r in range(1, n_init):
+        fit = _kmeans_fit(emb, ids, k, iters, init, int(seed) + r, spherical)
+        if float(fit.inertia) < float(best.inertia):
+            best = fit
+    return best
+
+
+def cluster_metrics(labels, targets, n_classes=None):
+    """Agreement of a clustering with class labels -> {"n", "clusters", "nmi", "purity"}: clusters = the non-empty
+    ones; NMI = I(U; V) / ((H(U) + H(V)) / 2) in nats (1.0 when both partitions are trivial); purity = (1/n) sum_k max_c
+    |cluster k and class c|.  The K x C contingency table is one torch.bincount on the labels' device, evaluated in
+    float64 on the host.  A metric, not a hot path.  Multilabel and regression targets are refused."""
+    labels, targets = torch.as_tensor(labels), torch.as_tensor(targets)
+    if targets.is_floating_point() or targets.dtype == torch.bool:
+        raise ValueError("cluster_metrics: targets must be integer class ids (no regression or multilabel targets), not %s"
+                         % targets.dtype)
+    if targets.dim() > 2 or (targets.dim() == 2 and int(targets.shape[1]) != 1):
+        raise ValueError("cluster_metrics: targets must be one class id per row (no multilabel targets), not shape %s"
+                         % (tuple(targets.shape),))
+    if labels.is_floating_point() or labels.dim() != 1 or labels.numel() != targets.numel() or labels.numel() < 1:
+        raise ValueError("cluster_metrics: labels must be integer [n] with one target each")
+    u, v = labels.long(), targets.to(labels.device).long().view(-1)
+    if int(u.min()) < 0 or int(v.min()) < 0:
+        raise ValueError("cluster_metrics: labels and targets must be non-negative")
+    C = int(v.max()) + 1 if n_classes is None else int(n_classes)
+    if int(v.max()) >= C:
+        raise ValueError("cluster_metrics: class id out of range [0, %d)" % C)
+    K = int(u.max()) + 1
+    T = torch.bincount(u * C + v, minlength=K * C).view(K, C).cpu().double().numpy()
+    n = T.sum()
+    pu, pv = T.sum(axis=1) / n, T.sum(axis=0) / n
+
+    def H(p):
+        p = p[p > 0]
+        return float(-(p * np.log(p)).sum())
+    nz = T > 0
+    mi = float((T[nz] / n * (np.log(T[nz] / n) - np.log(np.outer(pu, pv)[nz]))).sum())
+    hu, hv = H(pu), H(pv)
+    if hu + hv == 0.0 or (int(nz.sum(axis=1).max()) == 1 and int(nz.sum(axis=0).max()) == 1):
+        nmi = 1.0                                      # the same partition under other names: exactly 1, no round-off
+    else:
+        nmi = max(0.0, mi) / ((hu + hv) / 2.0)
+    return {"n": int(n), "clusters": int((pu > 0).sum()), "nmi": min(1.0, nmi), "purity": float(T.max(axis=1).sum() / n)}
+
+
+def cluster_eval(emb, problem, k=None, iters=50, init="++", n_init=1, seed=0, spherical=False):
+    """k-means on the embeddings of every node of the problem's three folds, scored on the val and test folds ->
+    {"k", "iters", "inertia", "val": cluster_metrics or None, "test": ..., "nodes", "labels", "centroids"}; k defaults
+    to problem.n_classes.  A problem without class labels (multilabel, regression) is clustered all the same and scores
+    None."""
+    dev = emb.device
+    folds = {m: np.asarray(problem.nodes[m], dtype=np.int64).reshape(-1) for m in ("train", "val", "test")}
+    nodes = np.concatenate([folds["train"], folds["val"], folds["test"]])
+    k = int(problem.n_classes if k is None else k)
+    km = kmeans(emb, k, nodes=torch.from_numpy(nodes).to(dev), iters=iters, init=init, n_init=n_init, seed=seed,
+                spherical=spherical)
+    out = {"k": k, "iters": km.n_iter, "inertia": float(km.inertia), "nodes": nodes, "labels": km.labels,
+           "centroids": km.centroids}
+    at = len(folds["train"])
+    for name in ("val", "test"):
+        m = len(folds[name])
+        out[name] = None
+        if problem.task == "classification" and m:
+            y = torch.as_tensor(np.asarray(problem.targets[folds[name]])).long().view(-1)
+            out[name] = cluster_metrics(km.labels[at:at + m], y, n_classes=int(problem.n_classes))
+        at += m
+    return out

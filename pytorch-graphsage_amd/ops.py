@@ -2174,6 +2174,196 @@ def probe_pass(table, ids, targets, W, b, task, splits=0):
 
 
 # =============================================================================================
+# K-means over embeddings: the assignment-and-accumulate pass and the centroid update (csrc/gsage_kmeans.hip)
+# =============================================================================================
+KMEANS_K_MAX, KMEANS_D_MAX = 128, 1024
+
+
+class KMeansPass(tuple):
+    """What kmeans_pass returns: (sums, counts, inertia, changed, labels[, dist]), and in `.partial` the [S, K D + K + 2]
+    rows [sums | counts | inertia | changed] they were summed from -- what kmeans_update takes."""
+    partial = None
+
+
+def kmeans_check(table, ids, K, D, who="kmeans_pass"):
+    """Shape and dtype checks shared by kmeans_pass and infer.kmeans -> ids int64 [n] on the table's device."""
+    if not torch.is_tensor(table) or table.dim() != 2 or not table.is_floating_point():
+        raise ValueError("%s: the table must be a [N, D] float tensor" % who)
+    if int(table.shape[1]) != D:
+        raise ValueError("%s: the table has %d columns, the centroids D = %d" % (who, int(table.shape[1]), D))
+    if not 1 <= K <= KMEANS_K_MAX:
+        raise ValueError("%s: the number of clusters must be in [1, %d], not %d (one workgroup holds every cluster of a row)"
+                         % (who, KMEANS_K_MAX, K))
+    if not 1 <= D <= KMEANS_D_MAX:
+        raise ValueError("%s: D must be in [1, %d], not %d" % (who, KMEANS_D_MAX, D))
+    ids = torch.as_tensor(ids)
+    if ids.is_floating_point() or ids.dtype == torch.bool:
+        raise ValueError("%s: node ids must be integers, not %s" % (who, ids.dtype))
+    ids = ids.to(table.device).long().contiguous().view(-1)
+    if int(ids.shape[0]) < 1:
+        raise ValueError("%s: no rows to cluster" % who)
+    return ids
+
+
+def kmeans_scratch(n, K, D, splits=0):
+    """(floats of gsage_kmeans_pass's partial buffer, its rows S) -- host arithmetic."""
+    floats = int(nat.lib().gsage_kmeans_pass_scratch(int(n), int(K), int(D), int(splits)))
+    if floats < 0:
+        raise ValueError("kmeans_pass: n = %d, K = %d, D = %d, splits = %d are outside the kernel's limits (K <= %d, "
+                         "D <= %d, n < 2^31, 0 <= splits <= 1024, fewer than 2^24 rows per split)"
+                         % (n, K, D, splits, KMEANS_K_MAX, KMEANS_D_MAX))
+    return floats, floats // (K * D + K + 2)
+
+
+def _kmeans_centroid_args(centroids, bias, who):
+    if not (torch.is_tensor(centroids) and centroids.dim() == 2 and centroids.dtype == torch.float32
+            and torch.is_tensor(bias) and bias.dtype == torch.float32 and tuple(bias.shape) == (int(centroids.shape[0]),)):
+        raise ValueError("%s: centroids must be fp32 [K, D] and bias fp32 [K]" % who)
+    return int(centroids.shape[0]), int(centroids.shape[1])
+
+
+def _kmeans_pass_host(table, ids, centroids, bias, k_live, labels_in, accumulate, want_dist):
+    """The definition in numpy float64 (host mode): operands rounded as the compute mode sees them."""
+    dt = torch_dtype()
+    K, D = int(centroids.shape[0]), int(centroids.shape[1])
+    N = int(table.shape[0])
+    ok = ((ids >= 0) & (ids < N)).numpy()
+    X = table.detach()[ids.clamp(0, N - 1)].to(dt).double().numpy() * ok[:, None]     # an id outside reads as a zero row
+    Cr = centroids.detach().to(dt).double().numpy()
+    s = X @ Cr[:k_live].T + bias.detach().double().numpy()[:k_live]
+    a = np.argmax(s, axis=1)                                                          # the first of equal scores
+    n = X.shape[0]
+    d2 = np.maximum(0.0, (X * X).sum(axis=1) - 2.0 * s[np.arange(n), a])
+    labels = torch.from_numpy(a.astype(np.int32))
+    dist = torch.from_numpy(d2.astype(np.float32))
+    if not accumulate:
+        return (labels, dist) if want_dist else (labels,)
+    sums = np.zeros((K, D))
+    np.add.at(sums, a, X)
+    counts = np.bincount(a, minlength=K)
+    changed = int((labels_in.numpy() != a).sum()) if labels_in is not None else 0
+    row = np.concatenate([sums.reshape(-1), counts.astype(np.float64), [d2.sum(), float(changed)]])
+    out = (torch.from_numpy(sums.astype(np.float32)), torch.from_numpy(counts.astype(np.int64)),
+           torch.tensor(d2.sum(), dtype=torch.float32), torch.tensor(changed, dtype=torch.int64), labels)
+    res = KMeansPass(out + ((dist,) if want_dist else ()))
+    res.partial = torch.from_numpy(row.astype(np.float32)).view(1, -1)
+    return res
+
+
+def kmeans_pass(table, ids, centroids, bias, k_live=None, labels_in=None, splits=0, want_dist=False, accumulate=True):
+    """One assignment-and-accumulate pass of Lloyd's algorithm over the rows `ids` of `table` ->
+    KMeansPass (sums fp32 [K, D], counts int64 [K], inertia fp32 scalar, changed int64 scalar, labels int32 [n]
+    [, dist fp32 [n]]); include/gsage.h, "K-means over embeddings".  centroids fp32 [K, D], bias fp32 [K] (-1/2 |c|^2:
+    kmeans_update writes it); only the clusters below k_live (default K) compete; labels_in int32 [n]: `changed` counts
+    the rows whose label differs from it.  Operands are taken in ops.config.compute_dtype (fp32 data is rounded to
+    bf16 once in the bf16 mode).  accumulate=False: labels only -> (labels[, dist]).
+
+    CUDA: ONE launch of gsage_kmeans_pass; `splits` = partial rows (0 = chosen by the library); the S rows are in
+    `.partial` and the returned sums are their float64 torch sum.  Labels do not depend on splits; everything is
+    bit-identical from call to call.  CPU: the same definition in numpy float64 (one partial row)."""
+    K, D = _kmeans_centroid_args(centroids, bias, "kmeans_pass")
+    ids = kmeans_check(table, ids, K, D)
+    n = int(ids.shape[0])
+    k_live = K if k_live is None else int(k_live)
+    if not 1 <= k_live <= K:
+        raise ValueError("kmeans_pass: k_live must be in [1, K = %d], not %d" % (K, k_live))
+    if labels_in is not None:
+        if not torch.is_tensor(labels_in) or labels_in.dtype != torch.int32 or tuple(labels_in.shape) != (n,):
+            raise ValueError("kmeans_pass: labels_in must be int32 [%d]" % n)
+        labels_in = labels_in.to(table.device).contiguous()
+    if not table.is_cuda:
+        return _kmeans_pass_host(table, ids, centroids, bias, k_live, labels_in, accumulate, want_dist)
+    dev, f32 = table.device, torch.float32
+    E = probe_operand(table, D)
+    Cc, bc = centroids.detach().contiguous(), bias.detach().contiguous()
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    dist = torch.empty(n, dtype=f32, device=dev) if want_dist else None
+    partial = None
+    if accumulate:
+        floats, S = kmeans_scratch(n, K, D, splits)
+        partial = torch.empty(floats, dtype=f32, device=dev)
+    nat.check(nat.lib().gsage_kmeans_pass(_ptr(E), _code(E.dtype), E.stride(0), int(E.shape[0]), _ptr(ids), n, _ptr(Cc),
+                                          _ptr(bc), K, D, k_live, _ptr(labels_in) if labels_in is not None else None,
+                                          int(splits), _ptr(partial) if accumulate else None, _ptr(labels),
+                                          _ptr(dist) if want_dist else None, _stream()), "kmeans_pass")
+    if not accumulate:
+        return (labels, dist) if want_dist else (labels,)
+    partial = partial.view(S, K * D + K + 2)
+    tot = partial.double().sum(dim=0)
+    out = (tot[:K * D].view(K, D).float(), tot[K * D:K * D + K].round().long(), tot[K * D + K].float(),
+           tot[K * D + K + 1].round().long(), labels)
+    res = KMeansPass(out + ((dist,) if want_dist else ()))
+    res.partial = partial
+    return res
+
+
+def kmeans_update(centroids, bias, partial=None, spherical=False, history=None):
+    """The update step of Lloyd's algorithm, IN PLACE on centroids fp32 [K, D] and bias fp32 [K] (gsage_kmeans_update):
+    with `partial` (kmeans_pass(...).partial, [S, K D + K + 2]) every cluster with count > 0 becomes sums / count (then
+    unit length if spherical), an empty cluster keeps its centroid; bias = -1/2 |c~|^2 in the compute mode's rounding (0
+    if spherical).  partial None: only the bias, from the centroids as they are.
+    history: (inertia fp32 [cap], changed int64 [cap], empty int32 [cap], index int64 [1]) -- slot index[0] is written
+    and index ticked; None: one fresh slot, returned as (inertia, changed, empty); otherwise -> None.
+
+    CUDA: one launch.  CPU: the same definition in numpy float64."""
+    K, D = _kmeans_centroid_args(centroids, bias, "kmeans_update")
+    if not (centroids.is_contiguous() and bias.is_contiguous()):
+        raise ValueError("kmeans_update: centroids and bias are updated in place and must be contiguous")
+    if not 1 <= K <= KMEANS_K_MAX or not 1 <= D <= KMEANS_D_MAX:
+        raise ValueError("kmeans_update: K must be in [1, %d] and D in [1, %d], not %d and %d"
+                         % (KMEANS_K_MAX, KMEANS_D_MAX, K, D))
+    dev = centroids.device
+    dt = torch_dtype()
+    spherical = bool(spherical)
+    S = 0
+    if partial is not None:
+        if not torch.is_tensor(partial) or partial.dtype != torch.float32 or partial.dim() != 2 or \
+                int(partial.shape[1]) != K * D + K + 2 or not partial.is_contiguous() or partial.device != dev:
+            raise ValueError("kmeans_update: partial must be fp32 [S, %d] (kmeans_pass(...).partial)" % (K * D + K + 2))
+        S = int(partial.shape[0])
+        if history is None:
+            history = (torch.zeros(1, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                       torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+            slot = 0
+        else:
+            slot = None
+        ih, chh, eh, index = history
+        cap = int(ih.shape[0])
+        if not (ih.dtype == torch.float32 and chh.dtype == torch.int64 and eh.dtype == torch.int32
+                and index.dtype == torch.int64 and int(chh.shape[0]) == cap and int(eh.shape[0]) == cap and cap >= 1):
+            raise ValueError("kmeans_update: history must be (fp32 [cap], int64 [cap], int32 [cap], int64 [1])")
+    if not centroids.is_cuda:
+        Cd = centroids.double().numpy()
+        if partial is not None:
+            P = partial.double().numpy()
+            counts = np.rint(P[:, K * D:K * D + K]).astype(np.int64).sum(axis=0)
+            sums = P[:, :K * D].sum(axis=0).reshape(K, D)
+            live = counts > 0
+            Cd[live] = sums[live] / counts[live][:, None]
+            if spherical:
+                norm = np.linalg.norm(Cd, axis=1)
+                scale = live & (norm > 0)
+                Cd[scale] /= norm[scale][:, None]
+            centroids[torch.from_numpy(live)] = torch.from_numpy(Cd[live].astype(np.float32))
+            at = int(index[0])
+            if 0 <= at < cap:
+                ih[at] = float(P[:, K * D + K].sum())
+                chh[at] = int(np.rint(P[:, K * D + K + 1]).sum())
+                eh[at] = int((~live).sum())
+            index += 1
+        Cr = centroids.to(dt).double().numpy()
+        bias.copy_(torch.from_numpy((np.zeros(K) if spherical else -0.5 * (Cr * Cr).sum(axis=1)).astype(np.float32)))
+    else:
+        args = (None, None, None, None, 0) if partial is None else (_ptr(ih), _ptr(chh), _ptr(eh), _ptr(index), cap)
+        nat.check(nat.lib().gsage_kmeans_update(_ptr(partial) if partial is not None else None, S, K, D, _code(dt),
+                                                int(spherical), _ptr(centroids), _ptr(bias), *args, _stream()),
+                  "kmeans_update")
+    if partial is None or slot is None:
+        return None
+    return ih[0], chh[0], eh[0]
+
+
+# =============================================================================================
 # The head for a wide class dimension: normalize + fc + loss + gradients in one launch (csrc/gsage_head_wide.hip)
 # =============================================================================================
 WIDE_HEAD_C_MAX, WIDE_HEAD_D_MAX = 128, 1024

@@ -70,6 +70,17 @@ Retrieval over the embeddings (infer.nearest, opt-in):
   --probe-iters N         Adam iterations (default 100)     --probe-lr F   learning rate (default 0.1)
   --probe-l2 F            Adam's L2 term (default 0).  The defaults reach the toy results of the tests; nobody has
                           tuned them on a real graph.
+  --cluster K             after training (sharing the one embedding pass with --save-embeddings / --link-eval / --probe):
+                          node clustering.  Lloyd's k-means with K clusters on the frozen embeddings of every node of the
+                          three folds (gs.kmeans: every iteration a fused assign / accumulate pass and an update launch of
+                          csrc/gsage_kmeans.hip), scored against the labels of the validation fold; one line {"cluster":
+                          {"fold": "val", "k", "iters", "inertia", "nmi", "purity"}} is printed, with --show-test a second
+                          one for the test fold.  With and without --unsupervised.  A problem without class labels
+                          (multilabel, regression) prints the line without nmi and purity: clustering needs no labels.
+  --cluster-iters N       Lloyd iterations at most (default 50)   --cluster-init ++|random   (default ++: k-means++)
+  --cluster-n-init R      fits with seeds S, S + 1, ..; the lowest inertia is kept (default 1)   --cluster-seed S (0)
+  --cluster-spherical     unit-length centroids, assignment by inner product
+  --save-clusters PATH    .npz of nodes (the ids that were clustered), labels (theirs) and centroids
   --correct-smooth        after training: Correct and Smooth (gs.correct_smooth_eval, propagate.py) -- the logits of EVERY row by
                           full-neighbourhood inference over the evaluation adjacency, the train fold's residual errors
                           propagated over the graph and added back, the result smoothed with the train labels held
@@ -270,6 +281,26 @@ def probe_eval(problem, args, emb):
         sys.stdout.flush()
 
 
+def cluster_eval(problem, args, emb):
+    """--cluster K: k-means on the embeddings of every node of the three folds (gs.cluster_eval), one JSON line for the
+    validation fold and, with --show-test, one for the test fold; NMI and purity where the problem has class labels.
+    --save-clusters: the nodes, their labels and the centroids as an .npz."""
+    try:
+        res = gs.cluster_eval(emb, problem, k=args.cluster, iters=args.cluster_iters, init=args.cluster_init,
+                              n_init=args.cluster_n_init, seed=args.cluster_seed, spherical=args.cluster_spherical)
+    except (ValueError, IndexError) as e:
+        raise SystemExit('gsage: --cluster: %s' % e)
+    for fold in (['val', 'test'] if args.show_test else ['val']):
+        line = {"fold": fold, "k": res["k"], "iters": res["iters"], "inertia": res["inertia"]}
+        if res[fold] is not None:
+            line["nmi"], line["purity"] = res[fold]["nmi"], res[fold]["purity"]
+        print(dumps({"cluster": line}))
+        sys.stdout.flush()
+    if args.save_clusters:
+        with open(args.save_clusters, 'wb') as f:
+            np.savez(f, nodes=res["nodes"], labels=res["labels"].cpu().numpy(), centroids=res["centroids"].cpu().numpy())
+
+
 def cs_settings(args):
     """(iters, alpha) of --cs-iters / --cs-alpha, or SystemExit with a sentence."""
     try:
@@ -324,12 +355,14 @@ def export(model, problem, args):
             raise SystemExit('gsage: --save-neighbours: %s' % e)
         with open(args.save_neighbours, 'wb') as f:
             np.savez(f, ids=ids.cpu().numpy(), scores=scores.cpu().numpy())
-    if args.link_eval or args.probe:
+    if args.link_eval or args.probe or args.cluster:
         emb = emb if emb is not None else gs.embeddings(model, problem.feats)
     if args.link_eval:
         link_eval(model, problem, args, emb)
     if args.probe:
         probe_eval(problem, args, emb)
+    if args.cluster:
+        cluster_eval(problem, args, emb)
 
 
 class FusedEvaluator(object):
@@ -453,6 +486,13 @@ def parse_args(argv=None):
     parser.add_argument('--probe-iters', type=int, default=100)
     parser.add_argument('--probe-lr', type=float, default=0.1)
     parser.add_argument('--probe-l2', type=float, default=0.0)
+    parser.add_argument('--cluster', type=int, default=0)
+    parser.add_argument('--cluster-iters', type=int, default=50)
+    parser.add_argument('--cluster-init', type=str, default='++', choices=['++', 'random'])
+    parser.add_argument('--cluster-n-init', type=int, default=1)
+    parser.add_argument('--cluster-seed', type=int, default=0)
+    parser.add_argument('--cluster-spherical', action="store_true")
+    parser.add_argument('--save-clusters', type=str, default=None)
     parser.add_argument('--correct-smooth', action="store_true")
     parser.add_argument('--cs-iters', type=str, default='50,50')
     parser.add_argument('--cs-alpha', type=str, default='0.8,0.8')
@@ -570,6 +610,10 @@ def main(argv=None, problem=None):
             raise SystemExit('gsage: --link-eval: data-parallel launches are not supported (run a single process)')
     if args.probe and (args.probe_iters < 1 or not args.probe_lr > 0 or args.probe_l2 < 0):
         raise SystemExit('gsage: --probe-iters must be >= 1, --probe-lr > 0 and --probe-l2 >= 0')
+    if args.cluster < 0 or (args.cluster and (args.cluster_iters < 1 or args.cluster_n_init < 1)):
+        raise SystemExit('gsage: --cluster must be a number of clusters >= 1, --cluster-iters >= 1 and --cluster-n-init >= 1')
+    if args.save_clusters and not args.cluster:
+        raise SystemExit('gsage: --save-clusters goes with --cluster K')
     if args.label_prop and not args.correct_smooth:
         raise SystemExit('gsage: --label-prop goes with --correct-smooth')
     if args.correct_smooth:
@@ -652,20 +696,22 @@ def main(argv=None, problem=None):
     if args.unsupervised:
         if args.full_neighbour_eval:
             raise SystemExit('gsage: --unsupervised: --full-neighbour-eval scores logits; there are none')
-        if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
+        if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe or args.cluster:
             try:
                 gs.infer.check_supported(model, model.val_sampler.csr('cpu') if weighted else None)
             except ValueError as e:
-                raise SystemExit('gsage: --save-embeddings / --save-neighbours / --link-eval / --probe: %s' % e)
+                raise SystemExit('gsage: --save-embeddings / --save-neighbours / --link-eval / --probe%s: %s'
+                                 % (' / --cluster' if args.cluster else '', e))
         set_seeds(args.seed ** 2)
         return train_unsupervised(args, problem, model)
-    if args.full_neighbour_eval or args.save_embeddings or args.save_neighbours or args.link_eval or args.probe or \
+    if args.full_neighbour_eval or args.save_embeddings or args.save_neighbours or args.link_eval or args.probe or args.cluster or \
             args.correct_smooth:
         try:
             gs.infer.check_supported(model, model.val_sampler.csr('cpu') if weighted else None)
         except ValueError as e:
             flags = '--full-neighbour-eval / --save-embeddings / --save-neighbours / --link-eval / --probe'
-            raise SystemExit('gsage: %s%s: %s' % (flags, ' / --correct-smooth' if args.correct_smooth else '', e))
+            raise SystemExit('gsage: %s%s%s: %s' % (flags, ' / --correct-smooth' if args.correct_smooth else '',
+                                                      ' / --cluster' if args.cluster else '', e))
     evaluate_fn = (lambda mode: full_neighbour_evaluate(model, problem, mode=mode, closure=args.eval_closure)) \
         if args.full_neighbour_eval else \
         (lambda mode: evaluate(model, problem, mode=mode))
@@ -705,7 +751,7 @@ def main(argv=None, problem=None):
         sys.stdout.flush()
         if args.show_test:
             print(dumps({"test_f1": evaluate_fn('test')}))
-        if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
+        if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe or args.cluster:
             export(model, problem, args)
         if args.correct_smooth:
             correct_smooth(model, problem, args)
@@ -764,7 +810,7 @@ def train_unsupervised(args, problem, model):
     sys.stdout.flush()
     if eng is not None:
         eng.close()
-    if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
+    if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe or args.cluster:
         export(model, problem, args)
 
 
@@ -982,7 +1028,7 @@ def train_fused(args, problem, model, ddp, start_time, cls):
         sys.stdout.flush()
         if args.show_test:
             print(dumps({"test_f1": test_metric}))
-        if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe:
+        if args.save_embeddings or args.save_neighbours or args.link_eval or args.probe or args.cluster:
             export(model, problem, args)
         if args.correct_smooth:
             correct_smooth(model, problem, args)
