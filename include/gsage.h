@@ -1265,6 +1265,62 @@ int gsage_sample_csr_distinct(const int64_t *rowptr, const int32_t *col, int64_t
 int gsage_sample_hops_distinct(const gsage_hops_desc *hops, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Temporal neighbours (csrc/gsage_temporal.hip): neighbour sampling over the edges that happened BEFORE a query
+ * time, and the snapshot of a graph "as of T".  Additive; the ABI version is unchanged.  No reference counterpart
+ * (its samplers know no time).
+ *
+ * A temporal CSR is rowptr int64 [n_rows + 1], col int32 [nnz] and etime int64 [nnz]: within every row etime is
+ * non-decreasing, every etime is below INT64_MAX, every row is shorter than 2^32 (a longer one yields the dummy and
+ * sets *err_flag, as under "Distinct neighbours").
+ *
+ * One sampler call with n >= 1 samples per parent takes the parents ids[i], their query times times[i] (int64), a
+ * strategy and an inheritance rule.  For parent v = ids[i], t = times[i] and beg = rowptr[v]:
+ *     cnt  = the number of edges e of row v with etime[e] < t     -- STRICT: an edge that happens at the prediction
+ *            time is not visible; the comparison is one of signed 64-bit values.  The eligible edges are positions
+ *            0 .. cnt-1 of the row (the row is in time order); t = INT64_MAX sees the whole row.
+ *     w(g) = philox4x32_10({lo(g>>2), hi(g>>2), lo(call), hi(call)}, {lo(seed), hi(seed) ^ 0x54000000})[g & 3]
+ *            with g = g0 + i*n + j and call = call_base + (call_ctr ? *call_ctr : 0): the uniform sampler's addressing
+ *            under a key tag of its own.
+ *     GSAGE_TEMPORAL_UNIFORM   off = (w(g) * cnt) >> 32         (not the reference's sel % deg: cnt is typically far
+ *                              below max_deg, and the modulo bias would reach a factor of two)
+ *     GSAGE_TEMPORAL_RECENT    off = cnt - 1 - (j % cnt)        -- no random word: the min(n, cnt) most recent eligible
+ *                              edges, most recent first, cycled; when cnt divides n the plain mean over the slots is
+ *                              the exact mean over the eligible edges
+ *     out[i*n+j]      = col[beg + off]
+ *     out_time[i*n+j] = times[i]            under GSAGE_TEMPORAL_INHERIT_SEED: every hop looks before the seed's time
+ *                     = etime[beg + off]    under GSAGE_TEMPORAL_INHERIT_EDGE: the next hop looks before the edge just
+ *                                           walked, so times strictly decrease along a path
+ *     cnt == 0                 the dummy 0 in all n slots, out_time = times[i]
+ *     v outside [0, n_rows)    0 in all n slots, out_time = times[i], and *err_flag (may be NULL) is set to 1
+ *
+ * gsage_sample_csr_temporal -- one launch per hop: out, out_time int64 [M * n].
+ * gsage_temporal_count -- cnt[i] (int64 [M]) for the rows ids[i], or for every row i in [0, M) when ids == NULL
+ * (then M <= n_rows), against times[i], or against the one scalar t when times == NULL.  A row outside the graph
+ * counts 0 and sets *err_flag.
+ * gsage_temporal_compact -- given cnt int64 [n_rows] and its exclusive prefix int64 [n_rows], copy the first
+ * min(cnt[v], deg_v) entries of every row's col and etime to out_col / out_etime (out_nnz entries each) from
+ * position prefix[v] on: with the prefix as the new rowptr, the CSR of the edges before t.  Nothing is written
+ * outside [0, out_nnz).
+ *
+ * All three: a null pointer, a negative size, n < 1, an unknown strategy or rule give GSAGE_EINVAL without a launch,
+ * the message naming the argument; M == 0 (n_rows == 0 for the compaction) returns GSAGE_OK without one.  All three
+ * can be recorded in a command list.
+ * ---------------------------------------------------------------------------------------- */
+#define GSAGE_TEMPORAL_UNIFORM 0
+#define GSAGE_TEMPORAL_RECENT 1
+#define GSAGE_TEMPORAL_INHERIT_SEED 0
+#define GSAGE_TEMPORAL_INHERIT_EDGE 1
+int gsage_sample_csr_temporal(const int64_t *rowptr, const int32_t *col, const int64_t *etime, int64_t n_rows,
+                              const int64_t *ids, const int64_t *times, int64_t M, int32_t n, int32_t strategy,
+                              int32_t inherit, uint64_t seed, const uint64_t *call_ctr, uint64_t call_base, uint64_t g0,
+                              int64_t *out, int64_t *out_time, int32_t *err_flag, void *stream);
+int gsage_temporal_count(const int64_t *rowptr, const int64_t *etime, int64_t n_rows, const int64_t *ids, int64_t M,
+                         const int64_t *times, int64_t t, int64_t *cnt, int32_t *err_flag, void *stream);
+int gsage_temporal_compact(const int64_t *rowptr, const int32_t *col, const int64_t *etime, int64_t n_rows,
+                           const int64_t *cnt, const int64_t *prefix, int32_t *out_col, int64_t *out_etime,
+                           int64_t out_nnz, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance neighbourhoods (csrc/gsage_importance.hip): a node's most-visited nodes under short random walks become
  * its neighbourhood, the visit counts its edge weights (the construction PinSAGE introduced).  What turns ANY
  * adjacency into a weighted one for everything under "Weighted adjacency".  Additive; the ABI version is unchanged.

@@ -32,6 +32,10 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
     nn_modules.SparseDistinctNeighborSampler   neighbours WITHOUT replacement (sparse_distinct_neighbor_sampler in
                               sampler_extensions; ops.sample_csr_distinct, csrc/gsage_distinct.hip): every neighbour of a
                               short row, n distinct ones of a long row
+    nn_modules.SparseTemporalNeighborSampler   neighbours among the edges BEFORE a query time (sparse_temporal_neighbor_
+                              sampler in sampler_extensions; ops.sample_csr_temporal, csrc/gsage_temporal.hip) over a
+                              store.TemporalAdj; store.DeviceCSR.snapshot(t): the graph "as of t" for everything in
+                              infer.py and propagate.py
     engine/                   the whole train_step as recorded launches (captured autograd path; fused mean /
                               pool / attention engines on a shared base; opt-in: the weighted mean engine, the
                               distinct-draw mean engine FusedDistinctMeanTrainStep and the unsupervised engines,
@@ -47,10 +51,10 @@ from .nn_modules import aggregator_lookup, find_sampler, prep_lookup, sampler_ex
 # (gs.propagate is the FUNCTION; its module is sys.modules[gs.propagate.__module__])
 from .propagate import correct_and_smooth, correct_smooth_eval, label_propagation, propagate   # noqa: F401
 from .problem import DeviceMetrics, NodeProblem, ProblemLosses, ProblemMetrics, batch_metric   # noqa: F401
-from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef, WeightedAdj, importance_adj  # noqa: F401
+from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef, TemporalAdj, WeightedAdj, importance_adj  # noqa: F401
 
 __all__ = ["GSSupervised", "GSUnsupervised", "NodeProblem", "aggregator_lookup", "prep_lookup", "sampler_lookup",
            "set_seeds", "to_numpy", "LRSchedule", "FeatureStore", "DeviceCSR", "RowRef", "ops", "full_neighbour",
            "embeddings", "query", "nearest", "link_rank", "link_metrics", "held_out_edges", "LinearProbe", "linear_probe",
-           "probe_eval", "KMeans", "kmeans", "cluster_metrics", "cluster_eval", "WeightedAdj", "find_sampler", "sampler_extensions", "importance_adj",
+           "probe_eval", "KMeans", "kmeans", "cluster_metrics", "cluster_eval", "WeightedAdj", "TemporalAdj", "find_sampler", "sampler_extensions", "importance_adj",
            "propagate", "label_propagation", "correct_and_smooth", "correct_smooth_eval"]

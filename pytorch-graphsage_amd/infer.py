@@ -38,7 +38,7 @@ from . import _native as nat
 from . import ops
 from .nn_modules import (AttentionAggregator, IdentityPrep, LinearPrep, LSTMAggregator, MeanAggregator,
                          NodeEmbeddingPrep, PoolAggregator, concat_combine, _split_activation)
-from .store import DenseAdj, DeviceCSR, FeatureStore, WeightedAdj, _round_up
+from .store import DenseAdj, DeviceCSR, FeatureStore, TemporalAdj, WeightedAdj, _round_up
 
 SLICE_LEN = 256          # rows of higher degree are cut into slices of this many edges (one team each)
 
@@ -635,7 +635,7 @@ def nearest(emb, nodes=None, k=10, exclude="self", adj=None):
             raise ValueError("nearest: exclude='neighbours' needs adj (a store.DeviceCSR)")
         if isinstance(adj, DenseAdj):
             raise ValueError("nearest: exclude='neighbours' reads a CSR; a DenseAdj holds samples, not the edges")
-        if isinstance(adj, WeightedAdj):
+        if isinstance(adj, (WeightedAdj, TemporalAdj)):      # (a TemporalAdj: every stored edge, whatever its time)
             adj = DeviceCSR.from_scipy(adj.adj, dev)
         if not isinstance(adj, DeviceCSR):
             raise ValueError("nearest: adj must be a store.DeviceCSR or a store.WeightedAdj")
@@ -650,7 +650,7 @@ def _as_csr(adj, dev, who):
     """`adj` as a store.DeviceCSR: a WeightedAdj is read as its CSR, a DenseAdj is refused with nearest()'s sentence."""
     if isinstance(adj, DenseAdj):
         raise ValueError("%s: exclude='neighbours' reads a CSR; a DenseAdj holds samples, not the edges" % who)
-    if isinstance(adj, WeightedAdj):
+    if isinstance(adj, (WeightedAdj, TemporalAdj)):
         got = getattr(adj, "_device_csr", None)
         if got is None or got.device != torch.device(dev):
             got = DeviceCSR.from_scipy(adj.adj, dev)

@@ -72,8 +72,11 @@ class _SageModel(nn.Module):
             self._wrapped = {key: FeatureStore.wrap(feats)}
         return self._wrapped[key]
 
-    def _encode(self, ids, feats, train=True):
-        """The un-normalised top-level rows [len(ids), width] (fp32) of `ids`: frontier, prep, layer stack."""
+    def _encode(self, ids, feats, train=True, times=None):
+        """The un-normalised top-level rows [len(ids), width] (fp32) of `ids`: frontier, prep, layer stack.
+        times: int64 [len(ids)], the seeds' query times under a temporal sampler (nn_modules.
+        SparseTemporalNeighborSampler) -- they flow hop by hop beside the ids; None: node_time[ids] of the sampler's
+        adjacency, or INT64_MAX without one.  With any other sampler `times` must be None."""
         # a fused engine that defers the embedding table's zero-gradient Adam updates (engine.sync_rows)
         # settles them HERE: the prep reads `embedding.weight` directly, not through the nn.Embedding
         # module, so a hook on that module would never fire
@@ -85,9 +88,19 @@ class _SageModel(nn.Module):
         rows = (lambda i: table[i]) if table is not None else (lambda i: None)
 
         # frontier: [B], [B*f1], [B*f1*f2], ...  (models.py:75-81)
+        sampler = self.train_sampler if train else self.val_sampler
+        temporal = bool(getattr(sampler, "temporal", False))
+        if temporal:
+            times = sampler.default_times(ids) if times is None else times.to(ids.device).contiguous().view(-1)
+        elif times is not None:
+            raise ValueError("times were given, but %s is not a temporal sampler (sparse_temporal_neighbor_sampler)"
+                             % type(sampler).__name__)
         hops = [self.prep(ids, rows(ids), layer_idx=0)]
         for hop, sample in enumerate(sample_fns):
-            ids = sample(ids=ids).contiguous().view(-1)
+            if temporal:
+                ids, times = sample(ids=ids, times=times)
+            else:
+                ids = sample(ids=ids).contiguous().view(-1)
             hops.append(self.prep(ids, rows(ids), layer_idx=hop + 1))
 
         # layer l maps every adjacent pair of hop representations; shared weights (models.py:85-86)
@@ -181,18 +194,18 @@ class GSSupervised(_SageModel):
         self.fc = nn.Linear(width, n_classes, bias=True)
         self._build_optimizer(lr_init, weight_decay, lr_schedule)
 
-    def forward(self, ids, feats, train=True):
-        out = F.normalize(self._encode(ids, feats, train), dim=1)
+    def forward(self, ids, feats, train=True, times=None):
+        out = F.normalize(self._encode(ids, feats, train, times=times), dim=1)
         if out.is_cuda:
             # the head's projection on K5 in exact fp32 (models.py:91 is an nn.Linear: a library GEMM on the GPU
             # otherwise -- the last one of the module path, forward and backward)
             return ops.linear(out, self.fc.weight, self.fc.bias, compute_dtype="fp32")
         return self.fc(out)
 
-    def train_step(self, ids, feats, targets, loss_fn):
+    def train_step(self, ids, feats, targets, loss_fn, times=None):
         flat = self._flat_optimizer()
         self.optimizer.zero_grad()
-        preds = self(ids, feats, train=True)
+        preds = self(ids, feats, train=True) if times is None else self(ids, feats, train=True, times=times)
         loss = loss_fn(preds, targets.squeeze())
         loss.backward()
         self._clip_and_step(flat)

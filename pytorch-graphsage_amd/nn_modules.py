@@ -21,7 +21,7 @@ from torch.nn import functional as F
 
 from . import _native as nat
 from . import ops
-from .store import DenseAdj, DeviceCSR, RowRef, WeightedAdj
+from .store import DenseAdj, DeviceCSR, RowRef, TemporalAdj, WeightedAdj
 
 
 # --------------------------------------------------------------------------------------------
@@ -79,7 +79,7 @@ class SparseUniformNeighborSampler(object):
     rng_default = "compat"
 
     def __init__(self, adj, rng=None, seed=0):
-        if isinstance(adj, WeightedAdj):          # a weighted problem under the uniform sampler: the weights are ignored
+        if isinstance(adj, (WeightedAdj, TemporalAdj)):    # under the uniform sampler the weights / times are ignored
             adj = adj.adj
         self.adj = adj
         self._host = DeviceCSR.from_scipy(adj, torch.device("cpu"))
@@ -250,7 +250,7 @@ class SparseDistinctNeighborSampler(object):
     _said_philox = False
 
     def __init__(self, adj, rng=None, seed=0):
-        if isinstance(adj, WeightedAdj):
+        if isinstance(adj, (WeightedAdj, TemporalAdj)):
             adj = adj.adj
         if (rng or SparseUniformNeighborSampler.rng_default) != "philox" and not SparseDistinctNeighborSampler._said_philox:
             SparseDistinctNeighborSampler._said_philox = True
@@ -294,6 +294,108 @@ class SparseDistinctNeighborSampler(object):
         return self._static_calls
 
 
+class SparseTemporalNeighborSampler(object):
+    """CSR neighbour sampling over the edges that happened strictly BEFORE a query time (no reference counterpart;
+    include/gsage.h, "Temporal neighbours"): training node v "as of time t" on later edges would leak the future
+    into the prediction.  adj: a store.TemporalAdj (a bare scipy matrix carries no times: ValueError).  strategy
+    "uniform" draws with replacement among the eligible edges, "recent" takes the latest ones; inherit "seed" keeps the
+    seed's time at every hop, "edge" hands the walked edge's time to the next hop (class-wide strategy_default /
+    inherit_default, as rng_default).  The call takes and returns the times explicitly --
+    (ids, times, n_samples) -> (ids, times) -- and keeps no frontier time between calls: two interleaved forwards
+    cannot mix.  times=None asks for the adjacency's node_time (INT64_MAX without one: the whole row).  Same `shard`,
+    begin_capture / calls_in_capture, csr(device) and use_device_csr as SparseUniformNeighborSampler, of which it is
+    deliberately NOT a subclass (see SparseDistinctNeighborSampler).  It always draws from Philox and says so once when
+    the class-wide default asks for "compat"."""
+
+    _said_philox = False
+    strategy_default = "uniform"
+    inherit_default = "seed"
+    temporal = True                   # what models.py asks a sampler: do the times flow beside the ids
+
+    def __init__(self, adj, rng=None, seed=0, strategy=None, inherit=None):
+        if not isinstance(adj, TemporalAdj):
+            raise ValueError("SparseTemporalNeighborSampler: the adjacency carries no edge times "
+                             "(wrap it in store.TemporalAdj, or add adj_time / train_adj_time to the problem)")
+        self.strategy = strategy or SparseTemporalNeighborSampler.strategy_default
+        self.inherit = inherit or SparseTemporalNeighborSampler.inherit_default
+        if self.strategy not in ops.TEMPORAL_STRATEGIES:
+            raise ValueError("SparseTemporalNeighborSampler: unknown strategy %r (known: uniform, recent)" % (self.strategy,))
+        if self.inherit not in ops.TEMPORAL_INHERIT:
+            raise ValueError("SparseTemporalNeighborSampler: unknown inherit rule %r (known: seed, edge)" % (self.inherit,))
+        if (rng or SparseUniformNeighborSampler.rng_default) != "philox" and not SparseTemporalNeighborSampler._said_philox:
+            SparseTemporalNeighborSampler._said_philox = True
+            print("gsage: the temporal sampler always draws from Philox (--rng compat has no meaning for it)",
+                  file=sys.stderr)
+        self.adj = adj
+        self._host = DeviceCSR.from_scipy(adj.adj, torch.device("cpu")).with_times(torch.from_numpy(adj.time))
+        self._node_time = {}          # device -> int64 [n_rows]
+        if adj.node_time is not None:
+            self._node_time["cpu"] = torch.from_numpy(adj.node_time)
+        self._dev = {}
+        self.rng = "philox"
+        self.seed = int(seed)
+        self.calls = 0                # host-side call index (eager)
+        self.call_ctr = None          # device counter tensor (inside a captured graph)
+        self.shard = (0, 1)           # (rank, world): offsets the global sample index
+
+    degrees = SparseUniformNeighborSampler.degrees
+
+    def csr(self, device):
+        device = torch.device(device)
+        if device.type == "cpu":
+            return self._host
+        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        if key not in self._dev:
+            # (the host copy was checked when it was built: the same bytes need no second pass)
+            self._dev[key] = DeviceCSR(self._host.rowptr.to(device), self._host.col.to(device), self._host.n_rows,
+                                       self._host.max_deg, etime=self._host.etime.to(device))
+        return self._dev[key]
+
+    def use_device_csr(self, csr):
+        """Walk `csr` (a temporal store.DeviceCSR already in HBM) on its device, as the uniform sampler's."""
+        if csr.etime is None:
+            raise ValueError("SparseTemporalNeighborSampler: the adjacency carries no edge times")
+        dev = csr.device
+        self._dev[(dev.type, dev.index if dev.index is not None else torch.cuda.current_device())] = csr
+        return csr
+
+    def default_times(self, ids):
+        """The query times of seeds that come without any: node_time[ids], or INT64_MAX without a node_time."""
+        ids = ids.contiguous().view(-1)
+        if "cpu" not in self._node_time:
+            return torch.full((int(ids.shape[0]),), ops.INT64_MAX, dtype=torch.int64, device=ids.device)
+        key = str(ids.device)
+        if key not in self._node_time:
+            self._node_time[key] = self._node_time["cpu"].to(ids.device)
+        return self._node_time[key][ids]
+
+    def __call__(self, ids, times=None, n_samples=128):
+        assert n_samples > 0, 'SparseTemporalNeighborSampler: n_samples must be set explicitly'
+        ids = ids.contiguous().view(-1)
+        if times is None:
+            times = self.default_times(ids)
+        csr = self.csr(ids.device)
+        rank, _ = self.shard
+        ph = {"seed": self.seed, "g0": rank * int(ids.shape[0]) * n_samples}
+        if self.call_ctr is not None:
+            ph["call_ctr"] = self.call_ctr
+            ph["call_base"] = self._static_calls
+            self._static_calls += 1
+        else:
+            ph["call_base"] = self.calls
+            self.calls += 1
+        return ops.sample_csr_temporal(csr, ids, times, n_samples, ph, strategy=self.strategy, inherit=self.inherit)
+
+    _static_calls = 0
+
+    def begin_capture(self, counter):
+        self.call_ctr = counter
+        self._static_calls = 0
+
+    def calls_in_capture(self):
+        return self._static_calls
+
+
 sampler_lookup = {
     "uniform_neighbor_sampler": UniformNeighborSampler,
     "sparse_uniform_neighbor_sampler": SparseUniformNeighborSampler,
@@ -304,6 +406,7 @@ sampler_lookup = {
 sampler_extensions = {
     "sparse_weighted_neighbor_sampler": SparseWeightedNeighborSampler,
     "sparse_distinct_neighbor_sampler": SparseDistinctNeighborSampler,
+    "sparse_temporal_neighbor_sampler": SparseTemporalNeighborSampler,
 }
 
 

@@ -556,6 +556,170 @@ def sample_hops_distinct(csr, ids, B, fans, philox):
 
 
 # =============================================================================================
+# Temporal neighbours: sampling over the edges before a query time, snapshots (csrc/gsage_temporal.hip)
+# =============================================================================================
+TEMPORAL_TAG = 0x54000000                                                             # include/gsage.h
+TEMPORAL_STRATEGIES = {"uniform": 0, "recent": 1}                                     # GSAGE_TEMPORAL_UNIFORM / _RECENT
+TEMPORAL_INHERIT = {"seed": 0, "edge": 1}                                             # GSAGE_TEMPORAL_INHERIT_SEED / _EDGE
+INT64_MAX = (1 << 63) - 1
+
+
+def _temporal_csr(csr, who):
+    if getattr(csr, "etime", None) is None:
+        raise ValueError("%s: the adjacency carries no edge times (DeviceCSR.with_times)" % who)
+    return csr
+
+
+def _temporal_count_host(rp, et, rows, t):
+    """cnt int64 [len(rows)]: per row the number of edges with etime < t (t: an array per row); the rows are in time
+    order, so one binary search over all rows at once"""
+    lo, hi = rp[rows].copy(), rp[rows + 1].copy()
+    beg = lo.copy()
+    while True:
+        act = lo < hi
+        if not act.any():
+            break
+        mid = (lo + hi) >> 1
+        before = np.zeros(lo.shape, dtype=bool)
+        before[act] = et[mid[act]] < t[act]
+        lo = np.where(act & before, mid + 1, lo)
+        hi = np.where(act & ~before, mid, hi)
+    return lo - beg
+
+
+def sample_csr_temporal(csr, ids, times, n, philox, strategy="uniform", inherit="seed", out=None, out_time=None):
+    """SparseTemporalNeighborSampler.__call__ (include/gsage.h, "Temporal neighbours", gsage_sample_csr_temporal): n
+    neighbours of every id among the edges that happened strictly BEFORE the id's query time -- strategy "uniform":
+    uniformly with replacement, off = (w * cnt) >> 32; "recent": the min(n, cnt) latest, most recent first, cycled -- and
+    the query times of the next hop: the parent's own (inherit "seed") or the walked edge's (inherit "edge").  A
+    parent without an eligible edge yields the dummy 0 and its own time.  csr: a store.DeviceCSR with `.etime`; times:
+    int64 [M] on the ids' device; philox: dict(seed, call_base, g0, call_ctr) as for sample_csr.  Returns
+    (LongTensor [M*n], LongTensor [M*n]) on the ids' device.  CPU tensors: the same definition in numpy (host mode)."""
+    n = int(n)
+    assert n >= 1, "SparseTemporalNeighborSampler: n_samples must be set explicitly"
+    _temporal_csr(csr, "sample_csr_temporal")
+    if strategy not in TEMPORAL_STRATEGIES:
+        raise ValueError("sample_csr_temporal: unknown strategy %r (known: uniform, recent)" % (strategy,))
+    if inherit not in TEMPORAL_INHERIT:
+        raise ValueError("sample_csr_temporal: unknown inherit rule %r (known: seed, edge)" % (inherit,))
+    ids = ids.contiguous().view(-1)
+    times = times.contiguous().view(-1)
+    M = int(ids.shape[0])
+    assert times.dtype == torch.int64 and int(times.shape[0]) == M and times.device == ids.device, \
+        "sample_csr_temporal: times must be int64 [M] on the ids' device"
+    seed, base, g0 = int(philox["seed"]), int(philox.get("call_base", 0)), int(philox.get("g0", 0))
+    ctr = philox.get("call_ctr")
+    if ids.is_cuda:
+        if out is None:
+            out = torch.empty(M * n, dtype=torch.int64, device=ids.device)
+        if out_time is None:
+            out_time = torch.empty(M * n, dtype=torch.int64, device=ids.device)
+        for o in (out, out_time):
+            assert o.dtype == torch.int64 and o.numel() == M * n and o.is_contiguous()
+        nat.check(nat.lib().gsage_sample_csr_temporal(_ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.etime), csr.n_rows,
+                                                      _ptr(ids), _ptr(times), M, n, TEMPORAL_STRATEGIES[strategy],
+                                                      TEMPORAL_INHERIT[inherit], seed, _ptr(ctr), base, g0, _ptr(out),
+                                                      _ptr(out_time), _ptr(csr.err_flag), _stream()),
+                  "sample_csr_temporal")
+        return out, out_time
+    # ---- host mode
+    idn, tn = ids.numpy(), times.numpy()
+    if idn.size and (idn.min() < 0 or idn.max() >= csr.n_rows):
+        raise IndexError("sampler: node id out of range of the adjacency")
+    keep = np.repeat(tn, n)
+    if M == 0 or csr.nnz == 0:
+        return torch.zeros(M * n, dtype=torch.int64), torch.from_numpy(keep)
+    rp, col, et = csr.rowptr.numpy(), csr.col.numpy(), csr.etime.numpy()
+    beg = rp[idn]
+    cnt = _temporal_count_host(rp, et, idn, tn).astype(np.uint64)
+    live = cnt > 0
+    safe = np.maximum(cnt, np.uint64(1))[:, None]
+    slot = np.arange(n, dtype=np.uint64)[None, :]
+    if strategy == "recent":
+        off = safe - np.uint64(1) - slot % safe
+    else:
+        call = base + (int(ctr.item()) if ctr is not None else 0)
+        w = _philox_words_host(seed, TEMPORAL_TAG, call, g0, M * n).reshape(M, n)
+        off = (w * safe) >> np.uint64(32)
+    pos = np.minimum(beg[:, None] + off.astype(np.int64), col.shape[0] - 1)
+    vals = np.where(live[:, None], col[pos].astype(np.int64), 0).reshape(-1)
+    if inherit == "edge":
+        keep = np.where(live[:, None], et[pos], tn[:, None]).reshape(-1)
+    return torch.from_numpy(vals), torch.from_numpy(np.ascontiguousarray(keep, dtype=np.int64))
+
+
+def temporal_count(csr, ids=None, times=None, t=None):
+    """cnt int64 [M] (include/gsage.h, gsage_temporal_count): per row ids[i] -- every row of the graph when ids is
+    None -- the number of edges with etime < times[i], or < the one scalar t when times is None.  One launch, the hop
+    kernel's cooperative search.  CPU adjacencies: the same counts in numpy (host mode)."""
+    _temporal_csr(csr, "temporal_count")
+    if (times is None) == (t is None):
+        raise ValueError("temporal_count: exactly one of times (a tensor per row) and t (one scalar) must be given")
+    dev = csr.device
+    if ids is not None:
+        ids = ids.contiguous().view(-1)
+        assert ids.dtype == torch.int64 and ids.device == dev, "temporal_count: ids must be int64 on the adjacency's device"
+    M = int(ids.shape[0]) if ids is not None else csr.n_rows
+    if times is not None:
+        times = times.contiguous().view(-1)
+        assert times.dtype == torch.int64 and int(times.shape[0]) == M and times.device == dev, \
+            "temporal_count: times must be int64 [M] on the adjacency's device"
+    else:
+        t = int(t)
+        if not -INT64_MAX - 1 <= t <= INT64_MAX:
+            raise ValueError("temporal_count: t = %d is not an int64" % t)
+    if dev.type != "cpu":
+        cnt = torch.zeros(M, dtype=torch.int64, device=dev)
+        nat.check(nat.lib().gsage_temporal_count(_ptr(csr.rowptr), _ptr(csr.etime), csr.n_rows, _ptr(ids), M, _ptr(times),
+                                                 t if times is None else 0, _ptr(cnt), _ptr(csr.err_flag), _stream()),
+                  "temporal_count")
+        return cnt
+    # ---- host mode
+    rows = ids.numpy() if ids is not None else np.arange(M, dtype=np.int64)
+    if rows.size and (rows.min() < 0 or rows.max() >= csr.n_rows):
+        raise IndexError("sampler: node id out of range of the adjacency")
+    tn = times.numpy() if times is not None else np.full(M, t, dtype=np.int64)
+    if M == 0 or csr.nnz == 0:
+        return torch.zeros(M, dtype=torch.int64)
+    return torch.from_numpy(_temporal_count_host(csr.rowptr.numpy(), csr.etime.numpy(), rows, tn).astype(np.int64))
+
+
+def temporal_compact(csr, cnt, rowptr):
+    """(col int32 [nnz'], etime int64 [nnz']) of the CSR that keeps the first cnt[v] entries of every row of `csr`
+    (include/gsage.h, gsage_temporal_compact); rowptr int64 [n_rows + 1]: 0 followed by the running sum of cnt.  One
+    launch, a row copy.  CPU adjacencies: the same copy in numpy (host mode)."""
+    _temporal_csr(csr, "temporal_compact")
+    assert cnt.dtype == torch.int64 and cnt.numel() == csr.n_rows and cnt.is_contiguous() and cnt.device == csr.device
+    assert rowptr.dtype == torch.int64 and rowptr.numel() == csr.n_rows + 1 and rowptr.is_contiguous() and \
+        rowptr.device == csr.device
+    total = int(rowptr[-1]) if csr.n_rows else 0
+    col = torch.empty(total, dtype=torch.int32, device=csr.device)
+    etime = torch.empty(total, dtype=torch.int64, device=csr.device)
+    if csr.device.type != "cpu":
+        nat.check(nat.lib().gsage_temporal_compact(_ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.etime), csr.n_rows, _ptr(cnt),
+                                                   _ptr(rowptr), _ptr(col), _ptr(etime), total, _stream()),
+                  "temporal_compact")
+        return col, etime
+    if total:
+        c = cnt.numpy()
+        src = np.repeat(csr.rowptr.numpy()[:-1] - rowptr.numpy()[:-1], c) + np.arange(total, dtype=np.int64)
+        col.copy_(csr.col[torch.from_numpy(src)])
+        etime.copy_(csr.etime[torch.from_numpy(src)])
+    return col, etime
+
+
+def temporal_snapshot(csr, t):
+    """(rowptr, col, etime) of the graph "as of t" (store.DeviceCSR.snapshot): the edges with etime < t, by
+    temporal_count, one torch.cumsum and temporal_compact on the adjacency's device."""
+    cnt = temporal_count(csr, t=t)
+    rowptr = torch.zeros(csr.n_rows + 1, dtype=torch.int64, device=csr.device)
+    if csr.n_rows:
+        torch.cumsum(cnt, 0, out=rowptr[1:])
+    col, etime = temporal_compact(csr, cnt, rowptr)
+    return rowptr, col, etime
+
+
+# =============================================================================================
 # Importance neighbourhoods: visit counts of short random walks and their top-T (csrc/gsage_importance.hip)
 # =============================================================================================
 IMPORTANCE_TAG = 0x49000000                                                           # include/gsage.h

@@ -11,11 +11,17 @@ global stream for the shuffle.  Differences:
   * a sparse problem may carry edge weights: optional keys `adj_weight` / `train_adj_weight`, in the encoding of `adj`
     ((v, r, c) with v the weights); `adj` / `train_adj` then become store.WeightedAdj (what
     sparse_weighted_neighbor_sampler needs; the uniform samplers ignore the weights).  Files without them load as before;
+  * a sparse problem may carry edge times: optional keys `adj_time` / `train_adj_time`, int64 in the encoding of `adj`
+    ((v, r, c) with v the times), and `node_time`, int64 [n_nodes], the default query time of a seed; `adj` /
+    `train_adj` then become store.TemporalAdj (what sparse_temporal_neighbor_sampler needs; the other samplers ignore
+    the times).  A file with both weights and times loads as temporal.  Files without them load as before;
   * with cuda=True the feature matrix becomes a store.FeatureStore resident in HBM
     (bf16 rows padded to 128 B; fp32 when ops.config.compute_dtype == "fp32") instead of a
     FloatTensor, so per-batch gathers are fused into the aggregator kernels.
 """
 from __future__ import division, print_function
+
+import sys
 
 import numpy as np
 import torch
@@ -24,7 +30,7 @@ from scipy.sparse import csr_matrix
 from torch.nn import functional as F
 
 from . import ops
-from .store import FeatureStore, WeightedAdj
+from .store import FeatureStore, TemporalAdj, WeightedAdj
 
 
 class ProblemLosses:
@@ -199,8 +205,31 @@ def _weighted(adj, w):
     return WeightedAdj(adj, w)
 
 
+def _temporal(adj, tm, node_time, weight=None, key="adj", quiet=False):
+    """adj with the edge times of the problem file's (v, r, c) triple `tm` (v: int64 times) as a store.TemporalAdj,
+    or `adj` as it is without one.  Weights and times together are not supported: the weights are ignored, with one
+    line on stderr (quiet: the line was said for the problem's other adjacency already)."""
+    if tm is None:
+        return adj
+    if isinstance(adj, WeightedAdj) or weight is not None:
+        if not quiet:
+            print("gsage: the problem carries both edge weights and edge times (%s): loaded as temporal, the weights "
+                  "are ignored" % key, file=sys.stderr)
+        adj = adj.adj if isinstance(adj, WeightedAdj) else adj
+    if not sparse.issparse(adj):
+        raise ValueError("edge times need a sparse adjacency")
+    if not sparse.issparse(tm):
+        tm = np.asarray(tm)
+        if tm.ndim == 2 and tm.shape[0] == 3:
+            if tm.dtype.kind not in "iu":
+                raise ValueError("edge times must be int64 (the %s_time key holds %s)" % (key, tm.dtype))
+            v, r, c = tm
+            tm = csr_matrix((v.astype(np.int64), (r.astype(np.int64), c.astype(np.int64))), shape=adj.shape)
+    return TemporalAdj(adj, tm, node_time=node_time)
+
+
 def _is_sparse(adj):
-    return sparse.issparse(adj) or isinstance(adj, WeightedAdj)
+    return sparse.issparse(adj) or isinstance(adj, (WeightedAdj, TemporalAdj))
 
 
 def _scalar(v):
@@ -227,6 +256,15 @@ def save_problem_npz(path, problem):
     """Writes the .npz twin of the reference's problem.h5 (same keys; sparse adjacencies as the
     [3, nnz] (v, r, c) array of utils/convert.py:128-131)."""
     out = {}
+    problem = dict(problem)
+    for k in ("adj", "train_adj"):                  # a TemporalAdj's times travel under their own keys, in ITS order
+        v = problem.get(k)
+        if isinstance(v, TemporalAdj):
+            coo = v.adj.tocoo()
+            problem[k] = v.adj
+            problem[k + "_time"] = np.vstack([v.time, coo.row.astype(np.int64), coo.col.astype(np.int64)])
+            if v.node_time is not None and problem.get("node_time") is None:
+                problem["node_time"] = v.node_time
     for k, v in problem.items():
         if v is None:
             continue
@@ -248,9 +286,17 @@ class NodeProblem(object):
         self.feats = f['feats'] if 'feats' in f else None
         self.folds = np.array([s.decode() if isinstance(s, bytes) else str(s) for s in f['folds']])
         self.targets = f['targets']
+        self.node_time = None
         if 'sparse' in f and bool(_scalar(f['sparse'])):
             self.adj = _weighted(parse_csr_matrix(f['adj']), f.get('adj_weight'))
             self.train_adj = _weighted(parse_csr_matrix(f['train_adj']), f.get('train_adj_weight'))
+            self.node_time = np.asarray(f['node_time']) if 'node_time' in f else None
+            said = isinstance(self.adj, WeightedAdj) and 'adj_time' in f
+            self.adj = _temporal(self.adj, f.get('adj_time'), self.node_time, key='adj')
+            self.train_adj = _temporal(self.train_adj, f.get('train_adj_time'), self.node_time, key='train_adj',
+                                       quiet=said)
+        elif 'adj_time' in f or 'train_adj_time' in f:
+            raise ValueError("edge times need a sparse adjacency")
         else:
             self.adj = f['adj']
             self.train_adj = f['train_adj']
@@ -267,17 +313,24 @@ class NodeProblem(object):
 
     @classmethod
     def from_arrays(cls, task, n_classes, adj, train_adj, feats, folds, targets, cuda=True, adj_weight=None,
-                    train_adj_weight=None):
+                    train_adj_weight=None, adj_time=None, train_adj_time=None, node_time=None):
         """The same object from arrays already in memory (the keys of utils/convert.py:192-202): adj / train_adj a
         scipy csr_matrix in the (v, r, c) convention (sparse problems) or an int array [n + 1, K] (dense), feats a
         float array / FeatureStore / None.  What bench.py's CLI measurements and the tests use instead of writing a
         multi-GB problem file first; everything downstream of the loader is the code path of `NodeProblem(path)`.
-        adj_weight / train_adj_weight (sparse problems): edge weights as store.WeightedAdj takes them."""
+        adj_weight / train_adj_weight (sparse problems): edge weights as store.WeightedAdj takes them.
+        adj_time / train_adj_time (sparse problems): int64 edge times as store.TemporalAdj takes them; node_time: int64
+        [n_nodes], the seeds' default query times.  With both weights and times a problem is temporal."""
         self = object.__new__(cls)
         self.task, self.n_classes = str(task), int(n_classes) if n_classes is not None else 1
         self.feats, self.folds, self.targets = feats, np.asarray(folds), targets
-        self.adj = adj if adj_weight is None else WeightedAdj(adj, adj_weight)
-        self.train_adj = train_adj if train_adj_weight is None else WeightedAdj(train_adj, train_adj_weight)
+        self.node_time = np.asarray(node_time) if node_time is not None else None
+        self.adj = adj if adj_weight is None or adj_time is not None else WeightedAdj(adj, adj_weight)
+        self.train_adj = train_adj if train_adj_weight is None or train_adj_time is not None \
+            else WeightedAdj(train_adj, train_adj_weight)
+        self.adj = _temporal(self.adj, adj_time, self.node_time, weight=adj_weight, key='adj')
+        self.train_adj = _temporal(self.train_adj, train_adj_time, self.node_time, weight=train_adj_weight,
+                                   key='train_adj', quiet=adj_weight is not None and adj_time is not None)
         self.feats_dim = feats.shape[1] if feats is not None else None
         self.n_nodes = self.adj.shape[0]
         self.cuda = cuda

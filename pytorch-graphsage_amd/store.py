@@ -8,6 +8,9 @@ store.py -- HBM-resident data layouts of the hot path.
                 uint64 per stored edge (include/gsage.h, "Weighted adjacency"), built by with_weights().
   WeightedAdj   the reference-convention scipy matrix plus one fp32 weight per stored edge: what a
                 weighted problem hands to the samplers in place of the bare matrix.
+  TemporalAdj   the reference-convention scipy matrix plus one int64 time per stored edge, rows reordered by
+                time: what a temporal problem hands to the samplers.  DeviceCSR.with_times() carries the times
+                (`etime`), DeviceCSR.snapshot(t) is the graph of the edges before t.
   FeatureStore  the node-feature table feats[N+1, D] (problem.py:118-121) kept in HBM as a
                 row-major [n_rows, ld] matrix, bf16 (default on GPU) or fp32, rows padded with zeros
                 to a multiple of 128 bytes so every row is a whole number of cache lines and
@@ -101,13 +104,63 @@ class WeightedAdj(object):
         return self.adj.shape
 
 
+INT64_MAX = (1 << 63) - 1
+
+
+class TemporalAdj(object):
+    """A sparse adjacency in the reference's convention with one int64 time per stored edge (include/gsage.h,
+    "Temporal neighbours").  `time`: a scipy matrix with the structure of `adj` whose data are the times, or a flat
+    array aligned with the data of `adj` in canonical (row-major, sorted-column) order, as WeightedAdj aligns weights;
+    anything else, a time that is not an integer and a time equal to INT64_MAX are a ValueError.  On the host every row
+    is reordered by time -- stably: edges of one time keep their order -- and its columns re-issued as 0..deg-1, so
+    afterwards `.adj` is in time order (still in the reference's convention) and `.time` is aligned with its data.
+    node_time: int64 [n_rows] or None, the default query time of a seed (None: INT64_MAX, the whole row).  Forwards
+    `.shape`; the temporal sampler reads `.adj`, `.time` and `.node_time`, every other sampler `.adj` alone."""
+
+    def __init__(self, adj, time, node_time=None):
+        from scipy import sparse
+        if not sparse.issparse(adj):
+            raise ValueError("TemporalAdj: the adjacency must be a scipy sparse matrix")
+        adj = _canonical_csr(adj)
+        if sparse.issparse(time):
+            tm = _canonical_csr(time)
+            if tm.shape[0] != adj.shape[0] or not np.array_equal(tm.indptr, adj.indptr) or \
+                    not np.array_equal(tm.indices, adj.indices):
+                raise ValueError("TemporalAdj: the time matrix does not have the adjacency's structure")
+            time = tm.data
+        time = np.asarray(time)
+        if time.ndim != 1 or time.shape[0] != adj.nnz:
+            raise ValueError("TemporalAdj: %s times for %d stored edges" % (time.shape, adj.nnz))
+        if time.dtype.kind not in "iu":
+            raise ValueError("TemporalAdj: edge times must be integers (int64), not %s" % time.dtype)
+        if time.size and int(time.max()) >= INT64_MAX:
+            raise ValueError("TemporalAdj: edge times must be below INT64_MAX (the query time that sees every edge)")
+        time = np.ascontiguousarray(time, dtype=np.int64)
+        indptr = np.asarray(adj.indptr, dtype=np.int64)
+        rows = np.repeat(np.arange(adj.shape[0], dtype=np.int64), np.diff(indptr))
+        order = np.lexsort((time, rows))                   # by row, then by time; lexsort is stable
+        self.adj = sparse.csr_matrix((np.asarray(adj.data)[order], row_positions(indptr), indptr), shape=adj.shape)
+        self.time = time[order]
+        if node_time is not None:
+            node_time = np.asarray(node_time)
+            if node_time.ndim != 1 or node_time.shape[0] != adj.shape[0] or node_time.dtype.kind not in "iu":
+                raise ValueError("TemporalAdj: node_time must be int64 [%d] (one query time per row)" % adj.shape[0])
+            node_time = np.ascontiguousarray(node_time, dtype=np.int64)
+        self.node_time = node_time
+
+    @property
+    def shape(self):
+        return self.adj.shape
+
+
 class DeviceCSR(object):
-    def __init__(self, rowptr, col, n_rows, max_deg, edge_cdf=None):
+    def __init__(self, rowptr, col, n_rows, max_deg, edge_cdf=None, etime=None):
         self.rowptr = rowptr          # int64 [n_rows + 1]
         self.col = col                # int32 [nnz]
         self.n_rows = int(n_rows)     # adj.shape[0]  (counts the dummy row)
         self.max_deg = int(max_deg)   # adj.shape[1]: the population `sel` is drawn from
         self.edge_cdf = edge_cdf      # weighted: int64 [nnz] holding the uint64 bits of the per-row running sums
+        self.etime = etime            # temporal: int64 [nnz], non-decreasing inside every row (with_times)
         self.err_flag = torch.zeros(1, dtype=torch.int32, device=rowptr.device)
 
     @property
@@ -131,6 +184,40 @@ class DeviceCSR(object):
             raise ValueError("with_weights: edge weights must be finite and >= 0")
         self.edge_cdf = ops.edge_cdf(self.rowptr, w, self.n_rows)
         return self
+
+    def with_times(self, etime):
+        """Make this adjacency temporal: etime = one int64 per stored edge, aligned with `col`, non-decreasing inside
+        every row and below INT64_MAX (ValueError otherwise -- checked here, once, by reductions on the adjacency's
+        device).  Sets `.etime` and returns self."""
+        t = torch.as_tensor(etime)
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError("with_times: edge times must be integers (int64), not %s" % t.dtype)
+        t = t.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
+        if int(t.shape[0]) != self.nnz:
+            raise ValueError("with_times: %d times for %d stored edges" % (int(t.shape[0]), self.nnz))
+        if t.numel():
+            if int(t.max()) >= INT64_MAX:
+                raise ValueError("with_times: edge times must be below INT64_MAX (the query time that sees every edge)")
+            if t.numel() > 1:
+                down = t[1:] < t[:-1]                      # a step down is allowed only where a new row begins
+                first = torch.zeros(self.nnz + 1, dtype=torch.bool, device=self.device)
+                first[self.rowptr] = True
+                if bool((down & ~first[1:self.nnz]).any()):
+                    raise ValueError("with_times: the edges of a row are not in time order (store.TemporalAdj reorders "
+                                     "the rows of a scipy adjacency by time)")
+        self.etime = t
+        return self
+
+    def snapshot(self, t):
+        """The graph "as of t": a new DeviceCSR over the same n_rows (max_deg unchanged, `.etime` kept) holding exactly
+        the edges with etime < t -- the first cnt positions of every row.  Built on the device by
+        gsage_temporal_count, one torch.cumsum and gsage_temporal_compact; on the CPU the same definition in numpy.
+        Full-neighbourhood inference, closures, propagation, retrieval and ranking take it as any adjacency."""
+        from . import ops
+        if self.etime is None:
+            raise ValueError("snapshot: the adjacency carries no edge times (DeviceCSR.with_times)")
+        rowptr, col, etime = ops.temporal_snapshot(self, int(t))
+        return DeviceCSR(rowptr, col, self.n_rows, self.max_deg, etime=etime)
 
     def _importance_rows(self, n_walks, walk_len, top, seed, chunk, p=1.0, q=1.0, restart=0.0):
         """(rowptr int64 [n_rows + 1], col int32 [nnz], counts fp32 [nnz]) of importance(), on this adjacency's device"""
@@ -176,6 +263,10 @@ class DeviceCSR(object):
         from scipy import sparse
         if isinstance(adj, WeightedAdj):
             adj = adj.adj
+        if isinstance(adj, TemporalAdj):          # its rows are in time order already: the times ride along
+            if weight is not None:
+                raise ValueError("DeviceCSR.from_scipy: weights and times together are not supported")
+            return DeviceCSR.from_scipy(adj.adj, device).with_times(adj.time)
         if weight is not None:
             wadj = WeightedAdj(adj, weight)
             return DeviceCSR.from_scipy(wadj.adj, device).with_weights(wadj.weight)

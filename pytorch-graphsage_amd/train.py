@@ -131,6 +131,14 @@ engine does not cover is an error with its sentence.  --unsupervised runs on the
 the frontier; --engine fused exits with the unsupervised engine's sentence); --importance-walks is refused (that run is
 a weighted one).
 
+--sampler-class sparse_temporal_neighbor_sampler [--temporal-strategy uniform|recent] [--temporal-inherit seed|edge]:
+neighbours drawn among the edges that happened strictly BEFORE the seed's query time (a problem file with `adj_time` /
+`train_adj_time`, int64, and optionally `node_time`, the seeds' query times; include/gsage.h, "Temporal neighbours").
+Always Philox; the module path runs it (--engine auto says so; --engine fused is refused: no engine covers the sampler).
+Refused with a sentence: a problem without edge times, a dense problem, --unsupervised (the walks are not temporal) and
+--importance-walks.  --eval-as-of T: --full-neighbour-eval, --save-embeddings and the exports built on the embeddings
+run over the snapshot of the evaluation adjacency as of T (store.DeviceCSR.snapshot: the edges with time < T).
+
 --weighted-walks (default off: nothing changes; with --unsupervised and the weighted sampler, asked for by name or
 reached through --importance-walks): the positives' random walks draw every step in proportion to the edge weights
 (models.GSUnsupervised(weighted_walks=True), gsage_unsup_batch_weighted), on the training graph and -- in the
@@ -233,17 +241,41 @@ def full_neighbour_evaluate(model, problem, mode='val', closure=False):
     nodes = problem.nodes[mode]
     _, acts = problem._batch(nodes, problem.targets[nodes])
     dev = problem.feats.device
-    preds = gs.full_neighbour(model, problem.feats, nodes=torch.from_numpy(nodes).to(dev), closure=closure)
+    preds = gs.full_neighbour(model, problem.feats, nodes=torch.from_numpy(nodes).to(dev), closure=closure,
+                              adj=as_of_adj(problem))
     return batch_metric(problem.task, acts.reshape(acts.shape[0], -1), preds)
+
+
+def as_of_adj(problem):
+    """--eval-as-of T: the snapshot of the evaluation adjacency that full-neighbourhood evaluation and the embedding
+    pass run over (set_as_of), or None: the adjacency evaluation samples from."""
+    return getattr(problem, "_as_of_adj", None)
+
+
+def set_as_of(args, problem):
+    """--eval-as-of T: build snapshot(T) of the evaluation adjacency once, on the device of the feature table."""
+    if not isinstance(problem.adj, gs.store.TemporalAdj):
+        raise SystemExit('gsage: --eval-as-of: this problem has no edge times (adj_time) to take a snapshot by')
+    if not (args.full_neighbour_eval or args.save_embeddings or args.save_neighbours or args.link_eval or args.probe
+            or args.cluster):
+        raise SystemExit('gsage: --eval-as-of goes with --full-neighbour-eval, --save-embeddings or an export built on '
+                         'the embeddings (the sampled evaluation takes its times from node_time)')
+    if args.correct_smooth:
+        raise SystemExit('gsage: --eval-as-of: --correct-smooth propagates over every stored edge and is not covered')
+    dev = torch.device('cuda' if args.cuda else 'cpu')
+    full = gs.DeviceCSR.from_scipy(problem.adj, dev)
+    problem._as_of_adj = full.snapshot(args.eval_as_of)
+    print('gsage: --eval-as-of %d: full-neighbourhood evaluation and the embedding pass run over %d of the %d '
+          'evaluation edges' % (args.eval_as_of, problem._as_of_adj.nnz, full.nnz), file=sys.stderr)
 
 
 def save_embeddings(model, problem, path, nodes=None):
     """F.normalize(H^L) of every row, node-id order, one .npy; nodes (--embed-nodes): of these rows only, in their order."""
     if nodes is not None:
         ids = torch.from_numpy(np.asarray(np.load(nodes), dtype=np.int64).reshape(-1)).to(problem.feats.device)
-        np.save(path, gs.infer.query_embeddings(model, problem.feats, ids).cpu().numpy())
+        np.save(path, gs.infer.query_embeddings(model, problem.feats, ids, adj=as_of_adj(problem)).cpu().numpy())
         return
-    np.save(path, gs.embeddings(model, problem.feats).cpu().numpy())
+    np.save(path, gs.embeddings(model, problem.feats, adj=as_of_adj(problem)).cpu().numpy())
 
 
 def link_eval(model, problem, args, emb):
@@ -340,11 +372,11 @@ def export(model, problem, args):
         if args.embed_nodes:
             save_embeddings(model, problem, args.save_embeddings, args.embed_nodes)
         else:
-            emb = gs.embeddings(model, problem.feats)
+            emb = gs.embeddings(model, problem.feats, adj=as_of_adj(problem))
             np.save(args.save_embeddings, emb.cpu().numpy())
     if args.save_neighbours:
         if emb is None:
-            emb = gs.embeddings(model, problem.feats)
+            emb = gs.embeddings(model, problem.feats, adj=as_of_adj(problem))
         nodes = None
         if args.neighbour_nodes:
             nodes = torch.from_numpy(np.asarray(np.load(args.neighbour_nodes), dtype=np.int64).reshape(-1))
@@ -356,7 +388,7 @@ def export(model, problem, args):
         with open(args.save_neighbours, 'wb') as f:
             np.savez(f, ids=ids.cpu().numpy(), scores=scores.cpu().numpy())
     if args.link_eval or args.probe or args.cluster:
-        emb = emb if emb is not None else gs.embeddings(model, problem.feats)
+        emb = emb if emb is not None else gs.embeddings(model, problem.feats, adj=as_of_adj(problem))
     if args.link_eval:
         link_eval(model, problem, args, emb)
     if args.probe:
@@ -519,6 +551,15 @@ def parse_args(argv=None):
     parser.add_argument('--importance-q', type=float, default=1.0)
     parser.add_argument('--importance-restart', type=float, default=0.0,
                         help='with --importance-walks: probability in [0, 1) that a step puts the walk back on its node')
+    parser.add_argument('--temporal-strategy', type=str, default=None, choices=['uniform', 'recent'],
+                        help='with --sampler-class sparse_temporal_neighbor_sampler: draw uniformly among the edges '
+                             'before the query time (default), or take the most recent ones')
+    parser.add_argument('--temporal-inherit', type=str, default=None, choices=['seed', 'edge'],
+                        help='with the temporal sampler: the next hop looks before the seed\'s time (default) or before '
+                             'the time of the edge just walked')
+    parser.add_argument('--eval-as-of', type=int, default=None,
+                        help='--full-neighbour-eval, --save-embeddings and the exports built on them run over the '
+                             'snapshot of the evaluation adjacency as of this time (edges with time < T)')
 
     args = parser.parse_args(argv)
     args.cuda = not args.no_cuda
@@ -559,6 +600,36 @@ def importance_graphs(args, problem):
           'edges, %d evaluation edges, %.2f s on %s)' % (args.importance_walks, args.importance_len, args.importance_top,
                                                          problem.train_adj.adj.nnz, problem.adj.adj.nnz, time() - t0,
                                                          device.type), file=sys.stderr)
+
+
+TEMPORAL = 'sparse_temporal_neighbor_sampler'
+
+
+def temporal_checks(args, problem):
+    """--sampler-class sparse_temporal_neighbor_sampler: one sentence for each thing it does not cover, and the class-wide
+    strategy / inheritance rule of the run."""
+    if args.sampler_class != TEMPORAL:
+        if args.temporal_strategy is not None or args.temporal_inherit is not None:
+            raise SystemExit('gsage: --temporal-strategy / --temporal-inherit: they belong to the temporal sampler '
+                             '(--sampler-class %s), not %s' % (TEMPORAL, args.sampler_class))
+        return
+    who = 'gsage: --sampler-class %s' % TEMPORAL
+    if not gs.problem._is_sparse(problem.adj):
+        raise SystemExit('%s: edge times need the stored edges of a sparse problem, not the dense sampler\'s pre-sampled '
+                         'table' % who)
+    if not (isinstance(problem.adj, gs.store.TemporalAdj) and isinstance(problem.train_adj, gs.store.TemporalAdj)):
+        raise SystemExit('%s: this problem has no edge times (adj_time / train_adj_time)' % who)
+    if args.unsupervised:
+        raise SystemExit('%s: --unsupervised is not supported (the random walks are not temporal: their positives would '
+                         'come from the future)' % who)
+    if args.importance_walks:
+        raise SystemExit('%s: --importance-walks is not supported (the walks are not temporal, and the rebuilt adjacency '
+                         'carries no edge times)' % who)
+    if args.engine == 'fused':
+        raise SystemExit('%s: --engine fused: no fused engine covers the temporal sampler (use --engine auto / eager)' % who)
+    cls = gs.nn_modules.SparseTemporalNeighborSampler
+    cls.strategy_default = args.temporal_strategy or 'uniform'
+    cls.inherit_default = args.temporal_inherit or 'seed'
 
 
 def build_model(args, problem):
@@ -654,8 +725,11 @@ def main(argv=None, problem=None):
         raise SystemExit('gsage: --probe: a linear probe is a classifier; this problem\'s task is %s' % problem.task)
     if args.link_eval and not gs.problem._is_sparse(problem.adj):
         raise SystemExit('gsage: --link-eval: a dense problem file holds neighbour samples, not edges to hold out')
+    temporal_checks(args, problem)
     if args.importance_walks:
         importance_graphs(args, problem)
+    if args.eval_as_of is not None:
+        set_as_of(args, problem)
     if args.correct_smooth:
         if problem.task not in ('classification', 'multilabel_classification'):
             raise SystemExit('gsage: --correct-smooth: labels are propagated as class scores; this problem\'s task is %s'
@@ -839,6 +913,8 @@ def choose_engine(args, problem, model, ddp):
         if nodes.shape[0] // (nodes.shape[0] // args.batch_size + 1) < 2:
             return give_up('chunks of fewer than two training nodes')
         return cls
+    if isinstance(model.train_sampler, gs.nn_modules.SparseTemporalNeighborSampler):
+        return give_up('no fused engine covers the temporal sampler (SparseTemporalNeighborSampler)')
     own = [(what, scls, cls) for what, scls, cls in
            (('weighted', gs.nn_modules.SparseWeightedNeighborSampler, gs.engine.FusedWeightedMeanTrainStep),
             ('distinct', gs.nn_modules.SparseDistinctNeighborSampler, gs.engine.FusedDistinctMeanTrainStep))
