@@ -586,7 +586,12 @@ int gsage_attn_bwd(const float *g, int64_t g_ld, const float *ws, const float *n
  *             W0 / W2: the bf16 operand copies of att.0.weight [32, ldw0 >= 32 ceil(D / 32)] and att.2.weight [32, ldw2]
  *   backward  dws = <row, g_parent>, ds = ws (dws - sum ws dws); dxa[parent] = sum_j ds_j na_j (fp32 [M, dxa_ld]);
  *             da = bf16(ds xa_parent) [M n, da_ld]; dhid = bf16((da W2)(1 - hid^2)) [M n, dhid_ld] -- the rows of a
- *             LAST hop are nobody's parents, so da has no second term.  W2T[k][h] = W2[h][k]: transposed operand copy */
+ *             LAST hop are nobody's parents, so da has no second term.  W2T[k][h] = W2[h][k]: transposed operand copy
+ * Pad columns.  The kernels run KS = 1, 2, 4, 8, 19 or 20 steps of 32 columns, the first of these >= ceil(D / 32), and
+ * read cols = 32 KS columns of every row whatever D is: ld, ldw0, g_ld and lp_ld must be >= cols (gsage_attn_fused_ok
+ * checks ld: D = 129..192 needs ld >= 256, D = 257..608 needs ld >= 608).  The columns [D, cols) of the table rows and
+ * of W0 must be ZERO; those of g may hold anything finite (they meet the rows' zeros); agg_lp gets zeros there, and its
+ * columns >= cols, like the columns >= 32 of hid, a, da, dhid and dxa, are not written. */
 int gsage_attn_fused_ok(int dtype, int64_t ld, int64_t D, int32_t n, int64_t Ha);
 int gsage_attn_fused_fwd(const void *table, int dtype, int64_t ld, const int64_t *ids, int64_t row0, const void *W0,
                          int64_t ldw0, const void *W2, int64_t ldw2, const float *xa, int64_t xa_ld, int64_t M,
