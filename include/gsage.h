@@ -1310,6 +1310,31 @@ int gsage_sample_hops_distinct(const gsage_hops_desc *hops, void *stream);
  * All three: a null pointer, a negative size, n < 1, an unknown strategy or rule give GSAGE_EINVAL without a launch,
  * the message naming the argument; M == 0 (n_rows == 0 for the compaction) returns GSAGE_OK without one.  All three
  * can be recorded in a command list.
+ *
+ * gsage_sample_hops_temporal -- every hop of a temporal frontier in ONE launch: gsage_sample_hops' descriptor, geometry
+ * (a 256-lane workgroup walks the sub-tree of its seeds, the previous hop in LDS) and queue fields, with the times
+ * travelling beside the ids.  gsage_hops_desc is unchanged: etime, times, time_queue and out_times are arguments of their
+ * own (as cdf is for gsage_sample_hops_weighted).
+ *     frontier    hops->ids is the usual buffer [hop 0 (B) | hop 1 (B * fan[0]) | ...]
+ *     out_times   may be NULL; when given: int64 of the same layout, receives every entry's query time, hop 0 included
+ *     hop 0       without hops->seed_queue its times are times[i] (int64 [B], device): times must not be NULL and
+ *                 time_queue must be NULL.  With hops->seed_queue, batch b = (*batch_idx + batch_base) % n_batches supplies
+ *                 the seeds (as in gsage_sample_hops: published as hop 0 of ids) and time_queue[b * B + i] (int64
+ *                 [n_batches, B]) their times (published as hop 0 of out_times when it is given): time_queue must not be
+ *                 NULL, times is ignored
+ *     hop k       k = 1 .. n_hops: exactly one gsage_sample_csr_temporal call with ids = hop k-1's ids, times = hop k-1's
+ *                 times, n = fan[k-1], the given strategy and inheritance rule, call index
+ *                 call_base + (call_ctr ? *call_ctr : 0) + (k - 1) and g0 = rank * |hop k|
+ * -- the frontier and its times are bit-identical to n_hops launches of the per-hop entry: the strict signed 64-bit
+ * comparison, cnt == 0 giving the dummy 0 with the parent's time, a parent outside [0, n_rows) giving 0 with its time and
+ * setting *err_flag, the >= 2^32 row rule, the key tag 0x54 and the word addressing w(g).  max_deg is ignored.
+ * A hop runs in two phases: teams of 16 lanes count (one search per parent, however many samples it takes), then one
+ * lane per sample draws.  LDS: 44 bytes per id of the widest hop of a workgroup's seeds (ids and times, each in two
+ * ping-pong buffers, and a parent's first edge and count), at most 160 KiB.
+ * GSAGE_EINVAL without a launch (and without a GPU), the message naming the argument: hops == NULL; etime == NULL;
+ * rowptr / col / ids NULL; sel != NULL; dense_adj != NULL; n_hops outside 1..5; a fan-out < 1; an unknown strategy or
+ * rule; times / time_queue not matching the presence of seed_queue as above; a frontier that does not fit the LDS.
+ * B == 0 returns GSAGE_OK without a launch.  The entry can be recorded in a command list.
  * ---------------------------------------------------------------------------------------- */
 #define GSAGE_TEMPORAL_UNIFORM 0
 #define GSAGE_TEMPORAL_RECENT 1
@@ -1319,6 +1344,9 @@ int gsage_sample_csr_temporal(const int64_t *rowptr, const int32_t *col, const i
                               const int64_t *ids, const int64_t *times, int64_t M, int32_t n, int32_t strategy,
                               int32_t inherit, uint64_t seed, const uint64_t *call_ctr, uint64_t call_base, uint64_t g0,
                               int64_t *out, int64_t *out_time, int32_t *err_flag, void *stream);
+int gsage_sample_hops_temporal(const gsage_hops_desc *hops, const int64_t *etime, const int64_t *times,
+                               const int64_t *time_queue, int32_t strategy, int32_t inherit, int64_t *out_times,
+                               void *stream);
 int gsage_temporal_count(const int64_t *rowptr, const int64_t *etime, int64_t n_rows, const int64_t *ids, int64_t M,
                          const int64_t *times, int64_t t, int64_t *cnt, int32_t *err_flag, void *stream);
 int gsage_temporal_compact(const int64_t *rowptr, const int32_t *col, const int64_t *etime, int64_t n_rows,

@@ -199,6 +199,7 @@ SIGNATURES = {
     "gsage_sample_hops_distinct": (_int, [_vp, _vp]),
     "gsage_sample_csr_temporal": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _u64, _vp, _u64, _u64, _vp,
                                          _vp, _vp, _vp]),
+    "gsage_sample_hops_temporal": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "gsage_temporal_count": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "gsage_temporal_compact": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gsage_segment_reduce_weighted": (_int, [_vp, _int, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,

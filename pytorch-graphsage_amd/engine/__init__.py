@@ -21,6 +21,10 @@ engine -- the whole train_step (reference models.py:97-104) as recorded launches
                                replacement by one sampler launch of its own (gsage_sample_hops_distinct), everything
                                behind it the mean engine's (opt-in: train.py --engine fused with the distinct sampler;
                                not one of ENGINES)
+  temporal.FusedTemporalMeanTrainStep  the mean engine over the temporal sampler: every hop drawn among the edges before
+                               the query time by one sampler launch of its own (gsage_sample_hops_temporal), the seeds'
+                               query times per call, from the epoch queue and in evaluation; everything behind it the
+                               mean engine's (opt-in: train.py --engine fused with the temporal sampler; not one of ENGINES)
 
 `fused_engine_for(model, feats)` picks the engine that covers a model, or explains why none does.
 """
@@ -34,6 +38,7 @@ from .attn import FusedAttnTrainStep
 from .unsup import FusedUnsupMeanTrainStep, FusedUnsupWeightedMeanTrainStep   # noqa: F401
 from .weighted import FusedWeightedMeanTrainStep             # noqa: F401
 from .distinct import FusedDistinctMeanTrainStep             # noqa: F401
+from .temporal import FusedTemporalMeanTrainStep             # noqa: F401
 
 ENGINES = (FusedMeanTrainStep, FusedPoolTrainStep, FusedAttnTrainStep)
 

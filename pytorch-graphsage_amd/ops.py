@@ -648,6 +648,61 @@ def sample_csr_temporal(csr, ids, times, n, philox, strategy="uniform", inherit=
     return torch.from_numpy(vals), torch.from_numpy(np.ascontiguousarray(keep, dtype=np.int64))
 
 
+def sample_hops_temporal(csr, ids, times, B, fans, philox, strategy="uniform", inherit="seed", out_times=None):
+    """Every hop of a temporal frontier (include/gsage.h, gsage_sample_hops_temporal: one launch): ids is the
+    concatenated buffer [hop 0 | hop 1 | ... | hop L] (int64, B (1 + n1 + n1 n2 + ...) entries) with hop 0 filled, times
+    int64 [B] the seeds' query times on the ids' device; hop k is written as sample_csr_temporal(hop k - 1 and its times,
+    fans[k - 1]) under call index call_base + k - 1 and g0 = rank * |hop k|.  out_times (optional): int64 of ids' layout,
+    receives every entry's query time, hop 0 included; allocated when None.  philox: dict(seed, call_base, call_ctr,
+    optional rank).  Returns (ids, out_times).  CPU tensors: the host definition of the per-hop draw, hop after hop
+    (host mode)."""
+    _temporal_csr(csr, "sample_hops_temporal")
+    if strategy not in TEMPORAL_STRATEGIES:
+        raise ValueError("sample_hops_temporal: unknown strategy %r (known: uniform, recent)" % (strategy,))
+    if inherit not in TEMPORAL_INHERIT:
+        raise ValueError("sample_hops_temporal: unknown inherit rule %r (known: seed, edge)" % (inherit,))
+    fans = [int(n) for n in fans]
+    assert 1 <= len(fans) <= 5 and all(n >= 1 for n in fans), "sample_hops_temporal: 1..5 hops of n_samples >= 1"
+    B = int(B)
+    sizes = [B]
+    for n in fans:
+        sizes.append(sizes[-1] * n)
+    assert ids.dtype == torch.int64 and ids.dim() == 1 and ids.is_contiguous() and ids.numel() == sum(sizes)
+    times = times.contiguous().view(-1)
+    assert times.dtype == torch.int64 and int(times.shape[0]) == B and times.device == ids.device, \
+        "sample_hops_temporal: times must be int64 [B] on the ids' device"
+    if out_times is None:
+        out_times = torch.empty_like(ids)
+    assert out_times.dtype == torch.int64 and out_times.numel() == ids.numel() and out_times.is_contiguous() and \
+        out_times.device == ids.device, "sample_hops_temporal: out_times must be int64 of ids' layout on its device"
+    seed, base, rank = int(philox["seed"]), int(philox.get("call_base", 0)), int(philox.get("rank", 0))
+    ctr = philox.get("call_ctr")
+    if ids.is_cuda:
+        d = nat.HopsDesc()
+        d.rowptr, d.col, d.n_rows = csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.n_rows
+        d.ids, d.B, d.n_hops = ids.data_ptr(), B, len(fans)
+        for k in range(5):
+            d.fan[k] = fans[k] if k < len(fans) else 1
+        d.max_deg, d.seed, d.call_base, d.rank = 1, seed, base, rank
+        d.call_ctr = ctr.data_ptr() if ctr is not None else None
+        d.err_flag = csr.err_flag.data_ptr()
+        nat.check(nat.lib().gsage_sample_hops_temporal(ctypes.addressof(d), _ptr(csr.etime), _ptr(times), None,
+                                                       TEMPORAL_STRATEGIES[strategy], TEMPORAL_INHERIT[inherit],
+                                                       _ptr(out_times), _stream()), "sample_hops_temporal")
+        return ids, out_times
+    off = 0
+    out_times[:B] = times
+    for k, n in enumerate(fans):
+        ph = {"seed": seed, "call_base": base + k, "g0": rank * sizes[k + 1]}
+        if ctr is not None:
+            ph["call_ctr"] = ctr
+        lo, hi = off + sizes[k], off + sizes[k] + sizes[k + 1]
+        ids[lo:hi], out_times[lo:hi] = sample_csr_temporal(csr, ids[off:lo], out_times[off:lo], n, ph,
+                                                           strategy=strategy, inherit=inherit)
+        off += sizes[k]
+    return ids, out_times
+
+
 def temporal_count(csr, ids=None, times=None, t=None):
     """cnt int64 [M] (include/gsage.h, gsage_temporal_count): per row ids[i] -- every row of the graph when ids is
     None -- the number of edges with etime < times[i], or < the one scalar t when times is None.  One launch, the hop

@@ -134,7 +134,12 @@ a weighted one).
 --sampler-class sparse_temporal_neighbor_sampler [--temporal-strategy uniform|recent] [--temporal-inherit seed|edge]:
 neighbours drawn among the edges that happened strictly BEFORE the seed's query time (a problem file with `adj_time` /
 `train_adj_time`, int64, and optionally `node_time`, the seeds' query times; include/gsage.h, "Temporal neighbours").
-Always Philox; the module path runs it (--engine auto says so; --engine fused is refused: no engine covers the sampler).
+Always Philox.  Under --engine auto / eager the module path runs it (said on stderr, with the name of the engine --engine
+fused would select); --engine fused (opt-in, mean aggregators, the identity prep over a bf16 / fp32 table, one process,
+a GPU) runs training on engine.FusedTemporalMeanTrainStep -- the mean engine behind one sampler launch that draws every
+hop with the times beside the ids (gsage_sample_hops_temporal), queue mode included, the seeds' query times the
+problem's `node_time` as on the module path -- and the validation / test folds on the same class; what that engine does
+not cover is an error with its sentence.
 Refused with a sentence: a problem without edge times, a dense problem, --unsupervised (the walks are not temporal) and
 --importance-walks.  --eval-as-of T: --full-neighbour-eval, --save-embeddings and the exports built on the embeddings
 run over the snapshot of the evaluation adjacency as of T (store.DeviceCSR.snapshot: the edges with time < T).
@@ -498,7 +503,9 @@ def parse_args(argv=None):
                         help='auto: a fused engine where one covers the run, else the module path (said on stderr); '
                              'eager: the module path; fused: an engine or an error.  --unsupervised runs on the module '
                              'path unless --engine fused asks for FusedUnsupMeanTrainStep (needs --rng philox; with '
-                             '--weighted-walks: FusedUnsupWeightedMeanTrainStep)')
+                             '--weighted-walks: FusedUnsupWeightedMeanTrainStep).  The weighted, distinct and temporal '
+                             'samplers run on the module path unless --engine fused asks for their engine '
+                             '(FusedWeightedMeanTrainStep / FusedDistinctMeanTrainStep / FusedTemporalMeanTrainStep)')
     parser.add_argument('--feature-dtype', type=str, default='native', choices=['native', 'fp8'])
     parser.add_argument('--wide-head', action="store_true",
                         help='fuse the multilabel head (2..128 labels) and cross-entropy over 65..128 classes '
@@ -625,8 +632,8 @@ def temporal_checks(args, problem):
     if args.importance_walks:
         raise SystemExit('%s: --importance-walks is not supported (the walks are not temporal, and the rebuilt adjacency '
                          'carries no edge times)' % who)
-    if args.engine == 'fused':
-        raise SystemExit('%s: --engine fused: no fused engine covers the temporal sampler (use --engine auto / eager)' % who)
+    if args.engine == 'fused' and not args.cuda:       # (with a GPU: choose_engine builds FusedTemporalMeanTrainStep)
+        raise SystemExit('%s: --engine fused: no fused engine covers the temporal sampler without a GPU (--no-cuda)' % who)
     cls = gs.nn_modules.SparseTemporalNeighborSampler
     cls.strategy_default = args.temporal_strategy or 'uniform'
     cls.inherit_default = args.temporal_inherit or 'seed'
@@ -913,11 +920,10 @@ def choose_engine(args, problem, model, ddp):
         if nodes.shape[0] // (nodes.shape[0] // args.batch_size + 1) < 2:
             return give_up('chunks of fewer than two training nodes')
         return cls
-    if isinstance(model.train_sampler, gs.nn_modules.SparseTemporalNeighborSampler):
-        return give_up('no fused engine covers the temporal sampler (SparseTemporalNeighborSampler)')
     own = [(what, scls, cls) for what, scls, cls in
            (('weighted', gs.nn_modules.SparseWeightedNeighborSampler, gs.engine.FusedWeightedMeanTrainStep),
-            ('distinct', gs.nn_modules.SparseDistinctNeighborSampler, gs.engine.FusedDistinctMeanTrainStep))
+            ('distinct', gs.nn_modules.SparseDistinctNeighborSampler, gs.engine.FusedDistinctMeanTrainStep),
+            ('temporal', gs.nn_modules.SparseTemporalNeighborSampler, gs.engine.FusedTemporalMeanTrainStep))
            if isinstance(model.train_sampler, scls)]
     if own:
         what, scls, cls = own[0]                       # opt-in: --engine fused, or the module path
@@ -1020,7 +1026,8 @@ def train_fused(args, problem, model, ddp, start_time, cls):
     elif os.environ.get("GSAGE_FUSED_EVAL", "1") == "1":
         fold_eval = FusedEvaluator(cls, model, problem, wide_head=args.wide_head,
                                    strict=cls in (gs.engine.FusedWeightedMeanTrainStep,
-                                                  gs.engine.FusedDistinctMeanTrainStep)).prepare('val')
+                                                  gs.engine.FusedDistinctMeanTrainStep,
+                                                  gs.engine.FusedTemporalMeanTrainStep)).prepare('val')
     else:
         fold_eval = lambda mode='val': evaluate(model, problem, mode=mode)                     # noqa: E731
     # The per-batch line (train.py:150-158) without a host sync per step: batch b is scored on the device right behind
