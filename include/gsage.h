@@ -1354,6 +1354,50 @@ int gsage_temporal_compact(const int64_t *rowptr, const int32_t *col, const int6
                            int64_t out_nnz, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Temporal walks (csrc/gsage_unsup.hip): the unsupervised batch builder over a temporal CSR.  Additive; the ABI
+ * version is unchanged.  No reference counterpart.
+ *
+ * gsage_unsup_batch_temporal -- one launch.  The temporal CSR is the one of "Temporal neighbours" (rows in time order,
+ * every etime < INT64_MAX, rows shorter than 2^32).  seeds, times: int64 [B] on the device.  It writes
+ *     ids        int64 [2B + Q] = [seeds (B) | positives (B) | negatives (Q)]      pair_w  fp32 [B]
+ *     out_times  int64 [2B + Q]: the query time every row of ids is to be embedded at
+ * call, P(c, tag) and g = g0 + i are exactly those of "Unsupervised GraphSAGE".
+ *   Positive of seed i, v = seeds[i], tau = times[i]:
+ *     t_i  = 1 + ((P(g, 0x4C000000)[0] * walk_len) >> 32)       (the plain builder's length word: the same seed takes
+ *                                                                the same number of steps)
+ *     for j = 0 .. t_i - 1:
+ *              cnt  = the number of edges e of row v with etime[e] < tau          (strict, signed 64-bit: the sampler's
+ *                     count);   cnt == 0: the walk ends at v
+ *              word = P(g, 0x56000000 | (j >> 2))[j & 3]                           (a tag no other role uses)
+ *              off  = (word * cnt) >> 32;   v = col[beg + off]                     (64-bit product, beg = rowptr[v])
+ *              GSAGE_TEMPORAL_INHERIT_EDGE: tau = etime[beg + off] -- a time-respecting walk, the edge times strictly
+ *              decrease along it;   GSAGE_TEMPORAL_INHERIT_SEED: tau stays times[i]
+ *     ids[i] = seeds[i];  ids[B + i] = v;  pair_w[i] = (v == seeds[i]) ? 0 : 1     (a seed without history before its
+ *     time takes no positive loss);   out_times[i] = out_times[B + i] = times[i]   (both ends of a pair are embedded as
+ *     of the prediction time, under either rule)
+ *     An id outside [0, n_rows) -- a seed, or a node the walk reaches -- is treated as in gsage_unsup_batch:
+ *     ids[B + i] = 0, a bad seed also ids[i] = 0 and pair_w[i] = 0, *err_flag (may be NULL) is set; out_times keeps
+ *     times[i].  A row of 2^32 edges or more counts as cnt = 0 and sets the flag.
+ *   A walk always draws uniformly among the eligible edges: the sampler's strategy does not enter ("recent" would make
+ *   every walk the same path).
+ *   Negative q:  ids[2B + q] is gsage_unsup_batch's, bit for bit (tag 0x4E000000, the double table; g0 does not enter);
+ *     out_times[2B + q] = times[q % b],  b = clamp(*n_valid, 1, B)   (n_valid: device int32 word as in
+ *     gsage_head_skipgram_live, NULL: b = B) -- a batch padded to a recorded geometry gives its negatives the times the
+ *     unpadded batch gives them.  A stated compromise: the Q negatives are shared by all seeds, so a negative is seen
+ *     as of one of the batch's query times, not as of each seed's.
+ *   A team of 16 lanes carries a walk and finds cnt together (the sampler's search, csrc/gsage_temporal_dev.h); the
+ *   negatives take a lane each.  No LDS.
+ *   GSAGE_EINVAL without a launch, the message naming the argument: a null pointer (n_valid, call_ctr and err_flag
+ *   may be NULL), B outside [1, 2^31), Q < 1, walk_len outside 1..16, an unknown rule, a cdf_total that is not positive
+ *   or not finite.  The entry can be recorded in a command list.
+ * ---------------------------------------------------------------------------------------- */
+int gsage_unsup_batch_temporal(const int64_t *rowptr, const int32_t *col, const int64_t *etime, int64_t n_rows,
+                               const int64_t *seeds, const int64_t *times, int64_t B, int32_t walk_len, int64_t Q,
+                               const double *cdf, double cdf_total, uint64_t seed, const uint64_t *call_ctr,
+                               uint64_t call_base, uint64_t g0, int32_t inherit, const int32_t *n_valid, int64_t *ids,
+                               int64_t *out_times, float *pair_w, int32_t *err_flag, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Importance neighbourhoods (csrc/gsage_importance.hip): a node's most-visited nodes under short random walks become
  * its neighbourhood, the visit counts its edge weights (the construction PinSAGE introduced).  What turns ANY
  * adjacency into a weighted one for everything under "Weighted adjacency".  Additive; the ABI version is unchanged.

@@ -28,7 +28,9 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
     models.GSUnsupervised     label-free training: random-walk positives, degree^0.75 negatives, skip-gram head;
                               weighted_walks=True: over a weighted adjacency the walks draw every step by edge weight
                               (ops.unsup_batch(weighted=True), gsage_unsup_batch_weighted); walk_p=, walk_q=: node2vec's
-                              return / in-out parameters (ops.unsup_batch(p=, q=), gsage_unsup_batch_biased)
+                              return / in-out parameters (ops.unsup_batch(p=, q=), gsage_unsup_batch_biased);
+                              temporal_walks=True: over the temporal sampler the walks respect time and the query times
+                              travel with the batch (ops.unsup_batch_temporal, gsage_unsup_batch_temporal)
     nn_modules.SparseDistinctNeighborSampler   neighbours WITHOUT replacement (sparse_distinct_neighbor_sampler in
                               sampler_extensions; ops.sample_csr_distinct, csrc/gsage_distinct.hip): every neighbour of a
                               short row, n distinct ones of a long row
@@ -39,7 +41,7 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
     engine/                   the whole train_step as recorded launches (captured autograd path; fused mean /
                               pool / attention engines on a shared base; opt-in: the weighted mean engine, the
                               distinct-draw mean engine FusedDistinctMeanTrainStep and the unsupervised engines,
-                              FusedUnsupMeanTrainStep / FusedUnsupWeightedMeanTrainStep)
+                              FusedUnsupMeanTrainStep / FusedUnsupWeightedMeanTrainStep / FusedUnsupTemporalMeanTrainStep)
 """
 from . import _native, dist, engine, helpers, infer, nn_modules, ops, optim, problem, store        # noqa: F401
 from .helpers import set_seeds, to_numpy                            # noqa: F401

@@ -188,6 +188,8 @@ SIGNATURES = {
                                           _u64, _u64, _vp, _vp, _vp, _vp]),
     "gsage_unsup_batch_biased": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i64, _vp, ctypes.c_double, _u64, _vp,
                                         _u64, _u64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "gsage_unsup_batch_temporal": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i64, _vp, ctypes.c_double, _u64,
+                                          _vp, _u64, _u64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gsage_head_skipgram": (_int, [_vp, _i64, _i32, _i32, _i32, _vp, _f32, _vp, _int, _i64, _vp, _vp, _vp, _vp]),
     "gsage_head_skipgram_scratch": (_i64, [_i32, _i32, _i32]),
     "gsage_head_skipgram_live": (_int, [_vp, _i64, _i32, _i32, _i32, _vp, _f32, _vp, _vp, _int, _i64, _vp, _vp, _vp,

@@ -8,11 +8,16 @@
 // find the first table entry above its draw, and the 64 lanes probe 64 entries of the row per round trip -- one round
 // for a row of at most 64 edges, ceil(log64(deg)) for a longer one -- instead of a lane's log2(deg) dependent probes.
 //
+// The temporal builder (include/gsage.h, "Temporal walks": every step among the edges before the walk's time) gives a
+// walk to a TEAM of 16 lanes, the unit the temporal sampler's search is written for (gsage_temporal_dev.h): a step is the
+// row's extent, two to three dependent search rounds and the col load.
+//
 // The head is k_head_ce (gsage_head.hip) with the normalised negatives in the role of fc.weight and the loss
 // exchanged: B x Q x D = 512 x 20 x 256 is 2.6 MFLOP, so the cost is launches and dependent phases, not flops.  A
 // workgroup keeps its 16 normalised seed rows in LDS, streams the negatives' rows from L2 (64 x 1024 floats do not fit
 // beside them), and leaves one partial of d z_neg per workgroup for the second launch to sum in a fixed order.
 #include "gsage_common.h"
+#include "gsage_temporal_dev.h"
 #include "gsage_walk_dev.h"
 #include "gsage_weighted_dev.h"
 
@@ -23,6 +28,7 @@ constexpr uint32_t UNSUP_TAG_STEP = 0x53000000u;    // | (step >> 2): walk steps
 constexpr uint32_t UNSUP_TAG_NEG = 0x4E000000u;     // negatives
 constexpr uint32_t UNSUP_TAG_WSTEP = 0x5A000000u;   // | (step >> 1): weighted walk steps, two to a Philox block
 constexpr uint32_t UNSUP_TAG_BIAS = 0x42000000u;    // | (step << 8) | round: a biased step's rounds, a block each
+constexpr uint32_t UNSUP_TAG_TSTEP = 0x56000000u;   // | (step >> 2): temporal walk steps, four to a Philox block
 constexpr int UNSUP_WALK_MAX = 16;
 
 struct UnsupParams {
@@ -307,6 +313,85 @@ k_unsup_batch_biased(const UnsupBiasedParams bp)
         p.ids[p.B + i] = v;
         p.pair_w[i] = v == s ? 0.f : 1.f;
     }
+}
+
+// ---- temporal walks: a team of 16 lanes per walk ---------------------------------------------------------------------
+// include/gsage.h, "Temporal walks".  blocks [0, walk_blocks): a team per seed (sixteen to a workgroup, four to a wave);
+// the rest: a lane per negative.  A step's eligible edges are the first cnt of the row, cnt found by the team with
+// temporal_count (gsage_temporal_dev.h).  That search is WAVE-uniform around __ballot and the four walks of a wave have
+// different lengths and end early at different steps, so the step loop runs until no team of the wave walks any more
+// and a team that has finished passes deg = 0.  Every value a team steers by (v, tau, cnt, the Philox words) is
+// computed by all of its 16 lanes from team-uniform inputs; lane 0 of the team writes the walk's five words.
+struct UnsupTemporalParams {
+    UnsupParams u;
+    const int64_t *etime;
+    const int64_t *times;
+    const int32_t *n_valid;                             // live seeds (device word) or NULL: the negatives' times
+    int64_t *out_times;
+};
+
+template <int INHERIT>
+__global__ void __launch_bounds__(256)
+k_unsup_batch_temporal(const UnsupTemporalParams tp)
+{
+    const UnsupParams &p = tp.u;
+    const uint64_t call = p.call_base + (p.call_ctr ? *p.call_ctr : 0ull);
+    if ((int)blockIdx.x >= p.walk_blocks) {
+        unsup_negative(p, call);
+        const int64_t q = (int64_t)((int)blockIdx.x - p.walk_blocks) * 256 + threadIdx.x;
+        if (q < p.Q) {
+            const int64_t b = tp.n_valid ? (int64_t)min(max((int64_t)*tp.n_valid, (int64_t)1), p.B) : p.B;
+            tp.out_times[2 * p.B + q] = tp.times[q % b];
+        }
+        return;
+    }
+    const uint32_t team = threadIdx.x / TEAM, l = threadIdx.x & (TEAM - 1);
+    const int64_t i = (int64_t)blockIdx.x * (256 / TEAM) + team;
+    const bool live = i < p.B;
+    const int64_t s = live ? p.seeds[i] : 0;
+    const int64_t t0 = live ? tp.times[i] : 0;
+    const bool seed_ok = live && (uint64_t)s < (uint64_t)p.n_rows;
+    const uint64_t g = p.g0 + (uint64_t)i;
+    int steps = 0;
+    if (seed_ok) {
+        const uint32_t wl = unsup_philox(p, g, call, UNSUP_TAG_LEN).v[0];
+        steps = 1 + (int)(((uint64_t)wl * (uint64_t)(uint32_t)p.walk_len) >> 32);
+    }
+    int64_t v = s, tau = t0;
+    bool walking = seed_ok, bad = false;
+    philox4 r = {};
+    for (int j = 0; j < UNSUP_WALK_MAX; ++j) {
+        const bool act = walking && j < steps;
+        if (!__any(act)) break;                                 // (uniform over the wave: its longest live walk is done)
+        int64_t beg;
+        const uint32_t deg = temporal_row(p.rowptr, p.n_rows, act, v, beg, p.err_flag);
+        const uint32_t cnt = temporal_count(tp.etime, beg, deg, tau);            // every lane of the wave
+        if (act && cnt == 0) walking = false;                   // no edge before tau: the walk ends at v
+        if (act && cnt != 0) {
+            if ((j & 3) == 0) r = unsup_philox(p, g, call, UNSUP_TAG_TSTEP | (uint32_t)(j >> 2));
+            const int w4 = j & 3;                               // selects, not r.v[j & 3]: no scratch
+            const uint32_t word = w4 == 0 ? r.v[0] : w4 == 1 ? r.v[1] : w4 == 2 ? r.v[2] : r.v[3];
+            const int64_t e = beg + (int64_t)(((uint64_t)word * (uint64_t)cnt) >> 32);  // < beg + cnt <= the row's end
+            const int64_t x = (int64_t)p.col[e];
+            if (INHERIT == GSAGE_TEMPORAL_INHERIT_EDGE) tau = tp.etime[e];
+            if ((uint64_t)x >= (uint64_t)p.n_rows) {
+                bad = true;
+                walking = false;
+                v = 0;
+            } else {
+                v = x;
+            }
+        }
+    }
+    if (!live || l != 0) return;
+    if (!seed_ok || bad) {
+        if (p.err_flag) *p.err_flag = 1;
+    }
+    p.ids[i] = seed_ok ? s : 0;
+    p.ids[p.B + i] = seed_ok ? v : 0;
+    p.pair_w[i] = (!seed_ok || v == s) ? 0.f : 1.f;
+    tp.out_times[i] = t0;
+    tp.out_times[p.B + i] = t0;
 }
 
 // ---- skip-gram head ------------------------------------------------------------------------------------------------
@@ -681,6 +766,39 @@ int gsage_unsup_batch_biased(const int64_t *rowptr, const int32_t *col, const ui
     launch(k_unsup_batch_biased, dim3((unsigned)(u.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream,
            bp);
     return check_launch("unsup_batch_biased");
+}
+
+int gsage_unsup_batch_temporal(const int64_t *rowptr, const int32_t *col, const int64_t *etime, int64_t n_rows,
+                               const int64_t *seeds, const int64_t *times, int64_t B, int32_t walk_len, int64_t Q,
+                               const double *cdf, double cdf_total, uint64_t seed, const uint64_t *call_ctr,
+                               uint64_t call_base, uint64_t g0, int32_t inherit, const int32_t *n_valid, int64_t *ids,
+                               int64_t *out_times, float *pair_w, int32_t *err_flag, void *stream)
+{
+    GSAGE_REQUIRE(rowptr && col && etime, "unsup_batch_temporal: null pointer (rowptr, col, etime)");
+    GSAGE_REQUIRE(seeds && times, "unsup_batch_temporal: null pointer (seeds, times)");
+    GSAGE_REQUIRE(cdf, "unsup_batch_temporal: null pointer (cdf)");
+    GSAGE_REQUIRE(ids && out_times && pair_w, "unsup_batch_temporal: null pointer (ids, out_times, pair_w)");
+    GSAGE_REQUIRE(n_rows > 0, "unsup_batch_temporal: n_rows must be >= 1");
+    GSAGE_REQUIRE(B >= 1 && B < (1LL << 31), "unsup_batch_temporal: B must be in [1, 2^31)");
+    GSAGE_REQUIRE(Q >= 1 && Q < (1LL << 31), "unsup_batch_temporal: Q must be in [1, 2^31)");
+    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= UNSUP_WALK_MAX, "unsup_batch_temporal: walk_len must be in 1..%d",
+                  UNSUP_WALK_MAX);
+    GSAGE_REQUIRE(inherit == GSAGE_TEMPORAL_INHERIT_SEED || inherit == GSAGE_TEMPORAL_INHERIT_EDGE,
+                  "unsup_batch_temporal: unknown inherit rule %d (0: seed, 1: edge)", (int)inherit);
+    GSAGE_REQUIRE(cdf_total > 0.0 && cdf_total <= 1.7976931348623157e308,
+                  "unsup_batch_temporal: cdf_total, the sum of the negatives' weights, is %g (every row has weight 0?)",
+                  cdf_total);
+    UnsupTemporalParams tp;
+    UnsupParams &u = tp.u;
+    u.rowptr = rowptr; u.col = col; u.seeds = seeds; u.cdf = cdf; u.edge_cdf = nullptr; u.call_ctr = call_ctr;
+    u.ids = ids; u.pair_w = pair_w; u.err_flag = err_flag; u.n_rows = n_rows; u.B = B; u.Q = Q; u.call_base = call_base;
+    u.g0 = g0; u.cdf_total = cdf_total; u.seed_lo = (uint32_t)seed; u.seed_hi = (uint32_t)(seed >> 32);
+    u.walk_len = walk_len; u.walk_blocks = (int32_t)ceil_div(B, 256 / TEAM);     // a team per walk, sixteen to a workgroup
+    tp.etime = etime; tp.times = times; tp.n_valid = n_valid; tp.out_times = out_times;
+    auto kernel = inherit == GSAGE_TEMPORAL_INHERIT_EDGE ? k_unsup_batch_temporal<GSAGE_TEMPORAL_INHERIT_EDGE>
+                                                         : k_unsup_batch_temporal<GSAGE_TEMPORAL_INHERIT_SEED>;
+    launch(kernel, dim3((unsigned)(u.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream, tp);
+    return check_launch("unsup_batch_temporal");
 }
 
 int64_t gsage_head_skipgram_scratch(int32_t B, int32_t Q, int32_t D)

@@ -13,6 +13,10 @@ engine -- the whole train_step (reference models.py:97-104) as recorded launches
                                (gsage_unsup_batch_weighted) and every hop (gsage_sample_hops_weighted) drawn from the
                                per-edge cdf table (opt-in: train.py --unsupervised --weighted-walks --engine fused; not
                                one of ENGINES)
+  unsup.FusedUnsupTemporalMeanTrainStep  FusedUnsupMeanTrainStep over a temporal adjacency: walks that respect time
+                               (gsage_unsup_batch_temporal) and every hop drawn among the edges before the batch's
+                               query times (gsage_sample_hops_temporal) (opt-in: train.py --unsupervised --temporal-walks
+                               --engine fused; not one of ENGINES)
   weighted.FusedWeightedMeanTrainStep  the mean engine over a weighted adjacency: every hop drawn from the per-edge
                                cdf table by one sampler launch of its own (gsage_sample_hops_weighted), everything
                                behind it the mean engine's (opt-in: train.py --engine fused with the weighted sampler;
@@ -35,7 +39,7 @@ from .common import FusedTrainStep, _PrepDesc, _ReduceDesc   # noqa: F401
 from .mean import FusedMeanTrainStep
 from .pool import FusedPoolTrainStep
 from .attn import FusedAttnTrainStep
-from .unsup import FusedUnsupMeanTrainStep, FusedUnsupWeightedMeanTrainStep   # noqa: F401
+from .unsup import FusedUnsupMeanTrainStep, FusedUnsupTemporalMeanTrainStep, FusedUnsupWeightedMeanTrainStep   # noqa: F401
 from .weighted import FusedWeightedMeanTrainStep             # noqa: F401
 from .distinct import FusedDistinctMeanTrainStep             # noqa: F401
 from .temporal import FusedTemporalMeanTrainStep             # noqa: F401

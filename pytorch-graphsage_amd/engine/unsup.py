@@ -9,7 +9,10 @@ The encoder sees one batch of R = 2B + Q rows [seeds | positives | negatives]: t
 FusedUnsupWeightedMeanTrainStep: the same step over a weighted adjacency (GSUnsupervised(weighted_walks=True)): the
 builder's steps and every hop of the frontier are drawn from the adjacency's per-edge table.
 
-Both record gsage_unsup_batch_biased as their builder when the model's walk_p / walk_q are not neutral (include/gsage.h,
+FusedUnsupTemporalMeanTrainStep: the same step over a temporal adjacency (GSUnsupervised(temporal_walks=True)): the
+builder's walks respect time and hand the frontier sampler (gsage_sample_hops_temporal) a query time per row.
+
+The first two record gsage_unsup_batch_biased as their builder when the model's walk_p / walk_q are not neutral (include/gsage.h,
 "Biased walks"): the same buffers and call index; nothing else of the step changes.
 """
 import ctypes
@@ -18,9 +21,11 @@ import torch
 
 from .. import _native as nat
 from .. import ops
-from ..nn_modules import MeanAggregator, NodeEmbeddingPrep, SparseUniformNeighborSampler, \
-    SparseWeightedNeighborSampler, UniformNeighborSampler, _split_activation
+from ..nn_modules import MeanAggregator, NodeEmbeddingPrep, SparseTemporalNeighborSampler, \
+    SparseUniformNeighborSampler, SparseWeightedNeighborSampler, UniformNeighborSampler, _split_activation
+from ..store import FeatureStore
 from .mean import FusedMeanTrainStep
+from .temporal import FusedTemporalMeanTrainStep
 from .weighted import FusedWeightedMeanTrainStep
 
 
@@ -311,3 +316,126 @@ class FusedUnsupWeightedMeanTrainStep(FusedUnsupMeanTrainStep):
 
     def step_queue(self, *a, **k):
         raise ValueError("FusedUnsupWeightedMeanTrainStep runs one batch per call: there is no queue mode")
+
+
+class FusedUnsupTemporalMeanTrainStep(FusedUnsupMeanTrainStep):
+    """FusedUnsupMeanTrainStep for a GSUnsupervised(temporal_walks=True) whose samplers are
+    SparseTemporalNeighborSampler: the same constructor plus `example_times` / `keep_times`, and `__call__(seeds,
+    times=None)`.  Two launches differ:
+
+        builder       gsage_unsup_batch_temporal: walks that respect time; beside the first R ids of the frontier buffer
+                      it writes an int64 times buffer of R entries (negative q: the time of live seed q % b, b the live
+                      count)
+        K1t           gsage_sample_hops_temporal, a launch of its own (as in FusedTemporalMeanTrainStep), with that
+                      buffer as hop 0's times
+
+    times=None means the sampler's default_times(seeds); a batch short of the recorded one pads its times with the first
+    seed's, as its seeds are padded.  The walk's rule and the sampler's strategy / rule are the train sampler's.
+    keep_times=True makes K1t write the whole frontier's times to `times_set[s]`, laid out like `ids_set[s]` (tests).
+    Step t builds the batch the model's `build_batch` would build at that point of its stream and draws hop k with the
+    call index a fresh SparseTemporalNeighborSampler consumes on the module path.  Opt-in (train.py --unsupervised
+    --temporal-walks --engine fused): not one of engine.ENGINES."""
+
+    TIMED = dict(FusedUnsupMeanTrainStep.TIMED, sampler=(14, 15))
+
+    @classmethod
+    def why_not(cls, model, feats, ddp=None, pipelined=False, eval_only=False):
+        """None, or one sentence: what of (model, feats, mode) this engine does not cover -- the sentences of
+        FusedUnsupMeanTrainStep and FusedTemporalMeanTrainStep, the model's first, the feature store's last."""
+        from ..models import GSUnsupervised
+        if not isinstance(model, GSUnsupervised):
+            return "a model that is not GSUnsupervised (%s: the supervised engines train it)" % type(model).__name__
+        if not getattr(model, "temporal_walks", False):
+            return ("a GSUnsupervised with temporal_walks=False: its walks know no time "
+                    "(FusedUnsupMeanTrainStep runs them over a uniform sampler)")
+        layers = list(model.agg_layers.children())
+        if not layers or any(type(l) is not MeanAggregator for l in layers):
+            return ("aggregators other than mean (%s): the pool, attention and LSTM aggregators have no unsupervised "
+                    "engine" % ", ".join(sorted({type(l).__name__ for l in layers})))
+        if isinstance(model.prep, NodeEmbeddingPrep):
+            return "the node_embedding prep (a trainable table under the skip-gram loss has no fused form)"
+        for s in (model.train_sampler, model.val_sampler):
+            if not isinstance(s, SparseTemporalNeighborSampler):
+                return ("a train / validation sampler that is not SparseTemporalNeighborSampler (%s: "
+                        "FusedUnsupMeanTrainStep covers the uniform sparse sampler)" % type(s).__name__)
+        if ddp is not None:
+            return "a data-parallel handle: the unsupervised engine runs in one process"
+        if pipelined:
+            return "pipelined=True: the unsupervised engine runs one batch at a time"
+        if eval_only:
+            return "eval_only=True: there is no evaluation engine for the unsupervised model (model.evaluate runs it)"
+        if isinstance(feats, FeatureStore) and feats.is_fp8:
+            return "an FP8 feature store (the temporal engine reads bf16 / fp32 rows)"
+        why = cls._why_not_common(model, feats, (MeanAggregator,), "mean", sampler=False)
+        if why:
+            return why
+        if not all(l.output_dim_ % 8 == 0 for l in layers):
+            return "output dims that are not multiples of 8"
+        post = _split_activation(layers[-1].activation)[1]
+        probe = torch.linspace(-2.0, 2.0, 12).view(3, 4)
+        if post is not None and not torch.equal(post(probe), probe):
+            return "an activation on the last layer other than the identity"
+        if int(model.output_dim) > 1024 or not 1 <= int(model.n_negatives) <= 64:
+            return "an embedding wider than 1024 or more than 64 negatives (the skip-gram head's limits)"
+        return cls._why_not_input(model, feats, None, concat_ok=False, fp8_ok=False)
+
+    def __init__(self, model, feats, example_seeds, capture=True, warmup=2, pipelined=False, eval_only=False, ddp=None,
+                 example_times=None, keep_times=False):
+        self._example_times, self.keep_times = example_times, bool(keep_times)
+        super(FusedUnsupTemporalMeanTrainStep, self).__init__(model, feats, example_seeds, capture=capture, warmup=warmup,
+                                                              pipelined=pipelined, eval_only=eval_only, ddp=ddp)
+        del self._example_times
+
+    _batch_times = FusedTemporalMeanTrainStep._batch_times
+
+    def _init_head(self, loss_fn, example_targets):
+        super(FusedUnsupTemporalMeanTrainStep, self)._init_head(loss_fn, example_targets)
+        # the seeds' query times (the builder's input) and the R times it writes (hop 0's times of K1t)
+        self.seed_times = self._batch_times(self._example_seeds, self._example_times, self.Bs).clone()
+        self.times_in = torch.zeros(2 * self.Bs + self.Q, dtype=torch.int64, device=self.dev)
+        # keep_times: the frontier's times beside every frontier buffer, keyed by the buffer the launch writes
+        self.times_set = [torch.zeros_like(t) if self.keep_times else None for t in self.ids_set]
+        self._times_of = {t.data_ptr(): tt for t, tt in zip(self.ids_set, self.times_set)}
+
+    # ---- stages ----------------------------------------------------------------------------------------------------
+    def _stage_batch(self, s):
+        """gsage_unsup_batch_temporal: seeds + their times -> the first R ids of the frontier buffer, R times, pair_w"""
+        csr, cdf, m = self.walk_csr, self.cdf, self.model
+        self._time_next(*self.TIMED["builder"])
+        nat.check(nat.lib().gsage_unsup_batch_temporal(
+            csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.etime.data_ptr(), csr.n_rows, self.seeds.data_ptr(),
+            self.seed_times.data_ptr(), self.Bs, m.walk_len, self.Q, cdf.data_ptr(), cdf._gsage_total,
+            int(getattr(self.sampler, "seed", 0)), self.batch_ctr.data_ptr(), self._call_base, 0,
+            ops.TEMPORAL_INHERIT[self.sampler.inherit], self.n_live.data_ptr(), self.ids_set[s].data_ptr(),
+            self.times_in.data_ptr(), self.pair_w.data_ptr(), csr.err_flag.data_ptr(), ops._stream()),
+            "unsup_batch_temporal")
+
+    def _stage_sample(self, s, ids=None, ahead=False, counters=None):
+        """K1t: every hop in one launch, among the edges before the builder's times (FusedTemporalMeanTrainStep's stage)"""
+        ids = self.ids_set[s] if ids is None else ids
+        d = self._hops_desc(ids, ahead, counters)
+        kept = self._times_of.get(ids.data_ptr()) if self.keep_times else None
+        self._time_next(*self.TIMED["sampler"])
+        nat.check(nat.lib().gsage_sample_hops_temporal(
+            ctypes.addressof(d), self.csr.etime.data_ptr(), self.times_in.data_ptr(), None,
+            ops.TEMPORAL_STRATEGIES[self.sampler.strategy], ops.TEMPORAL_INHERIT[self.sampler.inherit],
+            kept.data_ptr() if kept is not None else None, ops._stream()), "sample_hops_temporal")
+
+    _k1_own_launch = FusedTemporalMeanTrainStep._k1_own_launch
+    _k1_in_k5 = FusedTemporalMeanTrainStep._k1_in_k5
+    _k1_in_tail = FusedTemporalMeanTrainStep._k1_in_tail
+    _k1_early = FusedTemporalMeanTrainStep._k1_early
+
+    def load_epoch(self, *a, **k):
+        raise ValueError("FusedUnsupTemporalMeanTrainStep runs one batch per call: there is no queue mode")
+
+    def step_queue(self, *a, **k):
+        raise ValueError("FusedUnsupTemporalMeanTrainStep runs one batch per call: there is no queue mode")
+
+    def __call__(self, seeds, times=None):
+        """One train step on `seeds` (int64, 2 <= len <= the recorded batch) and their query times (int64, one per
+        seed; None: the sampler's default_times(seeds)) -> the loss (device scalar)."""
+        seeds = seeds.contiguous().view(-1)
+        if 2 <= int(seeds.shape[0]) <= self.Bs:                # (any other length: the base class says so)
+            self.seed_times.copy_(self._batch_times(seeds, times, self.Bs), non_blocking=True)
+        return super(FusedUnsupTemporalMeanTrainStep, self).__call__(seeds)

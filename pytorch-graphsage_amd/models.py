@@ -229,11 +229,18 @@ class GSUnsupervised(_SageModel):
 
     walk_p, walk_q (in [1/8, 8]): node2vec's return and in-out parameters -- every step of a walk after its first is a
     second-order step (include/gsage.h, "Biased walks", gsage_unsup_batch_biased); composes with weighted_walks (the
-    proposals are then drawn by edge weight).  1, 1: the plain walks, the entries and the bits of before."""
+    proposals are then drawn by edge weight).  1, 1: the plain walks, the entries and the bits of before.
+
+    temporal_walks=True (both samplers SparseTemporalNeighborSampler): the walks respect time (include/gsage.h, "Temporal
+    walks", gsage_unsup_batch_temporal) -- every step is drawn among the edges before the seed's query time (the sampler's
+    inherit "seed") or before the edge just walked ("edge"), and the query times travel with [seeds | positives |
+    negatives] into the temporal sampler: build_batch returns (ids, pair_w, times), and build_batch / train_step /
+    evaluate take `times` (None: the sampler's default_times).  Not with weighted_walks or walk_p / walk_q.  False:
+    nothing changes."""
 
     def __init__(self, input_dim, n_nodes, layer_specs, aggregator_class, prep_class, sampler_class, adj, train_adj,
                  lr_init=0.01, weight_decay=0.0, lr_schedule='constant', epochs=10, walk_len=5, n_negatives=20,
-                 neg_weight=1.0, weighted_walks=False, walk_p=1.0, walk_q=1.0):
+                 neg_weight=1.0, weighted_walks=False, walk_p=1.0, walk_q=1.0, temporal_walks=False):
         super(GSUnsupervised, self).__init__()
         assert 1 <= walk_len <= 16 and 1 <= n_negatives <= 64, "GSUnsupervised: walk_len in 1..16, n_negatives in 1..64"
         self.output_dim = self._build_encoder(input_dim, n_nodes, layer_specs, aggregator_class, prep_class,
@@ -241,6 +248,19 @@ class GSUnsupervised(_SageModel):
         self.walk_len, self.n_negatives, self.neg_weight = int(walk_len), int(n_negatives), float(neg_weight)
         self.weighted_walks = bool(weighted_walks)
         self.walk_p, self.walk_q, _ = ops.walk_bias_check(walk_p, walk_q, 0.0, "GSUnsupervised")
+        self.temporal_walks = bool(temporal_walks)
+        if self.temporal_walks:
+            for s in (self.train_sampler, self.val_sampler):
+                if not getattr(s, "temporal", False):
+                    raise ValueError("GSUnsupervised: temporal_walks=True needs the temporal sampler "
+                                     "(SparseTemporalNeighborSampler) for training and validation, not %s"
+                                     % type(s).__name__)
+            if self.weighted_walks:
+                raise ValueError("GSUnsupervised: temporal_walks=True does not combine with weighted_walks=True "
+                                 "(weights and times together are not covered)")
+            if self.biased_walks:
+                raise ValueError("GSUnsupervised: temporal_walks=True does not combine with walk_p / walk_q other than 1 "
+                                 "(biased temporal walks are not covered)")
         if self.weighted_walks:
             for s in (self.train_sampler, self.val_sampler):
                 host = None if isinstance(s, UniformNeighborSampler) else s.csr("cpu")
@@ -253,8 +273,9 @@ class GSUnsupervised(_SageModel):
 
     def extra_repr(self):
         bias = ", walk_p=%g, walk_q=%g" % (self.walk_p, self.walk_q) if self.biased_walks else ""
-        return "walk_len=%d, n_negatives=%d, neg_weight=%g%s%s" % (
-            self.walk_len, self.n_negatives, self.neg_weight, ", weighted_walks=True" if self.weighted_walks else "", bias)
+        return "walk_len=%d, n_negatives=%d, neg_weight=%g%s%s%s" % (
+            self.walk_len, self.n_negatives, self.neg_weight, ", weighted_walks=True" if self.weighted_walks else "", bias,
+            ", temporal_walks=True" if getattr(self, "temporal_walks", False) else "")
 
     @property
     def biased_walks(self):
@@ -277,40 +298,63 @@ class GSUnsupervised(_SageModel):
             self._walk[key] = (csr, ops.neg_cdf(csr, weighted=self.weighted_walks))
         return self._walk[key]
 
-    def build_batch(self, ids, train=True):
-        """-> (ids [2B + Q] = [seeds | positives | negatives], pair_w [B]) for the seeds `ids` (ops.unsup_batch)."""
+    def build_batch(self, ids, train=True, times=None):
+        """-> (ids [2B + Q] = [seeds | positives | negatives], pair_w [B]) for the seeds `ids` (ops.unsup_batch).
+        temporal_walks=True: -> (ids, pair_w, times [2B + Q]) (ops.unsup_batch_temporal) for the seeds' query times
+        `times` (int64 [B]; None: the sampler's default_times(ids)), the walk's rule the sampler's `inherit`."""
         ids = ids.contiguous().view(-1)
         csr, cdf = self._walk_graph(train, ids.device)
         sampler = self.train_sampler if train else self.val_sampler
         rank, _ = getattr(sampler, "shard", (0, 1))
         ph = {"seed": int(getattr(sampler, "seed", 0)), "call_base": self._batch_calls[int(train)],
               "g0": rank * int(ids.shape[0])}
+        if not getattr(self, "temporal_walks", False):
+            if times is not None:
+                raise ValueError("GSUnsupervised: times were given, but the walks are not temporal (temporal_walks=True)")
+        else:
+            times = sampler.default_times(ids) if times is None else times.to(ids.device).contiguous().view(-1)
+            self._batch_calls[int(train)] += 1
+            return ops.unsup_batch_temporal(csr, ids, times, self.walk_len, self.n_negatives, cdf, ph,
+                                            inherit=sampler.inherit)
         self._batch_calls[int(train)] += 1
         return ops.unsup_batch(csr, ids, self.walk_len, self.n_negatives, cdf, ph, weighted=self.weighted_walks,
                                p=self.walk_p, q=self.walk_q)
 
-    def _loss_inputs(self, ids, feats, batch, train):
-        all_ids, pair_w = batch if batch is not None else self.build_batch(ids, train=train)
+    def _loss_inputs(self, ids, feats, batch, train, times=None):
+        all_times = None
+        if batch is None:
+            batch = self.build_batch(ids, train=train, times=times)
+        elif times is not None:
+            raise ValueError("GSUnsupervised: an explicit batch carries its own times (batch = (ids, pair_w, times))")
+        if getattr(self, "temporal_walks", False):
+            if len(batch) != 3:
+                raise ValueError("GSUnsupervised: with temporal_walks=True a batch is (ids [2B + Q], pair_w [B], "
+                                 "times [2B + Q])")
+            all_ids, pair_w, all_times = batch
+        else:
+            all_ids, pair_w = batch
         B = int(pair_w.shape[0])
         Q = int(all_ids.shape[0]) - 2 * B
         assert Q >= 1, "GSUnsupervised: a batch is [seeds (B) | positives (B) | negatives (Q >= 1)]"
-        return self._encode(all_ids, feats, train=train), B, Q, pair_w
+        return self._encode(all_ids, feats, train=train, times=all_times), B, Q, pair_w
 
-    def train_step(self, ids, feats, batch=None):
-        """One optimisation step on the seeds `ids` (or on an explicit batch = (ids [2B + Q], pair_w [B])): the loss."""
+    def train_step(self, ids, feats, batch=None, times=None):
+        """One optimisation step on the seeds `ids` (or on an explicit batch = (ids [2B + Q], pair_w [B])): the loss.
+        temporal_walks=True: `times` are the seeds' query times (None: the sampler's default_times), an explicit batch
+        is (ids, pair_w, times [2B + Q])."""
         flat = self._flat_optimizer()
         self.optimizer.zero_grad()
-        E, B, Q, pair_w = self._loss_inputs(ids, feats, batch, True)
+        E, B, Q, pair_w = self._loss_inputs(ids, feats, batch, True, times)
         loss = ops.skipgram_loss(E, B, Q, pair_w, self.neg_weight)
         loss.backward()
         self._clip_and_step(flat)
         return loss.detach()
 
-    def evaluate(self, ids, feats, batch=None):
+    def evaluate(self, ids, feats, batch=None, times=None):
         """{"loss", "mrr"} of the seeds `ids` on the evaluation graph: mrr = mean of 1 / rank of a_i among
-        [a_i, n_i1 .. n_iQ] (rank 1: the positive is closer than every negative)."""
+        [a_i, n_i1 .. n_iQ] (rank 1: the positive is closer than every negative).  times: as for train_step."""
         with torch.no_grad():
-            E, B, Q, pair_w = self._loss_inputs(ids, feats, batch, False)
+            E, B, Q, pair_w = self._loss_inputs(ids, feats, batch, False, times)
             if E.is_cuda:
                 loss, aff, _ = ops.skipgram_head(E, B, Q, pair_w, self.neg_weight)
             else:

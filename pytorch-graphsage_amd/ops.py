@@ -1146,6 +1146,91 @@ def unsup_batch(csr, seeds, walk_len, Q, cdf, philox, weighted=False, p=1.0, q=1
     return torch.from_numpy(ids), torch.from_numpy(pair_w)
 
 
+UNSUP_TAG_TSTEP = 0x56000000                                                          # temporal steps, four to a block
+
+
+def unsup_batch_temporal(csr, seeds, times, walk_len, Q, cdf, philox, inherit="seed", n_valid=None):
+    """The id batch of one unsupervised step over a temporal adjacency (include/gsage.h, "Temporal walks",
+    gsage_unsup_batch_temporal): -> (ids int64 [2B + Q] = [seeds | positives | negatives], pair_w fp32 [B], times int64
+    [2B + Q]).  Every step of a seed's walk is drawn uniformly among the edges of the current row that happened strictly
+    before the walk's time: the seed's query time times[i] (inherit "seed"), or the time of the edge just walked
+    (inherit "edge": edge times strictly decrease along the walk).  A seed without such an edge is its own positive and
+    gets pair_w 0.  Seeds and positives are to be embedded as of times[i]; negative q as of times[q % b], b =
+    clamp(n_valid, 1, B) -- n_valid: an int32 device word (a tensor of one element) or an int, None: b = B.
+    csr: a store.DeviceCSR with `.etime`; cdf: neg_cdf(csr); philox: dict(seed, call_base, g0, call_ctr) as for
+    unsup_batch.  CPU tensors: the same definition in numpy / Python integers (host mode)."""
+    _temporal_csr(csr, "unsup_batch_temporal")
+    if inherit not in TEMPORAL_INHERIT:
+        raise ValueError("unsup_batch_temporal: unknown inherit rule %r (known: seed, edge)" % (inherit,))
+    seeds = seeds.contiguous().view(-1)
+    times = times.contiguous().view(-1)
+    B, Q, walk_len = int(seeds.shape[0]), int(Q), int(walk_len)
+    assert times.dtype == torch.int64 and int(times.shape[0]) == B and times.device == seeds.device, \
+        "unsup_batch_temporal: times must be int64 [B] on the seeds' device"
+    total = getattr(cdf, "_gsage_total", None)
+    if total is None:
+        total = float(cdf[-1].item())
+    seed, base, g0 = int(philox["seed"]), int(philox.get("call_base", 0)), int(philox.get("g0", 0))
+    ctr = philox.get("call_ctr")
+    if seeds.is_cuda:
+        assert cdf.dtype == torch.float64 and cdf.is_cuda and cdf.is_contiguous() and cdf.numel() == csr.n_rows
+        if n_valid is not None and not torch.is_tensor(n_valid):
+            n_valid = torch.full((1,), max(min(int(n_valid), 2 ** 31 - 1), -2 ** 31), dtype=torch.int32,
+                                 device=seeds.device)
+        assert n_valid is None or (n_valid.dtype == torch.int32 and n_valid.is_cuda and n_valid.numel() == 1)
+        ids = torch.empty(2 * B + Q, dtype=torch.int64, device=seeds.device)
+        out_times = torch.empty(2 * B + Q, dtype=torch.int64, device=seeds.device)
+        pair_w = torch.empty(B, dtype=torch.float32, device=seeds.device)
+        nat.check(nat.lib().gsage_unsup_batch_temporal(
+            _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.etime), csr.n_rows, _ptr(seeds), _ptr(times), B, walk_len, Q,
+            _ptr(cdf), total, seed, _ptr(ctr), base, g0, TEMPORAL_INHERIT[inherit], _ptr(n_valid), _ptr(ids),
+            _ptr(out_times), _ptr(pair_w), _ptr(csr.err_flag), _stream()), "unsup_batch_temporal")
+        return ids, pair_w, out_times
+    # ---- host mode
+    if not (B > 0 and Q > 0 and 1 <= walk_len <= 16):
+        raise ValueError("unsup_batch_temporal: needs B > 0, Q > 0 and 1 <= walk_len <= 16")
+    if not (total > 0.0 and total < float("inf")):
+        raise ValueError("unsup_batch_temporal: the negatives' weights sum to %g" % total)
+    call = (base + (int(ctr.item()) if ctr is not None else 0)) & 0xFFFFFFFFFFFFFFFF
+    clo, chi = call & 0xFFFFFFFF, call >> 32
+    klo, khi = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    rp, col, et, n_rows = csr.rowptr.numpy(), csr.col.numpy(), csr.etime.numpy(), csr.n_rows
+    sd, tn = seeds.numpy(), times.numpy()
+    if sd.min() < 0 or sd.max() >= n_rows:
+        raise IndexError("unsup_batch_temporal: node id out of range of the adjacency")
+    ids = np.zeros(2 * B + Q, dtype=np.int64)
+    out_times = np.zeros(2 * B + Q, dtype=np.int64)
+    pair_w = np.zeros(B, dtype=np.float32)
+    for i in range(B):
+        g = (g0 + i) & 0xFFFFFFFFFFFFFFFF
+        c = (g & 0xFFFFFFFF, g >> 32, clo, chi)
+        t = 1 + ((_philox4(c, (klo, khi ^ UNSUP_TAG_LEN))[0] * walk_len) >> 32)
+        v, tau, r = int(sd[i]), int(tn[i]), None
+        for j in range(t):
+            beg, end = int(rp[v]), int(rp[v + 1])
+            cnt = int(np.searchsorted(et[beg:end], tau, side="left")) if end - beg <= 0xFFFFFFFF else 0
+            if cnt == 0:
+                break
+            if j & 3 == 0:
+                r = _philox4(c, (klo, khi ^ (UNSUP_TAG_TSTEP | (j >> 2))))
+            e = beg + ((r[j & 3] * cnt) >> 32)
+            v = int(col[e])
+            if v < 0 or v >= n_rows:
+                raise IndexError("unsup_batch_temporal: node id out of range of the adjacency")
+            if inherit == "edge":
+                tau = int(et[e])
+        ids[i], ids[B + i], pair_w[i] = sd[i], v, 0.0 if v == sd[i] else 1.0
+        out_times[i] = out_times[B + i] = tn[i]
+    cn = cdf.numpy()
+    for q_ in range(Q):
+        r = _philox4((q_ & 0xFFFFFFFF, q_ >> 32, clo, chi), (klo, khi ^ UNSUP_TAG_NEG))
+        x = np.float64((r[0] << 21) | (r[1] >> 11)) * np.float64(2.0 ** -53) * np.float64(total)
+        ids[2 * B + q_] = min(int(np.searchsorted(cn, x, side="right")), n_rows - 1)
+    b = B if n_valid is None else min(max(int(n_valid), 1), B)
+    out_times[2 * B:] = tn[np.arange(Q) % b]
+    return torch.from_numpy(ids), torch.from_numpy(pair_w), torch.from_numpy(out_times)
+
+
 # =============================================================================================
 # K2 / K6  gather + mean, segment mean, scatter-add
 # =============================================================================================

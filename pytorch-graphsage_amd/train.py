@@ -140,9 +140,22 @@ a GPU) runs training on engine.FusedTemporalMeanTrainStep -- the mean engine beh
 hop with the times beside the ids (gsage_sample_hops_temporal), queue mode included, the seeds' query times the
 problem's `node_time` as on the module path -- and the validation / test folds on the same class; what that engine does
 not cover is an error with its sentence.
-Refused with a sentence: a problem without edge times, a dense problem, --unsupervised (the walks are not temporal) and
---importance-walks.  --eval-as-of T: --full-neighbour-eval, --save-embeddings and the exports built on the embeddings
+Refused with a sentence: a problem without edge times, a dense problem, --unsupervised without --temporal-walks (the
+walks are not temporal) and --importance-walks.  --eval-as-of T: --full-neighbour-eval, --save-embeddings and the exports built on the embeddings
 run over the snapshot of the evaluation adjacency as of T (store.DeviceCSR.snapshot: the edges with time < T).
+
+--temporal-walks (default off: nothing changes; with --unsupervised and the temporal sampler): the positives come from
+walks that respect time (models.GSUnsupervised(temporal_walks=True), gsage_unsup_batch_temporal; include/gsage.h,
+"Temporal walks"): every step is drawn uniformly among the edges before the seed's query time (--temporal-inherit seed)
+or before the edge just walked (edge), and the query times -- the problem's `node_time` -- travel with [seeds |
+positives | negatives] into the temporal sampler, in training and in the validation / test lines.  The module path runs
+it under --engine auto / eager; --engine fused --rng philox runs engine.FusedUnsupTemporalMeanTrainStep -- the temporal
+builder and gsage_sample_hops_temporal in front of the unsupervised mean engine -- or exits with that engine's sentence.
+Errors: without --unsupervised, without the temporal sampler, with --weighted-walks, --walk-p / --walk-q other than 1 or
+--importance-walks.
+--link-eval-future (with --link-eval and --eval-as-of T): the ranked edges are those stored in the evaluation adjacency
+that its snapshot as of T does not store -- the edges that first happen at or after T -- ranked on the embeddings as of
+T, filtered as --link-eval filters; the JSON line gains "future": true and "as_of": T.
 
 --weighted-walks (default off: nothing changes; with --unsupervised and the weighted sampler, asked for by name or
 reached through --importance-walks): the positives' random walks draw every step in proportion to the edge weights
@@ -290,6 +303,8 @@ def link_eval(model, problem, args, emb):
     dev = emb.device
     adj, train_adj = model.val_sampler.csr(dev), model.train_sampler.csr(dev)
     ks = tuple(int(v) for v in args.link_eval_ks.split(','))
+    if args.link_eval_future:                      # the edges that first happen at or after T, on the embeddings as of T
+        train_adj = as_of_adj(problem)
     for i, fold in enumerate(['val', 'test'] if args.show_test else ['val']):
         src, dst = gs.held_out_edges(adj, train_adj, torch.from_numpy(np.asarray(problem.nodes[fold], dtype=np.int64)))
         n = int(src.shape[0])
@@ -299,6 +314,8 @@ def link_eval(model, problem, args, emb):
             src, dst = src[pick], dst[pick]
         ranks, _ = gs.link_rank(emb, src, dst, exclude='neighbours', adj=adj)
         res = {"fold": fold, "held_out_edges": n}
+        if args.link_eval_future:
+            res["future"], res["as_of"] = True, int(args.eval_as_of)
         res.update(gs.link_metrics(ranks, ks))
         print(dumps({"link_eval": res}))
         sys.stdout.flush()
@@ -503,7 +520,8 @@ def parse_args(argv=None):
                         help='auto: a fused engine where one covers the run, else the module path (said on stderr); '
                              'eager: the module path; fused: an engine or an error.  --unsupervised runs on the module '
                              'path unless --engine fused asks for FusedUnsupMeanTrainStep (needs --rng philox; with '
-                             '--weighted-walks: FusedUnsupWeightedMeanTrainStep).  The weighted, distinct and temporal '
+                             '--weighted-walks: FusedUnsupWeightedMeanTrainStep, with --temporal-walks: '
+                             'FusedUnsupTemporalMeanTrainStep).  The weighted, distinct and temporal '
                              'samplers run on the module path unless --engine fused asks for their engine '
                              '(FusedWeightedMeanTrainStep / FusedDistinctMeanTrainStep / FusedTemporalMeanTrainStep)')
     parser.add_argument('--feature-dtype', type=str, default='native', choices=['native', 'fp8'])
@@ -564,6 +582,12 @@ def parse_args(argv=None):
     parser.add_argument('--temporal-inherit', type=str, default=None, choices=['seed', 'edge'],
                         help='with the temporal sampler: the next hop looks before the seed\'s time (default) or before '
                              'the time of the edge just walked')
+    parser.add_argument('--temporal-walks', action="store_true",
+                        help='with --unsupervised and the temporal sampler: the positives come from walks that respect '
+                             'time (gsage_unsup_batch_temporal) and the query times travel with the batch')
+    parser.add_argument('--link-eval-future', action="store_true",
+                        help='with --link-eval and --eval-as-of T: rank the edges that first happen at or after T on the '
+                             'embeddings as of T')
     parser.add_argument('--eval-as-of', type=int, default=None,
                         help='--full-neighbour-eval, --save-embeddings and the exports built on them run over the '
                              'snapshot of the evaluation adjacency as of this time (edges with time < T)')
@@ -626,7 +650,7 @@ def temporal_checks(args, problem):
                          'table' % who)
     if not (isinstance(problem.adj, gs.store.TemporalAdj) and isinstance(problem.train_adj, gs.store.TemporalAdj)):
         raise SystemExit('%s: this problem has no edge times (adj_time / train_adj_time)' % who)
-    if args.unsupervised:
+    if args.unsupervised and not args.temporal_walks:
         raise SystemExit('%s: --unsupervised is not supported (the random walks are not temporal: their positives would '
                          'come from the future)' % who)
     if args.importance_walks:
@@ -662,7 +686,7 @@ def build_model(args, problem):
     if args.unsupervised:
         return gs.GSUnsupervised(walk_len=args.walk_len, n_negatives=args.n_negatives, neg_weight=args.neg_weight,
                                  weighted_walks=args.weighted_walks, walk_p=args.walk_p, walk_q=args.walk_q,
-                                 **common)
+                                 **dict(common, **({"temporal_walks": True} if args.temporal_walks else {})))
     return GSSupervised(n_classes=problem.n_classes, **common)
 
 
@@ -712,6 +736,19 @@ def main(argv=None, problem=None):
         raise SystemExit('gsage: --unsupervised: --wide-head fuses a supervised head; there is none')
     if args.weighted_walks and not args.unsupervised:
         raise SystemExit('gsage: --weighted-walks: the walks belong to --unsupervised training (add --unsupervised)')
+    if args.temporal_walks:
+        if not args.unsupervised:
+            raise SystemExit('gsage: --temporal-walks: the walks belong to --unsupervised training (add --unsupervised)')
+        if args.sampler_class != TEMPORAL:
+            raise SystemExit('gsage: --temporal-walks: needs the temporal sampler (--sampler-class %s), not %s'
+                             % (TEMPORAL, args.sampler_class))
+        if args.weighted_walks or (args.walk_p, args.walk_q) != (1.0, 1.0) or args.importance_walks:
+            raise SystemExit('gsage: --temporal-walks: does not combine with --weighted-walks, --walk-p / --walk-q other '
+                             'than 1 or --importance-walks (weights and times together, and biased temporal walks, are '
+                             'not covered)')
+    if args.link_eval_future and not (args.link_eval and args.eval_as_of is not None):
+        raise SystemExit('gsage: --link-eval-future: goes with --link-eval and --eval-as-of T (the edges at or after T are '
+                         'ranked on the embeddings as of T)')
     if (args.walk_p, args.walk_q) != (1.0, 1.0) and not args.unsupervised:
         raise SystemExit('gsage: --walk-p / --walk-q: the walks belong to --unsupervised training (add --unsupervised)')
     if (args.importance_p, args.importance_q, args.importance_restart) != (1.0, 1.0, 0.0) and not args.importance_walks:
@@ -912,10 +949,11 @@ def choose_engine(args, problem, model, ddp):
     if args.unsupervised:                           # the engine is opt-in: --engine fused, or the module path
         if args.engine != 'fused':
             return give_up('unsupervised model')
-        cls = gs.engine.FusedUnsupWeightedMeanTrainStep if args.weighted_walks else gs.engine.FusedUnsupMeanTrainStep
+        cls = gs.engine.FusedUnsupWeightedMeanTrainStep if args.weighted_walks else \
+            gs.engine.FusedUnsupTemporalMeanTrainStep if args.temporal_walks else gs.engine.FusedUnsupMeanTrainStep
         why = cls.why_not(model, problem.feats, ddp)
         if why is not None:
-            return give_up('%s: %s' % (cls.__name__, why) if args.weighted_walks else why)
+            return give_up('%s: %s' % (cls.__name__, why) if args.weighted_walks or args.temporal_walks else why)
         nodes = problem.nodes['train']
         if nodes.shape[0] // (nodes.shape[0] // args.batch_size + 1) < 2:
             return give_up('chunks of fewer than two training nodes')
