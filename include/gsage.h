@@ -1816,6 +1816,99 @@ int gsage_kmeans_update(const float *partial, int32_t S, int32_t K, int32_t D, i
                         float *bias, float *inertia_hist, int64_t *changed_hist, int32_t *empty_hist, int64_t *index,
                         int64_t capacity, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Graph construction (csrc/gsage_build.hip): an edge list becomes a device CSR, and a device CSR its transpose or its
+ * symmetrised graph, on the GPU in a fixed number of launches.  Additive; the ABI version is unchanged.  Reference:
+ * utils/convert.py:100-126 (make_sparse_adjacency over a networkx graph), which the definition below restates; the
+ * GPU build, the host mode (numpy) and the tests' serial restatement agree on it bit for bit.
+ *
+ * Input.  src, dst: int64 [E], node ids in 0 .. n_nodes - 1 (n_nodes is given up front).  sel: optional bool
+ * [n_nodes].  weight: optional fp32 [E], finite and >= 0.  time: optional int64 [E], < INT64_MAX.  Weight and time
+ * together are refused.
+ *
+ * Records.  Input edge i makes record 2i = (src_i -> dst_i) and, unless the build is `directed` or src_i == dst_i,
+ * record 2i + 1 = (dst_i -> src_i): a self-loop is ONE record (Graph.add_edge(u, u) stores one entry).  With sel a
+ * record exists only if both of its ends are selected (make_sparse_adjacency(G, sel): only selected nodes get a row,
+ * only selected neighbours count).  A record carries its edge's weight or time.
+ *
+ * duplicates -- records with the same (row, neighbour):
+ *     "first"   (default without time) keep the record with the smallest index, with its payload: the reference
+ *     "sum"     (weights only) keep the first record; its weight becomes the fp32 sum of the run's weights, added in
+ *               record order, sequentially (s = w_0; s += w_1; ...): no atomics, the same bits every run
+ *     "all"     (default with time) keep every record: repeated interactions are distinct events
+ * order inside a row:
+ *     "insertion"   (default without time) ascending record index: the reference, networkx's neighbour order
+ *     "id"          ascending neighbour id, ties by record index
+ *     "time"        (default and only choice with time) ascending time, ties by record index: what TemporalAdj's
+ *                   stable lexsort gives
+ *
+ * Output, in the reference's sparse convention: n_rows = n_nodes + 1, row u + 1 holds neighbour + 1 as int32, row 0
+ * is the empty dummy.  rowptr int64 [n_rows + 1]; max_deg = max(largest row length, 1) -- for a non-empty graph the
+ * shape[1] scipy infers for the reference's matrix (`--rng compat` draws sel ~ U[0, shape[1])).  Weights become the
+ * edge table of "Weighted adjacency", times the etime of "Temporal neighbours", unchanged.
+ *
+ * Limits, checked from the shapes before anything is allocated: the record count (2E, or E when directed) must be
+ * below 2^31 (the sort carries int32 positions; a chunked build with a merge does not exist), and
+ * 2 * ceil(log2(n_rows)) <= 62.  A temporal build sorts time - min(time): max(time) - min(time) must be below 2^63.
+ * An id outside 0 .. n_nodes - 1 sets *err_flag (the record does not exist).
+ *
+ * Transpose of a device CSR, on its row ids directly (no shift by one): row v of A^T lists u for every stored u -> v,
+ * ascending u, duplicates kept, a source row's repeated edges in stored order; n_rows is the same, max_deg the largest
+ * new row length, at least 1.  The symmetrised adjacency is the union of the stored edges of A and A^T under
+ * duplicates = "first", order = "id".  A stored id outside 0 .. n_rows - 1 sets *err_flag and is dropped.  Both refuse
+ * weighted and temporal adjacencies (a device CSR keeps the CDF, not the weights; a transposed row is not in time
+ * order).
+ *
+ * The pipeline.  b = ceil(log2(n_rows)) (at least 1; bit_length(n_rows) for the two CSR builds); a record's KEY is
+ * row << b | neighbour in 0-based ids, the SENTINEL 2^(2b) - 1 stands for a record that does not exist: its row,
+ * 2^b - 1, lies behind every row.  The sorts are gsage_sort_rows (stable, 8 bits per pass, 3 launches per pass).
+ *     "id"         expand; sort 2b bits; [mark -> flag per sorted entry; inclusive scan, unless "all"]; finish; rowptr
+ *     "insertion"  expand; ["first" / "sum": sort 2b bits; mark -> row key per RECORD, the sentinel row for a dropped
+ *                  one | "all": row_keys]; sort b bits (stable: record order inside a row); finish; rowptr
+ *     "time"       expand; time_keys; sort by time; row_keys through that order; sort b bits; finish; rowptr
+ *     transpose    expand_csr (key = the column, rowof = the row); sort b bits; finish; rowptr
+ *     symmetrise   expand_csr (keys (r, c) and (c, r)); then as "id" / "first"
+ * Nothing is compacted between the stages, so the launch count depends on the key widths alone and the one readback
+ * of a build is (nnz, max_deg) at its end (a temporal build reads the time range first: it sets a sort's width).
+ *
+ *   gsage_edges_expand      keys int64 [R], R = directed ? E : 2E, 16-byte aligned.  sel: one byte per node or NULL.
+ *   gsage_edges_expand_csr  symmetric == 0: keys [nnz] = col[p] (sentinel 2^b - 1), rowof int32 [nnz] = the row of
+ *                           position p;  != 0: keys [2 nnz] = (r << b | c, c << b | r), rowof unused.  n_rows < 2^b.
+ *   gsage_edges_mark        over sorted (keys, positions): entry i is KEPT when its key is below the sentinel and
+ *                           (keep_all or it is the first of its run).  Exactly one of flag int32 [n] (by sorted entry:
+ *                           1 / 0) and row_keys int64 [n] (by record: key >> b, or 2^b - 1 when dropped).  weight /
+ *                           wsum (both or neither): wsum[same index] = the run's sum, for kept entries; the weight of
+ *                           record r is weight[r >> eshift].
+ *   gsage_edges_row_keys    row_keys[j] = keys[perm ? perm[j] : j] >> b
+ *   gsage_edges_time_keys   time_keys[r] = time[r >> eshift] - t_min
+ *   gsage_edges_finish      over the last sort's (keys, positions): a kept entry i (incl != NULL: the inclusive scan of
+ *                           the flags steps at i, its rank o = incl[i] - 1; NULL: key >> shift < n_lim, o = i) writes
+ *                           col[o] = nbr32 ? nbr32[q] : ((nbr64 ? nbr64[q] : key) & (2^nbr_bits - 1)) + col_add with
+ *                           q = perm ? perm[pos[i]] : pos[i], and w[o] / t[o] = wsrc / tsrc [by_entry ? i : q >> eshift].
+ *                           Nothing is written at or beyond `cap`.
+ *   gsage_edges_rowptr      rowptr[base + r] = the number of kept entries whose row key >> shift is below r, for
+ *                           r = 0 .. n_lim; base == 1 also writes rowptr[0] = 0 (the dummy row).
+ * All: GSAGE_EINVAL without a launch (and without a GPU) for a null pointer, a size outside the limits or a misaligned
+ * key buffer, the message naming the argument; n == 0 returns GSAGE_OK without one (rowptr still launches: it writes
+ * the zeros).  One launch each, recordable in a command list.
+ * ---------------------------------------------------------------------------------------- */
+int gsage_edges_expand(const int64_t *src, const int64_t *dst, int64_t E, int64_t n_nodes, const uint8_t *sel,
+                       int32_t directed, int32_t b, int64_t *keys, int32_t *err_flag, void *stream);
+int gsage_edges_expand_csr(const int64_t *rowptr, const int32_t *col, int64_t n_rows, int64_t nnz, int32_t symmetric,
+                           int32_t b, int64_t *keys, int32_t *rowof, int32_t *err_flag, void *stream);
+int gsage_edges_mark(const int64_t *keys_sorted, const int32_t *pos_sorted, int64_t n, int32_t b, int32_t keep_all,
+                     int32_t *flag, int64_t *row_keys, const float *weight, int32_t eshift, float *wsum, void *stream);
+int gsage_edges_row_keys(const int64_t *keys, const int32_t *perm, int64_t n, int32_t b, int64_t *row_keys,
+                         void *stream);
+int gsage_edges_time_keys(const int64_t *time, int64_t n, int32_t eshift, int64_t t_min, int64_t *time_keys,
+                          void *stream);
+int gsage_edges_finish(const int64_t *keys_sorted, const int32_t *pos_sorted, const int32_t *perm, const int32_t *incl,
+                       int64_t n, int32_t shift, int64_t n_lim, const int32_t *nbr32, const int64_t *nbr64,
+                       int32_t nbr_bits, int32_t col_add, const float *wsrc, const int64_t *tsrc, int32_t eshift,
+                       int32_t by_entry, int32_t *col, float *w, int64_t *t, int64_t cap, void *stream);
+int gsage_edges_rowptr(const int64_t *keys_sorted, const int32_t *incl, int64_t n, int32_t shift, int64_t n_lim,
+                       int64_t *rowptr, int32_t base, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,10 @@ surface of bkj/pytorch-graphsage.  Directory name has a hyphen: import it with
     store.importance_adj      any adjacency -> its importance-weighted one: visit counts of short random walks, the
                               top-T most-visited nodes per row (DeviceCSR.importance, csrc/gsage_importance.hip);
                               p=, q=, restart=: node2vec-biased walks with restarts (gsage_importance_walks_biased)
+    store.graph_from_edges    an edge list -> the adjacency (scipy matrix / WeightedAdj / TemporalAdj), built on the GPU:
+                              DeviceCSR.from_edges / .transpose() / .symmetrized() (ops.edges_to_csr, ops.csr_transpose,
+                              csrc/gsage_build.hip); gs.problem_from_edges: a NodeProblem from an edge list;
+                              `convert edges`: the problem file
     models.GSUnsupervised     label-free training: random-walk positives, degree^0.75 negatives, skip-gram head;
                               weighted_walks=True: over a weighted adjacency the walks draw every step by edge weight
                               (ops.unsup_batch(weighted=True), gsage_unsup_batch_weighted); walk_p=, walk_q=: node2vec's
@@ -53,10 +57,13 @@ from .nn_modules import aggregator_lookup, find_sampler, prep_lookup, sampler_ex
 # (gs.propagate is the FUNCTION; its module is sys.modules[gs.propagate.__module__])
 from .propagate import correct_and_smooth, correct_smooth_eval, label_propagation, propagate   # noqa: F401
 from .problem import DeviceMetrics, NodeProblem, ProblemLosses, ProblemMetrics, batch_metric   # noqa: F401
-from .store import DenseAdj, DeviceCSR, FeatureStore, RowRef, TemporalAdj, WeightedAdj, importance_adj  # noqa: F401
+from .store import (DenseAdj, DeviceCSR, FeatureStore, RowRef, TemporalAdj, WeightedAdj, graph_from_edges,  # noqa: F401
+                    importance_adj)
+from .convert import problem_from_edges                             # noqa: F401
 
 __all__ = ["GSSupervised", "GSUnsupervised", "NodeProblem", "aggregator_lookup", "prep_lookup", "sampler_lookup",
            "set_seeds", "to_numpy", "LRSchedule", "FeatureStore", "DeviceCSR", "RowRef", "ops", "full_neighbour",
            "embeddings", "query", "nearest", "link_rank", "link_metrics", "held_out_edges", "LinearProbe", "linear_probe",
            "probe_eval", "KMeans", "kmeans", "cluster_metrics", "cluster_eval", "WeightedAdj", "TemporalAdj", "find_sampler", "sampler_extensions", "importance_adj",
-           "propagate", "label_propagation", "correct_and_smooth", "correct_smooth_eval"]
+           "propagate", "label_propagation", "correct_and_smooth", "correct_smooth_eval", "graph_from_edges",
+           "problem_from_edges"]

@@ -235,6 +235,14 @@ SIGNATURES = {
     "gsage_propagate_scales": (_int, [_vp, _i64, _int, _vp, _vp, _vp]),
     "gsage_propagate": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _i64, _vp, _vp, _i64, _vp, _i64,
                                _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "gsage_edges_expand": (_int, [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "gsage_edges_expand_csr": (_int, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "gsage_edges_mark": (_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "gsage_edges_row_keys": (_int, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "gsage_edges_time_keys": (_int, [_vp, _i64, _i32, _i64, _vp, _vp]),
+    "gsage_edges_finish": (_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp,
+                                  _vp, _vp, _i64, _vp]),
+    "gsage_edges_rowptr": (_int, [_vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp]),
 }
 
 

@@ -19,6 +19,12 @@ the reference's order, so a seeded run reproduces the reference's adjacency bit 
     python -m pytorch-graphsage_amd.convert graphsage --inpath data/reddit [--sparse]
     python -m pytorch-graphsage_amd.convert cora      --inpath data/cora
     python -m pytorch-graphsage_amd.convert pokec     --inpath data/pokec
+    python -m pytorch-graphsage_amd.convert edges     --edges E.npy --targets T.npy --folds F.npy [--feats X.npy]
+                                                      [--edge-weight W.npy | --edge-time T.npy [--node-time N.npy]]
+                                                      --task classification --outpath sparse-problem.npz
+The last one needs no dictionary loop: the adjacencies of an edge list are built by store.graph_from_edges (on the
+GPU when there is one; include/gsage.h, "Graph construction") and equal what graph_from_edgelist +
+make_sparse_adjacency give.
 """
 from __future__ import print_function
 
@@ -287,16 +293,98 @@ def convert_pokec(inpath, out_dense, out_sparse, max_degree=128, seed=123):
     return outs
 
 
+# ---- edge lists: the adjacency built by the device builder (store.graph_from_edges) -----------------
+def _node_time_rows(node_time, n_nodes):
+    """node_time as TemporalAdj wants it, one entry per ROW: [n_nodes] gets the dummy's entry in front (INT64_MAX: a
+    query time that sees the whole row; the dummy is never a seed)"""
+    if node_time is None:
+        return None
+    node_time = np.asarray(node_time)
+    if node_time.ndim == 1 and node_time.shape[0] == n_nodes:
+        node_time = np.hstack([np.array([np.iinfo(np.int64).max], dtype=node_time.dtype), node_time])
+    return node_time
+
+
+def _edge_adjacencies(edges, folds, weight, time, node_time, device):
+    """(adj over all edges, train_adj over the edges between training nodes): build_problem(sparse=True)'s pair"""
+    from .store import graph_from_edges
+    folds = np.asarray(folds)
+    n = int(folds.shape[0])
+    nt = _node_time_rows(node_time, n)
+    adj = graph_from_edges(edges, n, weight=weight, time=time, node_time=nt, device=device)
+    train_adj = graph_from_edges(edges, n, sel=(folds == 'train'), weight=weight, time=time, node_time=nt, device=device)
+    return adj, train_adj
+
+
+def problem_from_edges(task, n_classes, edges, feats, folds, targets, weight=None, time=None, node_time=None, cuda=True):
+    """A NodeProblem straight from an edge list: edges int [E, 2] over nodes 0..n-1 (n = len(folds)), feats [n, D] or
+    None, folds [n] strings, targets [n, k]; weight fp32 [E] or time int64 [E] (node_time int64 [n]) make it a
+    weighted or a temporal problem.  adj is built from all edges, train_adj from the edges between training nodes
+    (store.graph_from_edges: on the GPU when cuda and there is one), the dummy row goes first -- what
+    NodeProblem.from_arrays gives over build_problem(graph_from_edgelist(edges, n), ..., sparse=True), without the
+    Python loop over the edges."""
+    import torch
+    from .problem import NodeProblem
+    folds, targets = np.asarray(folds), np.asarray(targets)
+    adj, train_adj = _edge_adjacencies(edges, folds, weight, time, node_time, None if cuda else torch.device("cpu"))
+    f, t, fo = _augment(None if feats is None else np.asarray(feats), targets, folds, dummy_first=True)
+    return NodeProblem.from_arrays(task, n_classes, adj, train_adj, f, fo, t, cuda=cuda,
+                                   node_time=getattr(adj, "node_time", None))
+
+
+def convert_edges(edges, targets, folds, outpath, feats=None, task='classification', weight=None, time=None,
+                  node_time=None, device=None):
+    """Arrays -> the sparse problem file (the keys save_problem writes; weights and times under `adj_weight` /
+    `train_adj_weight` and `adj_time` / `train_adj_time` / `node_time`).  Without weights and times the file equals
+    save_problem(build_problem(graph_from_edgelist(edges, n), ..., sparse=True)) key by key."""
+    from .store import WeightedAdj
+    folds, targets = np.asarray(folds), np.asarray(targets)
+    if targets.ndim == 1:
+        targets = targets.reshape(-1, 1)
+    adj, train_adj = _edge_adjacencies(edges, folds, weight, time, node_time, device)
+    f, t, fo = _augment(None if feats is None else np.asarray(feats), targets, folds, dummy_first=True)
+    n_classes = None if task.startswith('regression') else \
+        (len(np.unique(targets)) if task == 'classification' else targets.shape[1])
+    prob = {"task": task, "n_classes": n_classes, "adj": adj, "train_adj": train_adj, "feats": f, "targets": t,
+            "folds": fo, "sparse": True}
+    for k in ("adj", "train_adj"):
+        if isinstance(prob[k], WeightedAdj):
+            coo = prob[k].adj.tocoo()
+            prob[k + "_weight"] = np.vstack([prob[k].weight.astype(np.float64), coo.row, coo.col])
+    return save_problem(prob, outpath)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('dataset', choices=['graphsage', 'cora', 'pokec'])
-    ap.add_argument('--inpath', type=str, required=True)
+    ap.add_argument('dataset', choices=['graphsage', 'cora', 'pokec', 'edges'])
+    ap.add_argument('--inpath', type=str)
     ap.add_argument('--outpath', type=str)
     ap.add_argument('--max-degree', type=int, default=128)
     ap.add_argument('--task', type=str, default='classification')
     ap.add_argument('--sparse', action='store_true')
     ap.add_argument('--seed', type=int, default=123)
+    ap.add_argument('--edges', type=str, help='edges: int array [E, 2] (.npy), node ids 0..n-1')
+    ap.add_argument('--targets', type=str, help='edges: [n, k] (.npy)')
+    ap.add_argument('--folds', type=str, help="edges: [n] strings 'train' / 'val' / 'test' (.npy)")
+    ap.add_argument('--feats', type=str, help='edges: [n, D] (.npy), optional')
+    ap.add_argument('--edge-weight', type=str, help='edges: fp32 [E] (.npy), optional')
+    ap.add_argument('--edge-time', type=str, help='edges: int64 [E] (.npy), optional')
+    ap.add_argument('--node-time', type=str, help='edges: int64 [n] (.npy), with --edge-time')
     args = ap.parse_args(argv)
+    if args.dataset == 'edges':
+        for k in ('edges', 'targets', 'folds', 'outpath'):
+            if getattr(args, k) is None:
+                ap.error('edges: the following arguments are required: --%s' % k)
+        if args.edge_weight and args.edge_time:
+            ap.error('edges: --edge-weight and --edge-time together are not supported')
+        if args.node_time and not args.edge_time:
+            ap.error('edges: --node-time needs --edge-time')
+        load = lambda p: None if p is None else np.load(p, allow_pickle=False)
+        print(convert_edges(load(args.edges), load(args.targets), load(args.folds), args.outpath, load(args.feats),
+                            args.task, load(args.edge_weight), load(args.edge_time), load(args.node_time)))
+        return
+    if args.inpath is None:
+        ap.error('the following arguments are required: --inpath')
     ext = '.h5' if 'h5py' in sys.modules else '.npz'
     if args.dataset == 'graphsage':
         out = args.outpath or os.path.join(args.inpath, ('sparse-problem' if args.sparse else 'problem') + ext)

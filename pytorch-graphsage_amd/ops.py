@@ -2871,3 +2871,260 @@ def propagate_step(adj, plan, y, base, a, b, alpha, beta, lo, hi, C, out=None, y
         _ptr(plan["long_rows"]), plan["n_long"], plan["slice_len"], _ptr(partials), ldp if partials is None else
         partials.stride(0), _ptr(out), ld(out), _ptr(yout), ld(yout), _ptr(adj.err_flag), _stream()), "propagate")
     return out, yout
+
+
+# =============================================================================================
+# Graph construction: edge list -> CSR, transpose, symmetrise (csrc/gsage_build.hip; include/gsage.h, "Graph
+# construction").  The GPU pipeline and the numpy host mode state one definition and agree bit for bit.
+# =============================================================================================
+EDGE_ORDERS = ("insertion", "id", "time")
+EDGE_DUPLICATES = ("first", "sum", "all")
+_OUT_OF_RANGE = "sampler: node id out of range of the adjacency"
+
+
+def edges_check(E, n_nodes, weighted, timed, directed, order, duplicates, who="edges_to_csr"):
+    """(order, duplicates) with the defaults filled in; ValueError, one sentence each, for a combination the definition
+    does not have and for shapes outside the limits -- from the shapes alone, before anything is allocated."""
+    if weighted and timed:
+        raise ValueError("%s: weights and times together are not supported" % who)
+    if order is None:
+        order = "time" if timed else "insertion"
+    if duplicates is None:
+        duplicates = "all" if timed else "first"
+    if order not in EDGE_ORDERS:
+        raise ValueError("%s: order must be one of %s, not %r" % (who, ", ".join(EDGE_ORDERS), order))
+    if duplicates not in EDGE_DUPLICATES:
+        raise ValueError("%s: duplicates must be one of %s, not %r" % (who, ", ".join(EDGE_DUPLICATES), duplicates))
+    if timed and (order != "time" or duplicates != "all"):
+        raise ValueError("%s: with edge times the rows are in time order and keep every record (order='time', "
+                         "duplicates='all')" % who)
+    if order == "time" and not timed:
+        raise ValueError("%s: order='time' needs edge times" % who)
+    if duplicates == "sum" and not weighted:
+        raise ValueError("%s: duplicates='sum' needs edge weights" % who)
+    if n_nodes < 0 or E < 0:
+        raise ValueError("%s: negative size" % who)
+    if (E if directed else 2 * E) >= 2 ** 31:
+        raise ValueError("%s: %d records; the record count must stay below 2^31 (the sort carries int32 positions)"
+                         % (who, E if directed else 2 * E))
+    if 2 * max(int(n_nodes).bit_length(), 1) > 62:
+        raise ValueError("%s: %d rows; a packed (row, neighbour) key must fit 62 bits" % (who, n_nodes + 1))
+    return order, duplicates
+
+
+def _edges_rows_host(rrow, rnbr, ridx, n_lim, order, duplicates, w, t):
+    """Host mode of the build over the EXISTING records (rrow, rnbr: 0-based int64; ridx: their record indices,
+    ascending; w / t: their payloads or None) -> (counts int64 [n_lim], neighbour ids, payload) in final order."""
+    if duplicates != "all" and rrow.size:
+        o = np.lexsort((ridx, rnbr, rrow))
+        r_, n_ = rrow[o], rnbr[o]
+        first = np.ones(o.size, dtype=bool)
+        first[1:] = (r_[1:] != r_[:-1]) | (n_[1:] != n_[:-1])
+        starts = np.flatnonzero(first)
+        if duplicates == "sum":
+            wo = w[o]
+            lens = np.diff(np.append(starts, o.size))
+            s = wo[starts].astype(np.float32)
+            for k in range(1, int(lens.max())):              # record order inside a run, sequentially, in fp32
+                m = lens > k
+                s[m] = s[m] + wo[starts[m] + k]
+            w = np.zeros(rrow.size, dtype=np.float32)
+            w[o[starts]] = s
+        kept = np.sort(o[starts])
+        rrow, rnbr, ridx = rrow[kept], rnbr[kept], ridx[kept]
+        w = None if w is None else w[kept]
+        t = None if t is None else t[kept]
+    if order == "insertion":
+        o = np.lexsort((ridx, rrow))
+    elif order == "id":
+        o = np.lexsort((ridx, rnbr, rrow))
+    else:
+        o = np.lexsort((ridx, t, rrow))
+    counts = np.bincount(rrow, minlength=n_lim).astype(np.int64) if rrow.size else np.zeros(n_lim, dtype=np.int64)
+    pay = w[o] if w is not None else (t[o] if t is not None else None)
+    return counts, rnbr[o], pay
+
+
+def _edges_sort(keys, n, bits):
+    """gsage_sort_rows over keys int64 [n] (n > 0): (keys sorted, original positions int32), stable"""
+    lib = nat.lib()
+    nb = int(lib.gsage_sort_rows_temp_bytes(n, bits))
+    assert nb > 0, "gsage_sort_rows_temp_bytes failed"
+    temp = torch.empty(nb, dtype=torch.uint8, device=keys.device)
+    ks = torch.empty(n, dtype=torch.int64, device=keys.device)
+    ps = torch.empty(n, dtype=torch.int32, device=keys.device)
+    nat.check(lib.gsage_sort_rows(_ptr(keys), n, 0, 0, bits, _ptr(ks), _ptr(ps), _ptr(temp), nb, _stream()), "sort_rows")
+    return ks, ps
+
+
+def _edges_rows_device(keys, R, b, n_lim, base, col_add, order, duplicates, weight, time, eshift, err_flag):
+    """The stages behind the expand kernel (include/gsage.h, "The pipeline") -> (rowptr, col, max_deg, payload)."""
+    lib, dev, s = nat.lib(), keys.device, _stream()
+    rowptr = torch.empty(base + n_lim + 1, dtype=torch.int64, device=dev)
+    col = torch.empty(R, dtype=torch.int32, device=dev)
+    w = torch.empty(R, dtype=torch.float32, device=dev) if weight is not None else None
+    t = torch.empty(R, dtype=torch.int64, device=dev) if time is not None else None
+    wsum = torch.empty(R, dtype=torch.float32, device=dev) if duplicates == "sum" else None
+    summed = wsum is not None
+    perm = incl = None
+    if order == "id":
+        ks, ps = _edges_sort(keys, R, 2 * b)
+        if duplicates != "all":
+            flag = torch.empty(R, dtype=torch.int32, device=dev)
+            nat.check(lib.gsage_edges_mark(_ptr(ks), _ptr(ps), R, b, 0, _ptr(flag), None, _ptr(weight) if summed else None,
+                                           eshift, _ptr(wsum), s), "edges_mark")
+            incl = torch.cumsum(flag, 0, dtype=torch.int32)
+        shift, nbr64 = b, None
+        wsrc, pay_shift, by_entry = (wsum, 0, 1) if summed else (weight, eshift, 0)
+    else:
+        if order == "time":
+            lo, hi = (int(v) for v in torch.stack(torch.aminmax(time)).cpu())
+            if hi - lo >= 2 ** 63:
+                raise ValueError("edges_to_csr: the edge times span 2^63 or more")
+            tk = torch.empty(R, dtype=torch.int64, device=dev)
+            nat.check(lib.gsage_edges_time_keys(_ptr(time), R, eshift, lo, _ptr(tk), s), "edges_time_keys")
+            _, perm = _edges_sort(tk, R, max((hi - lo).bit_length(), 1))
+            del tk
+        rk = torch.empty(R, dtype=torch.int64, device=dev)
+        if duplicates == "all":
+            nat.check(lib.gsage_edges_row_keys(_ptr(keys), _ptr(perm), R, b, _ptr(rk), s), "edges_row_keys")
+        else:
+            ks, ps = _edges_sort(keys, R, 2 * b)
+            nat.check(lib.gsage_edges_mark(_ptr(ks), _ptr(ps), R, b, 0, None, _ptr(rk), _ptr(weight) if summed else None,
+                                           eshift, _ptr(wsum), s), "edges_mark")
+        ks, ps = _edges_sort(rk, R, b)
+        shift, nbr64 = 0, keys
+        wsrc, pay_shift, by_entry = (wsum, 0, 0) if summed else (weight, eshift, 0)
+    nat.check(lib.gsage_edges_finish(_ptr(ks), _ptr(ps), _ptr(perm), _ptr(incl), R, shift, n_lim, None, _ptr(nbr64), b,
+                                     col_add, _ptr(wsrc), _ptr(time), pay_shift if time is None else eshift, by_entry,
+                                     _ptr(col), _ptr(w), _ptr(t), R, s), "edges_finish")
+    nat.check(lib.gsage_edges_rowptr(_ptr(ks), _ptr(incl), R, shift, n_lim, _ptr(rowptr), base, s), "edges_rowptr")
+    return _edges_trim(rowptr, col, w if w is not None else t, err_flag)
+
+
+def _edges_trim(rowptr, col, payload, err_flag):
+    """The one readback of a build: (nnz, largest row, error flag).  IndexError -- the flag cleared -- for an id outside
+    the graph; otherwise the outputs cut to nnz entries."""
+    stats = torch.stack([rowptr[-1], (rowptr[1:] - rowptr[:-1]).max(), err_flag[0].to(torch.int64)]).cpu()
+    nnz, max_deg, err = (int(v) for v in stats)
+    if err:
+        err_flag.zero_()
+        raise IndexError(_OUT_OF_RANGE)
+    if nnz < int(col.shape[0]):                                   # (a copy: the full-length buffers are let go)
+        col = col[:nnz].clone()
+        payload = None if payload is None else payload[:nnz].clone()
+    return rowptr, col, max(max_deg, 1), payload
+
+
+def edges_to_csr(src, dst, n_nodes, sel=None, weight=None, time=None, directed=False, order=None, duplicates=None,
+                 err_flag=None):
+    """(rowptr int64 [n_nodes + 2], col int32 [nnz], max_deg, payload) of the edge list (src, dst: int64 [E] tensors on
+    one device) in the reference's sparse convention -- include/gsage.h, "Graph construction", has the definition:
+    records, `sel`, duplicates in first / sum / all, order in insertion / id / time.  payload: the kept records' fp32
+    weights (summed under "sum") or int64 times, aligned with col, or None.  On the GPU a fixed pipeline of launches
+    around gsage_sort_rows and one readback; CPU tensors: the same definition in numpy (host mode).  ValueError for a
+    combination or a size outside the definition, IndexError for an id outside 0..n_nodes-1 (err_flag, a device int32
+    word, is left clear)."""
+    n_nodes = int(n_nodes)
+    src, dst = src.contiguous().view(-1), dst.contiguous().view(-1)
+    if src.dtype != torch.int64 or dst.dtype != torch.int64 or src.shape != dst.shape or src.device != dst.device:
+        raise ValueError("edges_to_csr: src and dst must be int64 tensors of one length on one device")
+    E, dev = int(src.shape[0]), src.device
+    order, duplicates = edges_check(E, n_nodes, weight is not None, time is not None, directed, order, duplicates)
+    if sel is not None:
+        sel = sel.contiguous().view(-1)
+        if sel.dtype != torch.bool or int(sel.shape[0]) != n_nodes or sel.device != dev:
+            raise ValueError("edges_to_csr: sel must be a bool tensor [n_nodes] on the edges' device")
+    if weight is not None:
+        weight = weight.contiguous().view(-1)
+        if weight.dtype != torch.float32 or int(weight.shape[0]) != E or weight.device != dev:
+            raise ValueError("edges_to_csr: weight must be an fp32 tensor [E] on the edges' device")
+    if time is not None:
+        time = time.contiguous().view(-1)
+        if time.dtype != torch.int64 or int(time.shape[0]) != E or time.device != dev:
+            raise ValueError("edges_to_csr: time must be an int64 tensor [E] on the edges' device")
+    if E == 0:
+        pay = None if weight is None and time is None else (weight if weight is not None else time)[:0].clone()
+        return torch.zeros(n_nodes + 2, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev), 1, pay
+    if dev.type != "cpu":
+        if err_flag is None:
+            err_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        R, b = (E if directed else 2 * E), max(n_nodes.bit_length(), 1)
+        keys = torch.empty(R, dtype=torch.int64, device=dev)
+        nat.check(nat.lib().gsage_edges_expand(_ptr(src), _ptr(dst), E, n_nodes, _ptr(sel), int(bool(directed)), b,
+                                               _ptr(keys), _ptr(err_flag), _stream()), "edges_expand")
+        return _edges_rows_device(keys, R, b, n_nodes, 1, 1, order, duplicates, weight, time, 0 if directed else 1,
+                                  err_flag)
+    # ---- host mode
+    s_, d_ = src.numpy(), dst.numpy()
+    if min(s_.min(), d_.min()) < 0 or max(s_.max(), d_.max()) >= n_nodes:
+        raise IndexError(_OUT_OF_RANGE)
+    if directed:
+        rrow, rnbr, live, edge = s_, d_, np.ones(E, dtype=bool), np.arange(E)
+    else:
+        rrow, rnbr = np.stack([s_, d_], 1).ravel(), np.stack([d_, s_], 1).ravel()
+        live = np.ones(2 * E, dtype=bool)
+        live[1::2] = s_ != d_
+        edge = np.arange(2 * E) >> 1
+    if sel is not None:
+        sn = sel.numpy()
+        live &= sn[rrow] & sn[rnbr]
+    ridx = np.flatnonzero(live)
+    w = None if weight is None else weight.numpy()[edge[ridx]]
+    t = None if time is None else time.numpy()[edge[ridx]]
+    counts, nbr, pay = _edges_rows_host(rrow[ridx], rnbr[ridx], ridx, n_nodes, order, duplicates, w, t)
+    rowptr = np.zeros(n_nodes + 2, dtype=np.int64)
+    np.cumsum(counts, out=rowptr[2:])
+    return torch.from_numpy(rowptr), torch.from_numpy((nbr + 1).astype(np.int32)), max(int(counts.max(initial=0)), 1), \
+        None if pay is None else torch.from_numpy(np.ascontiguousarray(pay))
+
+
+def csr_transpose(csr, symmetric=False):
+    """(rowptr int64 [n_rows + 1], col int32 [nnz'], max_deg) of the transpose of a store.DeviceCSR -- row v lists u for
+    every stored u -> v, ascending u, duplicates kept -- or, symmetric=True, of the union of its stored edges and their
+    reverses, each pair once, ascending neighbour id (include/gsage.h, "Graph construction").  On the row ids as they
+    are stored.  One expand launch, one sort, finish and rowptr (the symmetrised graph: the "id" / "first" pipeline);
+    CPU adjacencies: numpy.  ValueError for a weighted or temporal adjacency, IndexError for a stored id outside the
+    graph (csr.err_flag is left clear)."""
+    who = "csr_symmetrize" if symmetric else "csr_transpose"
+    if csr.edge_cdf is not None:
+        raise ValueError("%s: a weighted adjacency is refused (a DeviceCSR keeps the CDF, not the weights)" % who)
+    if csr.etime is not None:
+        raise ValueError("%s: a temporal adjacency is refused (a transposed row is not in time order)" % who)
+    n_rows, nnz, dev = csr.n_rows, csr.nnz, csr.device
+    R = 2 * nnz if symmetric else nnz
+    if R >= 2 ** 31:
+        raise ValueError("%s: %d records; the record count must stay below 2^31 (the sort carries int32 positions)"
+                         % (who, R))
+    if nnz == 0:
+        return torch.zeros(n_rows + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev), 1
+    if dev.type != "cpu":
+        lib, b, s = nat.lib(), max(int(n_rows).bit_length(), 1), _stream()
+        keys = torch.empty(R, dtype=torch.int64, device=dev)
+        if symmetric:
+            nat.check(lib.gsage_edges_expand_csr(_ptr(csr.rowptr), _ptr(csr.col), n_rows, nnz, 1, b, _ptr(keys), None,
+                                                 _ptr(csr.err_flag), s), "edges_expand_csr")
+            return _edges_rows_device(keys, R, b, n_rows, 0, 0, "id", "first", None, None, 0, csr.err_flag)[:3]
+        rowof = torch.empty(nnz, dtype=torch.int32, device=dev)
+        nat.check(lib.gsage_edges_expand_csr(_ptr(csr.rowptr), _ptr(csr.col), n_rows, nnz, 0, b, _ptr(keys), _ptr(rowof),
+                                             _ptr(csr.err_flag), s), "edges_expand_csr")
+        ks, ps = _edges_sort(keys, nnz, b)
+        rowptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+        col = torch.empty(nnz, dtype=torch.int32, device=dev)
+        nat.check(lib.gsage_edges_finish(_ptr(ks), _ptr(ps), None, None, nnz, 0, n_rows, _ptr(rowof), None, b, 0, None,
+                                         None, 0, 0, _ptr(col), None, None, nnz, s), "edges_finish")
+        nat.check(lib.gsage_edges_rowptr(_ptr(ks), None, nnz, 0, n_rows, _ptr(rowptr), 0, s), "edges_rowptr")
+        return _edges_trim(rowptr, col, None, csr.err_flag)[:3]
+    # ---- host mode
+    rp, c = csr.rowptr.numpy(), csr.col.numpy().astype(np.int64)
+    if c.min() < 0 or c.max() >= n_rows:
+        raise IndexError(_OUT_OF_RANGE)
+    r = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(rp))
+    if symmetric:
+        rrow, rnbr = np.stack([r, c], 1).ravel(), np.stack([c, r], 1).ravel()
+        counts, nbr, _ = _edges_rows_host(rrow, rnbr, np.arange(2 * nnz), n_rows, "id", "first", None, None)
+    else:
+        counts, nbr, _ = _edges_rows_host(c, r, np.arange(nnz), n_rows, "insertion", "all", None, None)
+    rowptr = np.zeros(n_rows + 1, dtype=np.int64)
+    np.cumsum(counts, out=rowptr[1:])
+    return torch.from_numpy(rowptr), torch.from_numpy(nbr.astype(np.int32)), max(int(counts.max(initial=0)), 1)

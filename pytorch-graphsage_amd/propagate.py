@@ -8,7 +8,8 @@ Everything here iterates one step over a sparse adjacency (a store.DeviceCSR):
 
 with A the stored rows of the adjacency (an empty row sums to 0 -- it is NOT sent to the dummy -- and duplicates
 count) and a, b the scales of `norm`: "sym" a = b = deg^-1/2 (D^-1/2 A D^-1/2 on an adjacency that stores both
-directions of every edge; on any other adjacency the same formula over the stored rows, nothing is symmetrised), "row"
+directions of every edge; on any other adjacency the same formula over the stored rows, nothing is symmetrised here:
+store.DeviceCSR.symmetrized() builds the adjacency that stores both directions), "row"
 a = 1 / deg, b = 1 (D^-1 A), "col" a = 1, b = 1 / deg (A D^-1); 0 where deg == 0.
 
 On the GPU one step is ops.propagate_step (csrc/gsage_propagate.hip): the kernel walks the plan infer.plan builds for

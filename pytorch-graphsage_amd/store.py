@@ -6,6 +6,9 @@ store.py -- HBM-resident data layouts of the hot path.
                 in the convention of utils/convert.py:100-126 -- ids 1-based, row 0 the dummy,
                 row i's neighbours in columns 0..deg_i-1).  Optionally weighted: `edge_cdf`, one
                 uint64 per stored edge (include/gsage.h, "Weighted adjacency"), built by with_weights().
+                from_edges() builds it from an edge list on the device, transpose() / symmetrized() from another
+                DeviceCSR (include/gsage.h, "Graph construction"); graph_from_edges() is the same for the plugin
+                surface, returned as scipy.
   WeightedAdj   the reference-convention scipy matrix plus one fp32 weight per stored edge: what a
                 weighted problem hands to the samplers in place of the bare matrix.
   TemporalAdj   the reference-convention scipy matrix plus one int64 time per stored edge, rows reordered by
@@ -297,6 +300,60 @@ class DeviceCSR(object):
             raise ValueError("neighbour ids must be 1-based positive int32 values")
         return DeviceCSR(rowptr, col, adj.shape[0], adj.shape[1])
 
+    @staticmethod
+    def from_edges(src, dst, n_nodes, device, sel=None, weight=None, time=None, directed=False, order=None,
+                   duplicates=None):
+        """The adjacency of an edge list, built on `device` (include/gsage.h, "Graph construction"; ops.edges_to_csr):
+        src, dst int64 [E] node ids in 0..n_nodes-1 -> the reference's sparse convention (n_rows = n_nodes + 1, row
+        u + 1 holds neighbour + 1, row 0 the empty dummy), bit-identical to convert.graph_from_edgelist +
+        make_sparse_adjacency under the defaults.  sel: bool [n_nodes], only edges between selected nodes (the
+        training graph).  weight fp32 [E] / time int64 [E]: the result carries its edge_cdf (with_weights) / etime
+        (with_times).  directed: one record per edge instead of two.  duplicates: "first" (default), "sum" (weights),
+        "all" (default with time); order: "insertion" (default), "id", "time" (with time).  ValueError for what the
+        definition does not have (2^31 records or more among it: there is no chunked build), IndexError for an id
+        outside the graph."""
+        from . import ops
+        device = torch.device(device)
+
+        def dev(x, dtype):
+            if x is None:
+                return None
+            x = torch.as_tensor(x)
+            if dtype == torch.int64 and (x.dtype.is_floating_point or x.dtype == torch.bool):
+                raise ValueError("DeviceCSR.from_edges: node ids and edge times must be integers, not %s" % x.dtype)
+            return x.to(device=device, dtype=dtype).contiguous().view(-1)
+        rowptr, col, max_deg, pay = ops.edges_to_csr(dev(src, torch.int64), dev(dst, torch.int64), n_nodes,
+                                                     sel=dev(sel, torch.bool), weight=dev(weight, torch.float32),
+                                                     time=dev(time, torch.int64), directed=directed, order=order,
+                                                     duplicates=duplicates)
+        csr = DeviceCSR(rowptr, col, int(n_nodes) + 1, max_deg)
+        if weight is not None:
+            return csr.with_weights(pay)
+        return csr.with_times(pay) if time is not None else csr
+
+    def transpose(self):
+        """A^T over the same rows, on the stored ids as they are: row v lists u for every stored u -> v, ascending u,
+        duplicates kept (ops.csr_transpose: one sort).  max_deg = the largest new row, at least 1.  A weighted or
+        temporal adjacency is a ValueError."""
+        from . import ops
+        rowptr, col, max_deg = ops.csr_transpose(self)
+        return DeviceCSR(rowptr, col, self.n_rows, max_deg)
+
+    def symmetrized(self):
+        """The union of the stored edges and their reverses, every (row, neighbour) once, ascending neighbour id
+        (ops.csr_transpose(symmetric=True)).  A weighted or temporal adjacency is a ValueError."""
+        from . import ops
+        rowptr, col, max_deg = ops.csr_transpose(self, symmetric=True)
+        return DeviceCSR(rowptr, col, self.n_rows, max_deg)
+
+    def to_scipy(self):
+        """The scipy csr_matrix of this adjacency in the reference's convention: shape (n_rows, max_deg), row v's
+        neighbour ids as int64 data in columns 0..deg_v - 1.  One copy to the host."""
+        from scipy import sparse
+        indptr = self.rowptr.cpu().numpy()
+        return sparse.csr_matrix((self.col.cpu().numpy().astype(np.int64), row_positions(indptr), indptr),
+                                 shape=(self.n_rows, self.max_deg))
+
     def check(self):
         """Raise IndexError if a kernel saw an id outside the graph (synchronises)."""
         if int(self.err_flag.item()) != 0:
@@ -336,7 +393,6 @@ def importance_adj(adj, n_walks=50, walk_len=2, top=16, seed=0, device=None, p=1
     graph) and by DeviceCSR.from_scipy.  device: where the walks run -- default the GPU when there is one, else host
     mode (the same rows).  p, q, restart: as for DeviceCSR.importance (biased walks, restarts).  The defaults reach the
     toy results of the tests; nobody has tuned them on a real graph."""
-    from scipy import sparse
     if device is None:
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if isinstance(adj, WeightedAdj):
@@ -344,10 +400,51 @@ def importance_adj(adj, n_walks=50, walk_len=2, top=16, seed=0, device=None, p=1
     else:
         csr = DeviceCSR.from_scipy(adj, device)
     rowptr, col, counts = csr._importance_rows(n_walks, walk_len, top, seed, 1 << 20, p, q, restart)
-    indptr = rowptr.cpu().numpy()
-    out = sparse.csr_matrix((col.cpu().numpy().astype(np.int64), row_positions(indptr), indptr),
-                            shape=(csr.n_rows, int(top)))
-    return WeightedAdj(out, counts.cpu().numpy())
+    return WeightedAdj(DeviceCSR(rowptr, col, csr.n_rows, int(top)).to_scipy(), counts.cpu().numpy())
+
+
+def graph_from_edges(edges, n_nodes, sel=None, weight=None, time=None, node_time=None, directed=False, order=None,
+                     duplicates=None, device=None):
+    """An edge list -> the adjacency the plugin surface trades in, in the reference's sparse convention: a scipy
+    csr_matrix of shape (n_nodes + 1, max_deg), a WeightedAdj (weight: fp32 [E]) or a TemporalAdj (time: int64 [E];
+    node_time: int64 [n_nodes + 1], the seeds' default query times).  edges: int array [E, 2] of node ids in
+    0..n_nodes-1, or a pair (src, dst).  sel, directed, order, duplicates: as for DeviceCSR.from_edges, whose
+    definition this is (include/gsage.h, "Graph construction"); under the defaults the matrix equals
+    convert.make_sparse_adjacency(convert.graph_from_edgelist(edges, n_nodes), sel).  device: where it is built --
+    default the GPU when there is one, else host mode (the same arrays); the result comes back in one copy."""
+    from . import ops
+    if device is None:
+        device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    device = torch.device(device)
+    if isinstance(edges, (tuple, list)) and len(edges) == 2 and np.ndim(edges[0]) == 1:
+        src, dst = np.asarray(edges[0]), np.asarray(edges[1])
+    else:
+        e = np.asarray(edges)
+        if e.size == 0:
+            e = e.reshape(0, 2)
+        if e.ndim != 2 or e.shape[1] != 2:
+            raise ValueError("graph_from_edges: edges must be an int array [E, 2] or a pair (src, dst)")
+        src, dst = e[:, 0], e[:, 1]
+
+    def dev(x, dtype, what):
+        if x is None:
+            return None
+        x = np.asarray(x)
+        if dtype == torch.int64 and x.dtype.kind not in "iu":
+            raise ValueError("graph_from_edges: %s must be integers, not %s" % (what, x.dtype))
+        return torch.from_numpy(np.ascontiguousarray(x)).to(device=device, dtype=dtype).contiguous().view(-1)
+    rowptr, col, max_deg, pay = ops.edges_to_csr(
+        dev(src, torch.int64, "node ids"), dev(dst, torch.int64, "node ids"), n_nodes, sel=dev(sel, torch.bool, "sel"),
+        weight=dev(weight, torch.float32, "weight"), time=dev(time, torch.int64, "edge times"), directed=directed,
+        order=order, duplicates=duplicates)
+    csr = DeviceCSR(rowptr, col, int(n_nodes) + 1, max_deg)
+    if weight is not None:
+        csr.with_weights(pay)                               # (validates: finite and >= 0)
+        return WeightedAdj(csr.to_scipy(), pay.cpu().numpy())
+    if time is not None:
+        csr.with_times(pay)                                 # (validates: below INT64_MAX, rows in time order)
+        return TemporalAdj(csr.to_scipy(), pay.cpu().numpy(), node_time=node_time)
+    return csr.to_scipy()
 
 
 class DenseAdj(object):
