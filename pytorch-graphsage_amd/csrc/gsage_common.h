@@ -208,4 +208,49 @@ __host__ __device__ __forceinline__ philox4 philox4x32_10(uint32_t c0, uint32_t 
     return o;
 }
 
+// ---- the draw: which words of the stream a sample owns, and how a word becomes an offset ---------------------
+// Every sampler addresses the stream the same way: counter = (block, call), key = (seed_lo, seed_hi ^ the sampler's
+// tag); the caller passes seed_hi with its tag already xored in.
+__device__ __forceinline__ philox4 philox_block(uint64_t blk, uint64_t call, uint32_t seed_lo, uint32_t seed_hi)
+{
+    return philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)call, (uint32_t)(call >> 32), seed_lo, seed_hi);
+}
+
+// word `sel` (0..3) of a block; selects, not r.v[sel]: no scratch
+__device__ __forceinline__ uint32_t philox_pick(const philox4 r, uint32_t sel)
+{
+    return sel == 0 ? r.v[0] : sel == 1 ? r.v[1] : sel == 2 ? r.v[2] : r.v[3];
+}
+
+// the two 32-bit words of a block that make draw `odd` of it (a block holds two 64-bit draws); selects again
+__device__ __forceinline__ uint64_t philox_r64(const philox4 &r, bool odd)
+{
+    return ((uint64_t)(odd ? r.v[2] : r.v[0]) << 32) | (uint64_t)(odd ? r.v[3] : r.v[1]);
+}
+
+// 32-bit sample g: word g & 3 of block g >> 2
+__device__ __forceinline__ uint32_t philox_word(uint64_t g, uint64_t call, uint32_t seed_lo, uint32_t seed_hi)
+{
+    const philox4 r = philox_block(g >> 2, call, seed_lo, seed_hi);
+    return philox_pick(r, (uint32_t)g & 3u);
+}
+
+// 64-bit sample g: draw g & 1 of block g >> 1
+__device__ __forceinline__ uint64_t philox_word64(uint64_t g, uint64_t call, uint32_t seed_lo, uint32_t seed_hi)
+{
+    return philox_r64(philox_block(g >> 1, call, seed_lo, seed_hi), (g & 1ull) != 0);
+}
+
+// a word scaled to [0, n): floor(word * n / 2^32)
+__device__ __forceinline__ uint32_t philox_below(uint32_t word, uint32_t n)
+{
+    return (uint32_t)(((uint64_t)word * (uint64_t)n) >> 32);
+}
+
+// ... and to a row of deg > 0 edges (a row of 2^32 edges or more, which no adjacency of this project has: the word itself)
+__device__ __forceinline__ uint64_t philox_below_deg(uint32_t word, int64_t deg)
+{
+    return (deg <= 0xffffffffLL) ? ((uint64_t)word * (uint64_t)deg) >> 32 : (uint64_t)word;
+}
+
 }  // namespace gsage

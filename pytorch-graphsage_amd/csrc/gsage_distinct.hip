@@ -7,7 +7,7 @@
 // so the plain mean over the n slots is the row's mean whenever deg divides n and an unbiased estimate of it always.
 //
 //   gsage_sample_csr_distinct   one launch per hop: a workgroup takes whole parents, 256 / n per trip
-//   gsage_sample_hops_distinct  every hop of a frontier in ONE launch: the geometry of sample_hops_workgroup
+//   gsage_sample_hops_distinct  every hop of a frontier in ONE launch: frontier_walk
 //                               (gsage_sample_dev.h: a workgroup per seed sub-tree, the previous hop in LDS), each hop
 //                               walked in the same trips of whole parents
 // Both run the body of gsage_distinct_dev.h: one lane per sample, the shuffle's t_j exchanged through LDS.
@@ -44,56 +44,29 @@ k_sample_distinct(const int64_t *__restrict__ rowptr, const int32_t *__restrict_
     }
 }
 
-// All hops of a frontier: sample_hops_workgroup's walk (same seeds per workgroup, same ping-pong LDS buffers, same ids
-// layout, the LDS barrier between hops), each hop in trips of whole parents.
+// All hops of a frontier: the frontier walk of gsage_sample_dev.h, each hop in trips of whole parents.  The two trip
+// buffers sit behind the frontier's two LDS buffers; their parity runs on across the hops.
 __global__ void __launch_bounds__(256)
 k_sample_hops_distinct(const HopsParams p)
 {
     extern __shared__ int64_t frontier[];
-    const int seed0 = (int)blockIdx.x * p.spw;
-    const int nseed = min(p.spw, p.B - seed0);
-    if (nseed <= 0) return;
-    int width = 1, widest = 1;
-    for (int k = 1; k <= p.n_hops; ++k) { width *= p.fan[k]; widest = max(widest, width); }
-    int64_t *cur = frontier, *nxt = frontier + (int64_t)p.spw * widest;
-    uint32_t *tbuf = (uint32_t *)(frontier + 2 * (int64_t)p.spw * widest);
-    if (p.seed_queue) {           // take the seeds from the queue (and publish them as hop 0)
-        const int64_t b = (int64_t)((uint64_t)(*p.batch_idx + p.batch_base) % (uint64_t)p.n_batches);
-        for (int t = threadIdx.x; t < nseed; t += 256) {
-            const int64_t v = p.seed_queue[b * p.B + seed0 + t];
-            cur[t] = v;
-            p.ids[p.off[0] + seed0 + t] = v;
-        }
-    } else {
-        for (int t = threadIdx.x; t < nseed; t += 256) cur[t] = p.ids[p.off[0] + seed0 + t];
-    }
-    lds_barrier();              // LDS only: the ids stored to HBM are not read back in this launch
-    const uint64_t ctr = p.call_ctr ? *p.call_ctr : 0ull;
-    int64_t per_seed = 1;                            // nodes of hop k per seed
+    Frontier f;
+    if (!frontier_setup<256>(p, (int)blockIdx.x, frontier, f)) return;
+    uint32_t *tbuf = (uint32_t *)(frontier + 2 * f.cap);
     int par = 0;
-    for (int k = 1; k <= p.n_hops; ++k) {
-        const uint32_t n = (uint32_t)p.fan[k];
-        const int64_t parents = per_seed * nseed;    // <= spw * widest: fits the LDS buffer (fill_hops)
-        per_seed *= n;
-        const uint64_t call = p.call_base + ctr + (uint64_t)(k - 1);
-        const int64_t local0 = (int64_t)seed0 * per_seed;             // first sample of this WG in hop k
-        const uint32_t P = 256u / n;
+    frontier_walk(p, f, [&](const Hop &h) {
+        const uint32_t n = h.n, P = 256u / n;
         const uint32_t q = threadIdx.x / n, j = threadIdx.x - q * n;
-        for (int64_t i0 = 0; i0 < parents; i0 += P, par ^= 1) {       // (uniform over the workgroup)
+        for (int64_t i0 = 0; i0 < h.parents; i0 += P, par ^= 1) {     // (uniform over the workgroup)
             const int64_t i = i0 + q;
-            const bool active = q < P && i < parents;
+            const bool active = q < P && i < h.parents;
             const int64_t t = i * (int64_t)n + j;
-            const int64_t v = distinct_trip(p.rowptr, p.col, p.n_rows, active, active ? cur[i] : 0, j, n,
-                                            p.g0[k] + (uint64_t)(local0 + t), call, p.seed_lo, p.seed_hi, p.err_flag,
+            const int64_t v = distinct_trip(p.rowptr, p.col, p.n_rows, active, active ? f.cur[i] : 0, j, n,
+                                            hop_sample(p, h, t), h.call, p.seed_lo, p.seed_hi, p.err_flag,
                                             tbuf + 256 * par);
-            if (active) {
-                nxt[t] = v;
-                p.ids[p.off[k] + local0 + t] = v;
-            }
+            if (active) hop_store(p, f, h, t, v);
         }
-        lds_barrier();
-        int64_t *tmp = cur; cur = nxt; nxt = tmp;
-    }
+    });
 }
 
 }  // namespace
@@ -131,19 +104,15 @@ int gsage_sample_hops_distinct(const gsage_hops_desc *hops, void *stream)
     GSAGE_REQUIRE(hops->rowptr && hops->col && hops->ids, "sample_hops_distinct: null pointer (rowptr, col, ids)");
     gsage_hops_desc d = *hops;
     d.max_deg = 1;                                        // ignored: a draw is scaled by its row's degree
-    {
-        int64_t width = 1, widest = 1;                    // (before fill_hops: its message names another entry)
-        for (int k = 0; k < d.n_hops; ++k) { width *= d.fan[k]; if (width > widest) widest = width; }
-        GSAGE_REQUIRE(sizeof(int64_t) * 2 * (size_t)hops_spw() * (size_t)widest + DISTINCT_TBUF <= 160 * 1024,
-                      "sample_hops_distinct: the product of fan[] is too large: the widest hop of a workgroup's seeds "
-                      "(%lld ids) does not fit the LDS", (long long)(widest * hops_spw()));
-    }
+    const int64_t widest = hops_widest(d, d.n_hops);
+    GSAGE_REQUIRE(hops_lds_bytes(widest, 2 * sizeof(int64_t), DISTINCT_TBUF) <= HOPS_LDS_MAX,
+                  "sample_hops_distinct: the product of fan[] is too large: the widest hop of a workgroup's seeds "
+                  "(%lld ids) does not fit the LDS", (long long)(widest * hops_spw()));
     HopsParams p;
     size_t lds = 0;
-    int rc = fill_hops(p, lds, d);
+    int rc = fill_hops(p, lds, d, 2 * sizeof(int64_t), DISTINCT_TBUF);
     if (rc != GSAGE_OK || d.B == 0) return rc;
-    launch(k_sample_hops_distinct, dim3((unsigned)ceil_div(d.B, p.spw)), dim3(256), lds + DISTINCT_TBUF,
-           (hipStream_t)stream, p);
+    launch(k_sample_hops_distinct, dim3((unsigned)ceil_div(d.B, p.spw)), dim3(256), lds, (hipStream_t)stream, p);
     return check_launch("sample_hops_distinct");
 }
 

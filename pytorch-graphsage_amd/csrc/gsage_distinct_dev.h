@@ -18,16 +18,6 @@ namespace gsage {
 
 constexpr uint32_t DISTINCT_TAG = 0x44000000u;   // xored into the key's high word: a stream of its own
 
-// word g & 3 of the Philox block g >> 2 (the uniform sampler's addressing); selects, not r.v[g & 3]: no scratch
-__device__ __forceinline__ uint32_t distinct_word(uint64_t g, uint64_t call, uint32_t seed_lo, uint32_t seed_hi)
-{
-    const uint64_t blk = g >> 2;
-    const philox4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)call, (uint32_t)(call >> 32),
-                                    seed_lo, seed_hi ^ DISTINCT_TAG);
-    const uint32_t s = (uint32_t)g & 3u;
-    return s == 0 ? r.v[0] : s == 1 ? r.v[1] : s == 2 ? r.v[2] : r.v[3];
-}
-
 // One trip of the calling workgroup.  EVERY lane of the workgroup calls it (it holds a barrier); `active` lanes carry
 // slot j of parent `id`, whose slot 0 sits in lane threadIdx.x - j of this trip, and draw global sample g.  tbuf: this
 // trip's 256 words.  -> the child (0: the dummy, for an inactive lane too).
@@ -51,11 +41,9 @@ __device__ __forceinline__ int64_t distinct_trip(const int64_t *__restrict__ row
             }
         }
         if (deg > n) {                                  // t_j = j + floor(w_j (deg - j) / 2^32), in [j, deg)
-            const uint32_t w = distinct_word(g, call, seed_lo, seed_hi);
-            tbuf[threadIdx.x] = j + (uint32_t)(((uint64_t)w * (uint64_t)(deg - j)) >> 32);
+            tbuf[threadIdx.x] = j + philox_below(philox_word(g, call, seed_lo, seed_hi ^ DISTINCT_TAG), deg - j);
         } else if (deg && j == 0) {                     // every neighbour: the rotation r, in [0, deg)
-            const uint32_t w = distinct_word(g, call, seed_lo, seed_hi);
-            tbuf[threadIdx.x] = (uint32_t)(((uint64_t)w * (uint64_t)deg) >> 32);
+            tbuf[threadIdx.x] = philox_below(philox_word(g, call, seed_lo, seed_hi ^ DISTINCT_TAG), deg);
         }
     }
     lds_barrier();

@@ -251,6 +251,45 @@ inline int importance_grid(int64_t items, int64_t cap)
     return (int)(items < 1 ? 1 : items > cap ? cap : items);
 }
 
+// [host] what the two walk entries require, under the entry's name.  M == 0 passes (the caller then launches nothing)
+// before the pointers are looked at.
+int importance_check(const char *entry, const int64_t *rowptr, const int32_t *col, int64_t n_rows, const int64_t *ids,
+                     int64_t M, int32_t n_walks, int32_t walk_len, int32_t top, const int32_t *out_col, const float *out_w,
+                     const int32_t *out_deg)
+{
+    GSAGE_REQUIRE(n_walks >= 1, "%s: n_walks must be >= 1", entry);
+    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= 16, "%s: walk_len must be in 1..16", entry);
+    GSAGE_REQUIRE(top >= 1 && top <= 64, "%s: top must be in 1..64", entry);
+    GSAGE_REQUIRE((int64_t)n_walks * walk_len <= IMPORTANCE_MAX_LANDINGS,
+                  "%s: n_walks * walk_len = %lld, more than %d landings per source", entry, (long long)n_walks * walk_len,
+                  IMPORTANCE_MAX_LANDINGS);
+    GSAGE_REQUIRE(M >= 0 && n_rows >= 0 && n_rows < (1LL << 31), "%s: bad sizes (node ids are int32)", entry);
+    if (M == 0) return GSAGE_OK;
+    GSAGE_REQUIRE(rowptr && col && ids && out_col && out_w && out_deg, "%s: null pointer", entry);
+    return GSAGE_OK;
+}
+
+// slots the sorts run over: the power of two >= max(n_walks * walk_len, 64)
+inline int importance_slots(int32_t n_walks, int32_t walk_len)
+{
+    int n = 64;
+    while (n < n_walks * walk_len) n <<= 1;
+    return n;
+}
+
+// The size classes: the kernel instantiated for 256 / 1024 / 4096 slots, whichever holds n, a wave per source up to the
+// class's grid cap (a 256-slot workgroup holds 3 KB of LDS, a 4096-slot one 48: three of those fit a CU)
+template <typename K, typename... Args>
+void importance_launch(K k256, K k1024, K k4096, int64_t M, int n, void *stream, Args... args)
+{
+    if (n <= 256)
+        launch(k256, dim3(importance_grid(M, 16384)), dim3(64), 0, (hipStream_t)stream, args...);
+    else if (n <= 1024)
+        launch(k1024, dim3(importance_grid(M, 8192)), dim3(64), 0, (hipStream_t)stream, args...);
+    else
+        launch(k4096, dim3(importance_grid(M, 2048)), dim3(64), 0, (hipStream_t)stream, args...);
+}
+
 }  // namespace
 
 }  // namespace gsage
@@ -263,29 +302,12 @@ int gsage_importance_walks(const int64_t *rowptr, const int32_t *col, const uint
                            const int64_t *ids, int64_t M, int32_t n_walks, int32_t walk_len, int32_t top, uint64_t seed,
                            int32_t *out_col, float *out_w, int32_t *out_deg, int32_t *err_flag, void *stream)
 {
-    GSAGE_REQUIRE(n_walks >= 1, "importance_walks: n_walks must be >= 1");
-    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= 16, "importance_walks: walk_len must be in 1..16");
-    GSAGE_REQUIRE(top >= 1 && top <= 64, "importance_walks: top must be in 1..64");
-    GSAGE_REQUIRE((int64_t)n_walks * walk_len <= IMPORTANCE_MAX_LANDINGS,
-                  "importance_walks: n_walks * walk_len = %lld, more than %d landings per source",
-                  (long long)n_walks * walk_len, IMPORTANCE_MAX_LANDINGS);
-    GSAGE_REQUIRE(M >= 0 && n_rows >= 0 && n_rows < (1LL << 31), "importance_walks: bad sizes (node ids are int32)");
-    if (M == 0) return GSAGE_OK;
-    GSAGE_REQUIRE(rowptr && col && ids && out_col && out_w && out_deg, "importance_walks: null pointer");
-    int n = 64;
-    while (n < n_walks * walk_len) n <<= 1;
-    const hipStream_t st = (hipStream_t)stream;
-    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
-    // (a 256-slot workgroup holds 3 KB of LDS, a 4096-slot one 48: three of those fit a CU)
-    if (n <= 256)
-        launch(k_importance_walks<256>, dim3(importance_grid(M, 16384)), dim3(64), 0, st, rowptr, col, cdf, n_rows, ids,
-               M, n_walks, walk_len, top, n, lo, hi, out_col, out_w, out_deg, err_flag);
-    else if (n <= 1024)
-        launch(k_importance_walks<1024>, dim3(importance_grid(M, 8192)), dim3(64), 0, st, rowptr, col, cdf, n_rows, ids,
-               M, n_walks, walk_len, top, n, lo, hi, out_col, out_w, out_deg, err_flag);
-    else
-        launch(k_importance_walks<4096>, dim3(importance_grid(M, 2048)), dim3(64), 0, st, rowptr, col, cdf, n_rows, ids,
-               M, n_walks, walk_len, top, n, lo, hi, out_col, out_w, out_deg, err_flag);
+    int rc = importance_check("importance_walks", rowptr, col, n_rows, ids, M, n_walks, walk_len, top, out_col, out_w, out_deg);
+    if (rc != GSAGE_OK || M == 0) return rc;
+    const int n = importance_slots(n_walks, walk_len);
+    importance_launch(k_importance_walks<256>, k_importance_walks<1024>, k_importance_walks<4096>, M, n, stream, rowptr, col,
+                      cdf, n_rows, ids, M, n_walks, walk_len, top, n, (uint32_t)seed, (uint32_t)(seed >> 32), out_col, out_w,
+                      out_deg, err_flag);
     return check_launch("importance_walks");
 }
 
@@ -297,31 +319,15 @@ int gsage_importance_walks_biased(const int64_t *rowptr, const int32_t *col, con
     GSAGE_REQUIRE(p >= 0.125 && p <= 8.0, "importance_walks_biased: p must be in [1/8, 8] (got %g)", p);
     GSAGE_REQUIRE(q >= 0.125 && q <= 8.0, "importance_walks_biased: q must be in [1/8, 8] (got %g)", q);
     GSAGE_REQUIRE(restart >= 0.0 && restart < 1.0, "importance_walks_biased: restart must be in [0, 1) (got %g)", restart);
-    GSAGE_REQUIRE(n_walks >= 1, "importance_walks_biased: n_walks must be >= 1");
-    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= 16, "importance_walks_biased: walk_len must be in 1..16");
-    GSAGE_REQUIRE(top >= 1 && top <= 64, "importance_walks_biased: top must be in 1..64");
-    GSAGE_REQUIRE((int64_t)n_walks * walk_len <= IMPORTANCE_MAX_LANDINGS,
-                  "importance_walks_biased: n_walks * walk_len = %lld, more than %d landings per source",
-                  (long long)n_walks * walk_len, IMPORTANCE_MAX_LANDINGS);
-    GSAGE_REQUIRE(M >= 0 && n_rows >= 0 && n_rows < (1LL << 31),
-                  "importance_walks_biased: bad sizes (node ids are int32)");
-    if (M == 0) return GSAGE_OK;
-    GSAGE_REQUIRE(rowptr && col && ids && out_col && out_w && out_deg, "importance_walks_biased: null pointer");
+    int rc = importance_check("importance_walks_biased", rowptr, col, n_rows, ids, M, n_walks, walk_len, top, out_col,
+                              out_w, out_deg);
+    if (rc != GSAGE_OK || M == 0) return rc;
     WalkBias b;
     (void)walk_bias_make(p, q, restart, b);               // (the limits were checked above)
-    int n = 64;
-    while (n < n_walks * walk_len) n <<= 1;
-    const hipStream_t st = (hipStream_t)stream;
-    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
-    if (n <= 256)
-        launch(k_importance_walks_biased<256>, dim3(importance_grid(M, 16384)), dim3(64), 0, st, rowptr, col, cdf, n_rows,
-               ids, M, n_walks, walk_len, top, n, lo, hi, b, out_col, out_w, out_deg, err_flag);
-    else if (n <= 1024)
-        launch(k_importance_walks_biased<1024>, dim3(importance_grid(M, 8192)), dim3(64), 0, st, rowptr, col, cdf, n_rows,
-               ids, M, n_walks, walk_len, top, n, lo, hi, b, out_col, out_w, out_deg, err_flag);
-    else
-        launch(k_importance_walks_biased<4096>, dim3(importance_grid(M, 2048)), dim3(64), 0, st, rowptr, col, cdf, n_rows,
-               ids, M, n_walks, walk_len, top, n, lo, hi, b, out_col, out_w, out_deg, err_flag);
+    const int n = importance_slots(n_walks, walk_len);
+    importance_launch(k_importance_walks_biased<256>, k_importance_walks_biased<1024>, k_importance_walks_biased<4096>, M, n,
+                      stream, rowptr, col, cdf, n_rows, ids, M, n_walks, walk_len, top, n, (uint32_t)seed,
+                      (uint32_t)(seed >> 32), b, out_col, out_w, out_deg, err_flag);
     return check_launch("importance_walks_biased");
 }
 

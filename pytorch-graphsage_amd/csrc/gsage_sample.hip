@@ -42,14 +42,13 @@ k_sample_philox(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ 
     const uint64_t stride = (uint64_t)gridDim.x * 256;
     for (uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x; b < nblk; b += stride) {
         const uint64_t blk = blk0 + b;
-        const philox4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)call,
-                                        (uint32_t)(call >> 32), seed_lo, seed_hi);
+        const philox4 r = philox_block(blk, call, seed_lo, seed_hi);      // a lane per block: samples 4 blk .. 4 blk + 3
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const uint64_t g = (blk << 2) + (uint64_t)k;
             if (g < g0 || g >= g0 + (uint64_t)total) continue;
             const int64_t t = (int64_t)(g - g0);
-            const uint32_t s = (uint32_t)(((uint64_t)r.v[k] * (uint64_t)max_deg) >> 32);
+            const uint32_t s = philox_below(r.v[k], max_deg);
             const int64_t i = (total <= 0xffffffffLL) ? (int64_t)((uint32_t)t / n) : t / (int64_t)n;
             if (sel_out) sel_out[t] = (int32_t)s;
             out[t] = pick_neighbor(rowptr, col, n_rows, ids[i], s, err_flag);

@@ -1,6 +1,10 @@
 // gsage_sample_dev.h -- device body of the fused multi-hop sampler (K1), shared by the stand-alone
 // kernel (gsage_sample.hip) and by k_gather_multi_adam (gsage_gather.hip), which samples a LATER
 // batch's frontier inside the launch that gathers the next batch's rows.
+//
+// Every all-hops sampler is ONE frontier walk (frontier_setup, frontier_walk: a workgroup's seeds, the ping-pong LDS
+// buffers, the per-hop bookkeeping, the barrier and the swap) plus its own hop body: the uniform bodies below
+// (sample_hops_workgroup, sample_hops_wide) and the weighted, distinct and temporal kernels of their own files.
 #pragma once
 #include "gsage_common.h"
 
@@ -91,70 +95,125 @@ inline int hops_spw()
     return v;
 }
 
-// frontier: two ping-pong LDS buffers of the widest hop; wg: which group of p.spw seeds.
+// ---- the frontier walk every all-hops sampler shares ------------------------------------------------------------------
+// A workgroup's frontier: its seeds, the two ping-pong LDS buffers of cap = spw * widest ids each, sel of its batch.
+struct Frontier {
+    int seed0, nseed;             // this workgroup's seeds: [seed0, seed0 + nseed) of the batch
+    int64_t cap;
+    int64_t *cur, *nxt;           // hop k - 1 (read) and hop k (written)
+    const int32_t *sel;
+};
+
+// Hop 0: the workgroup's seeds into f.cur, from ids or from the seed queue (then published as hop 0 of ids).
+// hook(t, src) runs once per seed beside its load: t its slot in f.cur, src its index in a per-seed array of the batch
+// (with a seed queue: in the queue).  false: no seed for this workgroup (uniform over it), nothing was touched.
+template <int THREADS, typename SeedHook>
+__device__ __forceinline__ bool frontier_setup(const HopsParams &p, int wg, int64_t *lds, Frontier &f, SeedHook hook)
+{
+    f.seed0 = wg * p.spw;
+    f.nseed = min(p.spw, p.B - f.seed0);
+    if (f.nseed <= 0) return false;
+    int width = 1, widest = 1;
+    for (int k = 1; k <= p.n_hops; ++k) { width *= p.fan[k]; widest = max(widest, width); }
+    f.cap = (int64_t)p.spw * widest;
+    f.cur = lds;
+    f.nxt = lds + f.cap;
+    f.sel = p.sel;
+    if (p.seed_queue) {
+        const int64_t b = (int64_t)((uint64_t)(*p.batch_idx + p.batch_base) % (uint64_t)p.n_batches);
+        if (f.sel) f.sel += b * p.sel_stride;
+        for (int t = threadIdx.x; t < f.nseed; t += THREADS) {
+            const int64_t v = p.seed_queue[b * p.B + f.seed0 + t];
+            f.cur[t] = v;
+            p.ids[p.off[0] + f.seed0 + t] = v;
+            hook(t, b * p.B + f.seed0 + t);
+        }
+    } else {
+        for (int t = threadIdx.x; t < f.nseed; t += THREADS) {
+            f.cur[t] = p.ids[p.off[0] + f.seed0 + t];
+            hook(t, (int64_t)f.seed0 + t);
+        }
+    }
+    lds_barrier();              // LDS only: the ids stored to HBM are not read back in this launch
+    return true;
+}
+
+// ... for a sampler whose seeds carry nothing else
+template <int THREADS>
+__device__ __forceinline__ bool frontier_setup(const HopsParams &p, int wg, int64_t *lds, Frontier &f)
+{
+    return frontier_setup<THREADS>(p, wg, lds, f, [](int, int64_t) {});
+}
+
+// One hop of one workgroup: sample t in [0, count) is child t % n of parent f.cur[t / n]
+struct Hop {
+    int k;
+    uint32_t n;                   // fan[k]
+    int64_t parents, count;       // nodes of hop k - 1 and of hop k under this workgroup's seeds (both <= f.cap)
+    int64_t local0;               // first sample of this workgroup in hop k of the batch
+    uint64_t call;                // Philox call index of hop k
+};
+
+// global sample index of sample t: the counter of its Philox word
+__device__ __forceinline__ uint64_t hop_sample(const HopsParams &p, const Hop &h, int64_t t)
+{
+    return p.g0[h.k] + (uint64_t)(h.local0 + t);
+}
+
+__device__ __forceinline__ void hop_store(const HopsParams &p, const Frontier &f, const Hop &h, int64_t t, int64_t v)
+{
+    f.nxt[t] = v;
+    p.ids[p.off[h.k] + h.local0 + t] = v;
+}
+
+// Hops 1 .. n_hops: body(h) fills f.nxt and ids for hop h (hop_store), reading f.cur; then the barrier and the swap.
+template <typename Body>
+__device__ __forceinline__ void frontier_walk(const HopsParams &p, Frontier &f, Body body)
+{
+    const uint64_t ctr = p.call_ctr ? *p.call_ctr : 0ull;
+    int64_t per_seed = 1;                            // nodes of hop k per seed
+    for (int k = 1; k <= p.n_hops; ++k) {
+        Hop h;
+        h.k = k;
+        h.n = (uint32_t)p.fan[k];
+        h.parents = per_seed * f.nseed;
+        per_seed *= h.n;
+        h.count = per_seed * f.nseed;
+        h.call = p.call_base + ctr + (uint64_t)(k - 1);
+        h.local0 = (int64_t)f.seed0 * per_seed;
+        body(h);
+        lds_barrier();
+        int64_t *tmp = f.cur; f.cur = f.nxt; f.nxt = tmp;
+    }
+}
+
+// The uniform sampler: a lane per sample.  wg: which group of p.spw seeds; frontier: 2 * cap ids of LDS.
 // DENSE_OK = false compiles the dense-adjacency mode out: k_gather_multi_adam (gsage_gather.hip) runs this body
 // beside the HBM-bound gather role under a 72-VGPR cap it already sits on -- two more live values spill.
 template <bool DENSE_OK = true>
 __device__ __forceinline__ void sample_hops_workgroup(const HopsParams &p, int wg, int64_t *frontier)
 {
-    const int seed0 = wg * p.spw;
-    const int nseed = min(p.spw, p.B - seed0);
-    if (nseed <= 0) return;
-    int width = 1, widest = 1;
-    for (int k = 1; k <= p.n_hops; ++k) { width *= p.fan[k]; widest = max(widest, width); }
-    int64_t *cur = frontier, *nxt = frontier + (int64_t)p.spw * widest;
-    const int32_t *sel = p.sel;
-    if (p.seed_queue) {           // take the seeds from the queue (and publish them as hop 0)
-        const int64_t b = (int64_t)((uint64_t)(*p.batch_idx + p.batch_base) % (uint64_t)p.n_batches);
-        if (sel) sel += b * p.sel_stride;
-        for (int t = threadIdx.x; t < nseed; t += 256) {
-            const int64_t v = p.seed_queue[b * p.B + seed0 + t];
-            cur[t] = v;
-            p.ids[p.off[0] + seed0 + t] = v;
-        }
-    } else {
-        for (int t = threadIdx.x; t < nseed; t += 256) cur[t] = p.ids[p.off[0] + seed0 + t];
-    }
-    lds_barrier();              // LDS only: the ids stored to HBM are not read back in this launch
-    const uint64_t ctr = p.call_ctr ? *p.call_ctr : 0ull;
-    int64_t per_seed = 1;                            // nodes of hop k per seed
-    for (int k = 1; k <= p.n_hops; ++k) {
-        const uint32_t n = (uint32_t)p.fan[k];
-        const int64_t parents = per_seed * nseed;
-        per_seed *= n;
-        const int64_t count = per_seed * nseed;
-        const uint64_t call = p.call_base + ctr + (uint64_t)(k - 1);
-        const int64_t local0 = (int64_t)seed0 * per_seed;             // first sample of this WG in hop k
+    Frontier f;
+    if (!frontier_setup<256>(p, wg, frontier, f)) return;
+    frontier_walk(p, f, [&](const Hop &h) {
         // dense sampler: ONE column permutation per sampler call, shared by every parent of the hop
         // (nn_modules.py:44-48): sample j of a parent reads column keep_k[j], keep_k = sel[kbase ..]
         int64_t kbase = 0;
         if (DENSE_OK)
-            for (int q = 1; q < k; ++q) kbase += p.fan[q];
+            for (int q = 1; q < h.k; ++q) kbase += p.fan[q];
         const bool dense = DENSE_OK && p.dense_adj != nullptr;
-        for (int64_t t = threadIdx.x; t < count; t += 256) {
+        for (int64_t t = threadIdx.x; t < h.count; t += 256) {
             uint32_t s;
-            if (sel) {               // parity level 1: the reference's own draws (nn_modules.py:88), replayed
-                s = (uint32_t)sel[dense ? kbase + (int64_t)((uint32_t)t % n) : p.off[k] - p.off[1] + local0 + t];
-            } else {
-                const uint64_t g = p.g0[k] + (uint64_t)(local0 + t);
-                const uint64_t blk = g >> 2;
-                const philox4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)call,
-                                                (uint32_t)(call >> 32), p.seed_lo, p.seed_hi);
-                const uint32_t sel4 = (uint32_t)g & 3u;          // selects, not r.v[g & 3]: no scratch
-                const uint32_t w = sel4 == 0 ? r.v[0] : sel4 == 1 ? r.v[1] : sel4 == 2 ? r.v[2] : r.v[3];
-                s = (uint32_t)(((uint64_t)w * (uint64_t)p.max_deg) >> 32);
-            }
-            const int64_t parent = cur[(uint32_t)t / n];
-            const int64_t v = DENSE_OK
+            if (f.sel)               // parity level 1: the reference's own draws (nn_modules.py:88), replayed
+                s = (uint32_t)f.sel[dense ? kbase + (int64_t)((uint32_t)t % h.n) : p.off[h.k] - p.off[1] + h.local0 + t];
+            else
+                s = philox_below(philox_word(hop_sample(p, h, t), h.call, p.seed_lo, p.seed_hi), p.max_deg);
+            const int64_t parent = f.cur[(uint32_t)t / h.n];
+            hop_store(p, f, h, t, DENSE_OK
                 ? pick_any(p.rowptr, p.col, p.dense_adj, p.dense_ld, p.n_rows, parent, s, p.err_flag)
-                : pick_neighbor(p.rowptr, p.col, p.n_rows, parent, s, p.err_flag);
-            nxt[t] = v;
-            p.ids[p.off[k] + local0 + t] = v;
+                : pick_neighbor(p.rowptr, p.col, p.n_rows, parent, s, p.err_flag));
         }
-        (void)parents;
-        lds_barrier();
-        int64_t *tmp = cur; cur = nxt; nxt = tmp;
-    }
+    });
 }
 
 
@@ -165,54 +224,23 @@ __device__ __forceinline__ void sample_hops_workgroup(const HopsParams &p, int w
 template <int THREADS, int U>
 __device__ __forceinline__ void sample_hops_wide(const HopsParams &p, int wg, int64_t *frontier)
 {
-    const int seed0 = wg * p.spw;
-    const int nseed = min(p.spw, p.B - seed0);
-    if (nseed <= 0) return;
-    int width = 1, widest = 1;
-    for (int k = 1; k <= p.n_hops; ++k) { width *= p.fan[k]; widest = max(widest, width); }
-    int64_t *cur = frontier, *nxt = frontier + (int64_t)p.spw * widest;
-    const int32_t *sel = p.sel;
-    if (p.seed_queue) {
-        const int64_t b = (int64_t)((uint64_t)(*p.batch_idx + p.batch_base) % (uint64_t)p.n_batches);
-        if (sel) sel += b * p.sel_stride;
-        for (int t = threadIdx.x; t < nseed; t += THREADS) {
-            const int64_t v = p.seed_queue[b * p.B + seed0 + t];
-            cur[t] = v;
-            p.ids[p.off[0] + seed0 + t] = v;
-        }
-    } else {
-        for (int t = threadIdx.x; t < nseed; t += THREADS) cur[t] = p.ids[p.off[0] + seed0 + t];
-    }
-    lds_barrier();
-    const uint64_t ctr = p.call_ctr ? *p.call_ctr : 0ull;
-    int64_t per_seed = 1;
-    for (int k = 1; k <= p.n_hops; ++k) {
-        const uint32_t n = (uint32_t)p.fan[k];
-        per_seed *= n;
-        const int64_t count = per_seed * nseed;
-        const uint64_t call = p.call_base + ctr + (uint64_t)(k - 1);
-        const int64_t local0 = (int64_t)seed0 * per_seed;
-        for (int64_t t0 = threadIdx.x; t0 < count; t0 += (int64_t)THREADS * U) {
+    Frontier f;
+    if (!frontier_setup<THREADS>(p, wg, frontier, f)) return;
+    frontier_walk(p, f, [&](const Hop &h) {
+        for (int64_t t0 = threadIdx.x; t0 < h.count; t0 += (int64_t)THREADS * U) {
             uint32_t s[U];
             int64_t parent[U], beg[U], deg[U], v[U];
             bool ok[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t t = t0 + (int64_t)u * THREADS;
-                ok[u] = t < count;
-                const int64_t tt = ok[u] ? t : count - 1;
-                if (sel) {
-                    s[u] = (uint32_t)sel[p.off[k] - p.off[1] + local0 + tt];
-                } else {
-                    const uint64_t g = p.g0[k] + (uint64_t)(local0 + tt);
-                    const uint64_t blk = g >> 2;
-                    const philox4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)call,
-                                                    (uint32_t)(call >> 32), p.seed_lo, p.seed_hi);
-                    const uint32_t sel4 = (uint32_t)g & 3u;
-                    const uint32_t w = sel4 == 0 ? r.v[0] : sel4 == 1 ? r.v[1] : sel4 == 2 ? r.v[2] : r.v[3];
-                    s[u] = (uint32_t)(((uint64_t)w * (uint64_t)p.max_deg) >> 32);
-                }
-                parent[u] = cur[(uint32_t)tt / n];
+                ok[u] = t < h.count;
+                const int64_t tt = ok[u] ? t : h.count - 1;
+                if (f.sel)
+                    s[u] = (uint32_t)f.sel[p.off[h.k] - p.off[1] + h.local0 + tt];
+                else
+                    s[u] = philox_below(philox_word(hop_sample(p, h, tt), h.call, p.seed_lo, p.seed_hi), p.max_deg);
+                parent[u] = f.cur[(uint32_t)tt / h.n];
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -229,21 +257,32 @@ __device__ __forceinline__ void sample_hops_wide(const HopsParams &p, int wg, in
                 v[u] = deg[u] > 0 ? (int64_t)p.col[beg[u] + (int64_t)o] : 0;      // (numpy: x % 0 == 0 -> column 0)
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t t = t0 + (int64_t)u * THREADS;
-                if (ok[u]) {
-                    nxt[t] = v[u];
-                    p.ids[p.off[k] + local0 + t] = v[u];
-                }
-            }
+            for (int u = 0; u < U; ++u)
+                if (ok[u]) hop_store(p, f, h, t0 + (int64_t)u * THREADS, v[u]);
         }
-        lds_barrier();
-        int64_t *tmp = cur; cur = nxt; nxt = tmp;
-    }
+    });
+}
+
+// [host] The LDS bound of every all-hops entry: per_id bytes for every id of the widest hop of a workgroup's seeds (the
+// two ping-pong buffers: 16) plus `extra`, within HOPS_LDS_MAX.  hops_widest: the widest of the first n_hops hops of one
+// seed (an entry that refuses under its own name asks before fill_hops, whose refusal names the uniform sampler).
+constexpr size_t HOPS_LDS_MAX = 160 * 1024;
+
+inline int64_t hops_widest(const gsage_hops_desc &d, int n_hops)
+{
+    int64_t width = 1, widest = 1;
+    for (int k = 0; k < n_hops; ++k) { width *= d.fan[k]; if (width > widest) widest = width; }
+    return widest;
+}
+
+inline size_t hops_lds_bytes(int64_t widest, size_t per_id, size_t extra)
+{
+    return per_id * (size_t)hops_spw() * (size_t)widest + extra;
 }
 
 // [host] validate a gsage_hops_desc and turn it into kernel parameters + dynamic LDS bytes
-inline int fill_hops(HopsParams &p, size_t &lds, const gsage_hops_desc &d)
+inline int fill_hops(HopsParams &p, size_t &lds, const gsage_hops_desc &d, size_t per_id = 2 * sizeof(int64_t),
+                     size_t extra = 0)
 {
     GSAGE_REQUIRE(d.ids && ((d.rowptr && d.col) || d.dense_adj), "sample_hops_philox: null pointer");
     GSAGE_REQUIRE(!d.dense_adj || (d.sel && d.dense_ld > 0),
@@ -277,8 +316,8 @@ inline int fill_hops(HopsParams &p, size_t &lds, const gsage_hops_desc &d)
         if (k <= d.n_hops) off += size;
     }
     p.spw = hops_spw();
-    lds = sizeof(int64_t) * 2 * (size_t)p.spw * (size_t)widest;
-    GSAGE_REQUIRE(lds <= 160 * 1024, "sample_hops_philox: fan-out product too large for the fused kernel");
+    lds = hops_lds_bytes(widest, per_id, extra);
+    GSAGE_REQUIRE(lds <= HOPS_LDS_MAX, "sample_hops_philox: fan-out product too large for the fused kernel");
     return GSAGE_OK;
 }
 

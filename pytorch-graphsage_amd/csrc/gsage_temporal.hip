@@ -7,7 +7,7 @@
 //   gsage_sample_csr_temporal   one launch per hop: a team of 16 lanes takes one parent per trip, finds cnt together
 //                               (gsage_temporal_dev.h: 16-fold narrowing by __ballot, no LDS, no barrier) and then
 //                               takes the parent's n samples in ceil(n / 16) trips, one col (and etime) load per sample
-//   gsage_sample_hops_temporal  every hop of a frontier in ONE launch: the geometry of sample_hops_workgroup
+//   gsage_sample_hops_temporal  every hop of a frontier in ONE launch: frontier_walk
 //                               (gsage_sample_dev.h: a workgroup per seed sub-tree, the previous hop in LDS) with the
 //                               times of a hop in LDS beside its ids.  A hop runs in two phases: the teams COUNT (one
 //                               search per parent, beg and cnt left in LDS), then one lane per SAMPLE draws -- at one
@@ -49,12 +49,10 @@ k_sample_temporal(const int64_t *__restrict__ rowptr, const int32_t *__restrict_
             int64_t v = 0, vt = t;
             if (cnt) {
                 uint32_t off;
-                if (STRATEGY == GSAGE_TEMPORAL_RECENT) {
+                if (STRATEGY == GSAGE_TEMPORAL_RECENT)
                     off = cnt - 1 - j % cnt;
-                } else {
-                    const uint32_t w = temporal_word(g0 + (uint64_t)(base + j), call, seed_lo, seed_hi);
-                    off = (uint32_t)(((uint64_t)w * (uint64_t)cnt) >> 32);
-                }
+                else
+                    off = philox_below(philox_word(g0 + (uint64_t)(base + j), call, seed_lo, seed_hi ^ TEMPORAL_TAG), cnt);
                 v = (int64_t)col[beg + (int64_t)off];
                 if (INHERIT == GSAGE_TEMPORAL_INHERIT_EDGE) vt = etime[beg + (int64_t)off];
             }
@@ -64,8 +62,8 @@ k_sample_temporal(const int64_t *__restrict__ rowptr, const int32_t *__restrict_
     }
 }
 
-// All hops of a temporal frontier: sample_hops_workgroup's walk (same seeds per workgroup, same ids layout, the LDS
-// barrier between hops) with a second pair of ping-pong buffers for the times.  LDS, in entries of cap = spw * widest:
+// All hops of a temporal frontier: the frontier walk of gsage_sample_dev.h with a second pair of ping-pong buffers for
+// the times.  LDS, in entries of cap = spw * widest:
 //   [ids cur | ids nxt | times cur | times nxt | beg per parent] int64, then [cnt per parent] uint32
 constexpr size_t HOPS_TEMPORAL_LDS_PER_ID = 5 * sizeof(int64_t) + sizeof(uint32_t);      // 44 bytes
 
@@ -75,50 +73,26 @@ k_sample_hops_temporal(const HopsParams p, const int64_t *__restrict__ etime, co
                        const int64_t *__restrict__ time_queue, int64_t *__restrict__ out_times)
 {
     extern __shared__ int64_t frontier[];
-    const int seed0 = (int)blockIdx.x * p.spw;
-    const int nseed = min(p.spw, p.B - seed0);
-    if (nseed <= 0) return;                          // (uniform over the workgroup)
-    int width = 1, widest = 1;
-    for (int k = 1; k <= p.n_hops; ++k) { width *= p.fan[k]; widest = max(widest, width); }
-    const int64_t cap = (int64_t)p.spw * widest;
-    int64_t *cur = frontier, *nxt = frontier + cap, *tcur = frontier + 2 * cap, *tnxt = frontier + 3 * cap;
-    int64_t *pbeg = frontier + 4 * cap;
-    uint32_t *pcnt = (uint32_t *)(frontier + 5 * cap);
-    if (p.seed_queue) {           // take the seeds and their times from the queues (and publish them as hop 0)
-        const int64_t b = (int64_t)((uint64_t)(*p.batch_idx + p.batch_base) % (uint64_t)p.n_batches);
-        for (int t = threadIdx.x; t < nseed; t += 256) {
-            const int64_t v = p.seed_queue[b * p.B + seed0 + t], vt = time_queue[b * p.B + seed0 + t];
-            cur[t] = v;
-            tcur[t] = vt;
-            p.ids[p.off[0] + seed0 + t] = v;
-            if (out_times) out_times[p.off[0] + seed0 + t] = vt;
-        }
-    } else {
-        for (int t = threadIdx.x; t < nseed; t += 256) {
-            const int64_t vt = times[seed0 + t];
-            cur[t] = p.ids[p.off[0] + seed0 + t];
-            tcur[t] = vt;
-            if (out_times) out_times[p.off[0] + seed0 + t] = vt;
-        }
-    }
-    lds_barrier();              // LDS only: what is stored to HBM is not read back in this launch
-    const uint64_t ctr = p.call_ctr ? *p.call_ctr : 0ull;
+    Frontier f;
+    // the seeds' times ride on the seeds' loop (f.cap is set by then): from the time queue beside a seed queue, else
+    // from `times`; published as hop 0 of out_times
+    const int64_t *__restrict__ seed_times = p.seed_queue ? time_queue : times;
+    if (!frontier_setup<256>(p, (int)blockIdx.x, frontier, f, [&](int t, int64_t src) {
+            const int64_t vt = seed_times[src];
+            frontier[2 * f.cap + t] = vt;
+            if (out_times) out_times[p.off[0] + f.seed0 + t] = vt;
+        })) return;                                  // (uniform over the workgroup)
+    int64_t *tcur = frontier + 2 * f.cap, *tnxt = frontier + 3 * f.cap, *pbeg = frontier + 4 * f.cap;
+    uint32_t *pcnt = (uint32_t *)(frontier + 5 * f.cap);
     const uint32_t team = threadIdx.x / TEAM, l = threadIdx.x & (TEAM - 1);
-    int64_t per_seed = 1;                            // nodes of hop k per seed
-    for (int k = 1; k <= p.n_hops; ++k) {
-        const uint32_t n = (uint32_t)p.fan[k];
-        const int64_t parents = per_seed * nseed;    // <= cap, and so is parents * n (the entry's LDS bound)
-        per_seed *= n;
-        const int64_t count = per_seed * nseed;
-        const uint64_t call = p.call_base + ctr + (uint64_t)(k - 1);
-        const int64_t local0 = (int64_t)seed0 * per_seed;             // first sample of this WG in hop k
+    frontier_walk(p, f, [&](const Hop &h) {
         // phase 1, count: a team per parent; every lane of every wave runs every trip (temporal_count's ballots)
-        for (int64_t i0 = 0; i0 < parents; i0 += TEAMS) {             // (uniform over the workgroup)
+        for (int64_t i0 = 0; i0 < h.parents; i0 += TEAMS) {           // (uniform over the workgroup)
             const int64_t i = i0 + team;
-            const bool live = i < parents;
+            const bool live = i < h.parents;
             const int64_t t = live ? tcur[i] : 0;
             int64_t beg;
-            const uint32_t deg = temporal_row(p.rowptr, p.n_rows, live, live ? cur[i] : 0, beg, p.err_flag);
+            const uint32_t deg = temporal_row(p.rowptr, p.n_rows, live, live ? f.cur[i] : 0, beg, p.err_flag);
             const uint32_t cnt = temporal_count(etime, beg, deg, t);
             if (live && l == 0) {
                 pbeg[i] = beg;
@@ -127,31 +101,26 @@ k_sample_hops_temporal(const HopsParams p, const int64_t *__restrict__ etime, co
         }
         lds_barrier();
         // phase 2, draw: a lane per sample
-        for (int64_t t = threadIdx.x; t < count; t += 256) {
-            const uint32_t i = (uint32_t)t / n, j = (uint32_t)t - i * n;
+        for (int64_t t = threadIdx.x; t < h.count; t += 256) {
+            const uint32_t i = (uint32_t)t / h.n, j = (uint32_t)t - i * h.n;
             const uint32_t cnt = pcnt[i];
             const int64_t beg = pbeg[i];
             int64_t v = 0, vt = tcur[i];
             if (cnt) {
                 uint32_t off;
-                if (STRATEGY == GSAGE_TEMPORAL_RECENT) {
+                if (STRATEGY == GSAGE_TEMPORAL_RECENT)
                     off = cnt - 1 - j % cnt;
-                } else {
-                    const uint32_t w = temporal_word(p.g0[k] + (uint64_t)(local0 + t), call, p.seed_lo, p.seed_hi);
-                    off = (uint32_t)(((uint64_t)w * (uint64_t)cnt) >> 32);
-                }
+                else
+                    off = philox_below(philox_word(hop_sample(p, h, t), h.call, p.seed_lo, p.seed_hi ^ TEMPORAL_TAG), cnt);
                 v = (int64_t)p.col[beg + (int64_t)off];
                 if (INHERIT == GSAGE_TEMPORAL_INHERIT_EDGE) vt = etime[beg + (int64_t)off];
             }
-            nxt[t] = v;
+            hop_store(p, f, h, t, v);
             tnxt[t] = vt;
-            p.ids[p.off[k] + local0 + t] = v;
-            if (out_times) out_times[p.off[k] + local0 + t] = vt;
+            if (out_times) out_times[p.off[h.k] + h.local0 + t] = vt;
         }
-        lds_barrier();
-        int64_t *tmp = cur; cur = nxt; nxt = tmp;
-        tmp = tcur; tcur = tnxt; tnxt = tmp;
-    }
+        int64_t *tmp = tcur; tcur = tnxt; tnxt = tmp;                 // (the walk swaps the ids' pair after its barrier)
+    });
 }
 
 __global__ void __launch_bounds__(256)
@@ -247,19 +216,16 @@ int gsage_sample_hops_temporal(const gsage_hops_desc *hops, const int64_t *etime
                       "sample_hops_temporal: without a seed_queue times must not be NULL and time_queue must be NULL");
     gsage_hops_desc d = *hops;
     d.max_deg = 1;                                        // ignored: a draw is scaled by its row's count
-    int64_t width = 1, widest = 1;                        // (before fill_hops: its message names another entry)
-    for (int k = 0; k < d.n_hops; ++k) {
-        width *= d.fan[k];
-        if (width > widest) widest = width;
-        GSAGE_REQUIRE(HOPS_TEMPORAL_LDS_PER_ID * (size_t)hops_spw() * (size_t)widest <= 160 * 1024,
+    for (int k = 1; k <= d.n_hops; ++k) {                 // (hop by hop: the first hop that no longer fits is named)
+        const int64_t widest = hops_widest(d, k);
+        GSAGE_REQUIRE(hops_lds_bytes(widest, HOPS_TEMPORAL_LDS_PER_ID, 0) <= HOPS_LDS_MAX,
                       "sample_hops_temporal: the product of fan[] is too large: the widest hop of a workgroup's seeds "
                       "(%lld ids, 44 bytes each) does not fit the LDS", (long long)(widest * hops_spw()));
     }
     HopsParams p;
     size_t lds = 0;
-    int rc = fill_hops(p, lds, d);                        // (its LDS figure is the uniform kernel's: 16 bytes per id)
+    int rc = fill_hops(p, lds, d, HOPS_TEMPORAL_LDS_PER_ID, 0);
     if (rc != GSAGE_OK || d.B == 0) return rc;
-    lds = HOPS_TEMPORAL_LDS_PER_ID * (size_t)p.spw * (size_t)widest;
     const bool recent = strategy == GSAGE_TEMPORAL_RECENT, edge = inherit == GSAGE_TEMPORAL_INHERIT_EDGE;
     auto kernel = recent ? (edge ? k_sample_hops_temporal<1, 1> : k_sample_hops_temporal<1, 0>)
                          : (edge ? k_sample_hops_temporal<0, 1> : k_sample_hops_temporal<0, 0>);

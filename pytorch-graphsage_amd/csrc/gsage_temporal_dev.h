@@ -21,16 +21,6 @@ namespace gsage {
 constexpr uint32_t TEMPORAL_TAG = 0x54000000u;   // xored into the key's high word: a stream of its own
 constexpr int TEAM = 16;
 
-// word g & 3 of the Philox block g >> 2 (the uniform sampler's addressing); selects, not r.v[g & 3]: no scratch
-__device__ __forceinline__ uint32_t temporal_word(uint64_t g, uint64_t call, uint32_t seed_lo, uint32_t seed_hi)
-{
-    const uint64_t blk = g >> 2;
-    const philox4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)call, (uint32_t)(call >> 32),
-                                    seed_lo, seed_hi ^ TEMPORAL_TAG);
-    const uint32_t s = (uint32_t)g & 3u;
-    return s == 0 ? r.v[0] : s == 1 ? r.v[1] : s == 2 ? r.v[2] : r.v[3];
-}
-
 // The row's extent.  live: this team carries a row; v: its id.  -> deg (0: nothing to search), beg through `beg`.
 // A row outside the graph, or one of 2^32 edges or more, has deg 0 and raises the flag.
 __device__ __forceinline__ uint32_t temporal_row(const int64_t *__restrict__ rowptr, int64_t n_rows, bool live, int64_t v,

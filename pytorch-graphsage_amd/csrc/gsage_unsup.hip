@@ -50,8 +50,7 @@ struct UnsupParams {
 
 __device__ __forceinline__ philox4 unsup_philox(const UnsupParams &p, uint64_t c, uint64_t call, uint32_t tag)
 {
-    return philox4x32_10((uint32_t)c, (uint32_t)(c >> 32), (uint32_t)call, (uint32_t)(call >> 32), p.seed_lo,
-                         p.seed_hi ^ tag);
+    return philox_block(c, call, p.seed_lo, p.seed_hi ^ tag);
 }
 
 // the negatives' role of both builders: the workgroups behind the walk workgroups, a lane per negative
@@ -70,48 +69,67 @@ __device__ __forceinline__ void unsup_negative(const UnsupParams &p, uint64_t ca
     p.ids[2 * p.B + q] = lo;
 }
 
-// blocks [0, walk_blocks): a lane per seed;  the rest: a lane per negative
+// ---- the frame of the four batch builders: the role split, the walk's length, the walk's record ------------------
+// Blocks [0, walk_blocks) build walks, the rest draw negatives.  true: this workgroup walks; false: its lanes were
+// the negatives' and are done.
+__device__ __forceinline__ bool unsup_walk_role(const UnsupParams &p, uint64_t call)
+{
+    if ((int)blockIdx.x < p.walk_blocks) return true;
+    unsup_negative(p, call);
+    return false;
+}
+
+// steps of walk g: uniform in 1 .. walk_len
+__device__ __forceinline__ int unsup_walk_steps(const UnsupParams &p, uint64_t g, uint64_t call)
+{
+    return 1 + (int)philox_below(unsup_philox(p, g, call, UNSUP_TAG_LEN).v[0], (uint32_t)p.walk_len);
+}
+
+// the three words of walk i: seed s, positive v (a walk that ends on its seed is no pair)
+__device__ __forceinline__ void unsup_store(const UnsupParams &p, int64_t i, int64_t s, int64_t v)
+{
+    p.ids[i] = s;
+    p.ids[p.B + i] = v;
+    p.pair_w[i] = v == s ? 0.f : 1.f;
+}
+
+// ... of a seed outside the graph: the flag, and 0, 0, 0.f
+__device__ __forceinline__ void unsup_store_bad(const UnsupParams &p, int64_t i)
+{
+    if (p.err_flag) *p.err_flag = 1;
+    unsup_store(p, i, 0, 0);
+}
+
+// walk blocks: a lane per seed
 __global__ void __launch_bounds__(256)
 k_unsup_batch(const UnsupParams p)
 {
     const uint64_t call = p.call_base + (p.call_ctr ? *p.call_ctr : 0ull);
-    if ((int)blockIdx.x < p.walk_blocks) {
-        const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        if (i >= p.B) return;
-        const int64_t s = p.seeds[i];
-        const uint64_t g = p.g0 + (uint64_t)i;
-        if ((uint64_t)s >= (uint64_t)p.n_rows) {
-            if (p.err_flag) *p.err_flag = 1;
-            p.ids[i] = 0;
-            p.ids[p.B + i] = 0;
-            p.pair_w[i] = 0.f;
-            return;
-        }
-        const uint32_t wl = unsup_philox(p, g, call, UNSUP_TAG_LEN).v[0];
-        const int t = 1 + (int)(((uint64_t)wl * (uint64_t)(uint32_t)p.walk_len) >> 32);
-        int64_t v = s;
-        philox4 r = {};
-        for (int j = 0; j < t; ++j) {
-            const int64_t beg = p.rowptr[v];
-            const int64_t deg = p.rowptr[v + 1] - beg;
-            if (deg <= 0) break;
-            if ((j & 3) == 0) r = unsup_philox(p, g, call, UNSUP_TAG_STEP | (uint32_t)(j >> 2));
-            const int w4 = j & 3;                               // selects, not r.v[j & 3]: no scratch
-            const uint32_t word = w4 == 0 ? r.v[0] : w4 == 1 ? r.v[1] : w4 == 2 ? r.v[2] : r.v[3];
-            const uint64_t off = (deg <= 0xffffffffLL) ? ((uint64_t)word * (uint64_t)deg) >> 32 : (uint64_t)word;
-            v = (int64_t)p.col[beg + (int64_t)off];
-            if ((uint64_t)v >= (uint64_t)p.n_rows) {
-                if (p.err_flag) *p.err_flag = 1;
-                v = 0;
-                break;
-            }
-        }
-        p.ids[i] = s;
-        p.ids[p.B + i] = v;
-        p.pair_w[i] = v == s ? 0.f : 1.f;
+    if (!unsup_walk_role(p, call)) return;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.B) return;
+    const int64_t s = p.seeds[i];
+    const uint64_t g = p.g0 + (uint64_t)i;
+    if ((uint64_t)s >= (uint64_t)p.n_rows) {
+        unsup_store_bad(p, i);
         return;
     }
-    unsup_negative(p, call);
+    const int t = unsup_walk_steps(p, g, call);
+    int64_t v = s;
+    philox4 r = {};
+    for (int j = 0; j < t; ++j) {
+        const int64_t beg = p.rowptr[v];
+        const int64_t deg = p.rowptr[v + 1] - beg;
+        if (deg <= 0) break;
+        if ((j & 3) == 0) r = unsup_philox(p, g, call, UNSUP_TAG_STEP | (uint32_t)(j >> 2));
+        v = (int64_t)p.col[beg + (int64_t)philox_below_deg(philox_pick(r, j & 3), deg)];
+        if ((uint64_t)v >= (uint64_t)p.n_rows) {
+            if (p.err_flag) *p.err_flag = 1;
+            v = 0;
+            break;
+        }
+    }
+    unsup_store(p, i, s, v);
 }
 
 
@@ -165,32 +183,22 @@ __device__ __forceinline__ int64_t wave_cdf_step(const uint64_t *__restrict__ cd
     return lo + (__ffsll((unsigned long long)__ballot(lane < n && c > x)) - 1);
 }
 
-// blocks [0, walk_blocks): a wave per seed (four to a workgroup), every branch wave-uniform;  the rest: a lane per
-// negative.  Lane 0 writes the walk's three words.
+// walk blocks: a wave per seed (four to a workgroup), every branch wave-uniform.  Lane 0 writes the walk's three words.
 __global__ void __launch_bounds__(256)
 k_unsup_batch_weighted(const UnsupParams p)
 {
     const uint64_t call = p.call_base + (p.call_ctr ? *p.call_ctr : 0ull);
-    if ((int)blockIdx.x >= p.walk_blocks) {
-        unsup_negative(p, call);
-        return;
-    }
+    if (!unsup_walk_role(p, call)) return;
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (i >= p.B) return;
     const int64_t s = wave_uniform(p.seeds[i]);
     const uint64_t g = p.g0 + (uint64_t)i;
     if ((uint64_t)s >= (uint64_t)p.n_rows) {
-        if (lane == 0) {
-            if (p.err_flag) *p.err_flag = 1;
-            p.ids[i] = 0;
-            p.ids[p.B + i] = 0;
-            p.pair_w[i] = 0.f;
-        }
+        if (lane == 0) unsup_store_bad(p, i);
         return;
     }
-    const uint32_t wl = unsup_philox(p, g, call, UNSUP_TAG_LEN).v[0];
-    const int t = 1 + (int)(((uint64_t)wl * (uint64_t)(uint32_t)p.walk_len) >> 32);
+    const int t = unsup_walk_steps(p, g, call);
     int64_t v = s;
     philox4 r = {};
     bool bad = false;
@@ -209,9 +217,7 @@ k_unsup_batch_weighted(const UnsupParams p)
     }
     if (lane == 0) {
         if (bad && p.err_flag) *p.err_flag = 1;
-        p.ids[i] = s;
-        p.ids[p.B + i] = v;
-        p.pair_w[i] = v == s ? 0.f : 1.f;
+        unsup_store(p, i, s, v);
     }
 }
 
@@ -231,26 +237,17 @@ k_unsup_batch_biased(const UnsupBiasedParams bp)
     const UnsupParams &p = bp.u;
     const WalkBias &b = bp.b;
     const uint64_t call = p.call_base + (p.call_ctr ? *p.call_ctr : 0ull);
-    if ((int)blockIdx.x >= p.walk_blocks) {
-        unsup_negative(p, call);
-        return;
-    }
+    if (!unsup_walk_role(p, call)) return;
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (i >= p.B) return;
     const int64_t s = wave_uniform(p.seeds[i]);
     const uint64_t g = p.g0 + (uint64_t)i;
     if ((uint64_t)s >= (uint64_t)p.n_rows) {
-        if (lane == 0) {
-            if (p.err_flag) *p.err_flag = 1;
-            p.ids[i] = 0;
-            p.ids[p.B + i] = 0;
-            p.pair_w[i] = 0.f;
-        }
+        if (lane == 0) unsup_store_bad(p, i);
         return;
     }
-    const uint32_t wl = unsup_philox(p, g, call, UNSUP_TAG_LEN).v[0];
-    const int t = 1 + (int)(((uint64_t)wl * (uint64_t)(uint32_t)p.walk_len) >> 32);
+    const int t = unsup_walk_steps(p, g, call);
     const bool weighted = p.edge_cdf != nullptr;
     int64_t v = s, prev = -1;
     philox4 r = {};
@@ -279,11 +276,7 @@ k_unsup_batch_biased(const UnsupBiasedParams bp)
                     break;
                 }
             } else {
-                const int w4 = j & 3;                          // selects, not r.v[j & 3]: no scratch
-                const uint32_t w0 = w4 == 0 ? r.v[0] : w4 == 1 ? r.v[1] : w4 == 2 ? r.v[2] : r.v[3];
-                const uint32_t word = k == 0 ? w0 : nb.v[0];
-                const uint64_t off = (deg <= 0xffffffffLL) ? ((uint64_t)word * (uint64_t)deg) >> 32 : (uint64_t)word;
-                e = beg + (int64_t)off;
+                e = beg + (int64_t)philox_below_deg(k == 0 ? philox_pick(r, j & 3) : nb.v[0], deg);
             }
             x = wave_uniform((int64_t)p.col[e]);
             if ((uint64_t)x >= (uint64_t)p.n_rows) {
@@ -309,9 +302,7 @@ k_unsup_batch_biased(const UnsupBiasedParams bp)
     }
     if (lane == 0) {
         if (bad && p.err_flag) *p.err_flag = 1;
-        p.ids[i] = s;
-        p.ids[p.B + i] = v;
-        p.pair_w[i] = v == s ? 0.f : 1.f;
+        unsup_store(p, i, s, v);
     }
 }
 
@@ -336,8 +327,7 @@ k_unsup_batch_temporal(const UnsupTemporalParams tp)
 {
     const UnsupParams &p = tp.u;
     const uint64_t call = p.call_base + (p.call_ctr ? *p.call_ctr : 0ull);
-    if ((int)blockIdx.x >= p.walk_blocks) {
-        unsup_negative(p, call);
+    if (!unsup_walk_role(p, call)) {                            // the negatives' times beside their ids
         const int64_t q = (int64_t)((int)blockIdx.x - p.walk_blocks) * 256 + threadIdx.x;
         if (q < p.Q) {
             const int64_t b = tp.n_valid ? (int64_t)min(max((int64_t)*tp.n_valid, (int64_t)1), p.B) : p.B;
@@ -352,11 +342,7 @@ k_unsup_batch_temporal(const UnsupTemporalParams tp)
     const int64_t t0 = live ? tp.times[i] : 0;
     const bool seed_ok = live && (uint64_t)s < (uint64_t)p.n_rows;
     const uint64_t g = p.g0 + (uint64_t)i;
-    int steps = 0;
-    if (seed_ok) {
-        const uint32_t wl = unsup_philox(p, g, call, UNSUP_TAG_LEN).v[0];
-        steps = 1 + (int)(((uint64_t)wl * (uint64_t)(uint32_t)p.walk_len) >> 32);
-    }
+    const int steps = seed_ok ? unsup_walk_steps(p, g, call) : 0;
     int64_t v = s, tau = t0;
     bool walking = seed_ok, bad = false;
     philox4 r = {};
@@ -369,9 +355,7 @@ k_unsup_batch_temporal(const UnsupTemporalParams tp)
         if (act && cnt == 0) walking = false;                   // no edge before tau: the walk ends at v
         if (act && cnt != 0) {
             if ((j & 3) == 0) r = unsup_philox(p, g, call, UNSUP_TAG_TSTEP | (uint32_t)(j >> 2));
-            const int w4 = j & 3;                               // selects, not r.v[j & 3]: no scratch
-            const uint32_t word = w4 == 0 ? r.v[0] : w4 == 1 ? r.v[1] : w4 == 2 ? r.v[2] : r.v[3];
-            const int64_t e = beg + (int64_t)(((uint64_t)word * (uint64_t)cnt) >> 32);  // < beg + cnt <= the row's end
+            const int64_t e = beg + (int64_t)philox_below(philox_pick(r, j & 3), cnt);  // < beg + cnt <= the row's end
             const int64_t x = (int64_t)p.col[e];
             if (INHERIT == GSAGE_TEMPORAL_INHERIT_EDGE) tau = tp.etime[e];
             if ((uint64_t)x >= (uint64_t)p.n_rows) {
@@ -384,12 +368,12 @@ k_unsup_batch_temporal(const UnsupTemporalParams tp)
         }
     }
     if (!live || l != 0) return;
-    if (!seed_ok || bad) {
-        if (p.err_flag) *p.err_flag = 1;
+    if (!seed_ok) {
+        unsup_store_bad(p, i);
+    } else {
+        if (bad && p.err_flag) *p.err_flag = 1;
+        unsup_store(p, i, s, v);
     }
-    p.ids[i] = seed_ok ? s : 0;
-    p.ids[p.B + i] = seed_ok ? v : 0;
-    p.pair_w[i] = (!seed_ok || v == s) ? 0.f : 1.f;
     tp.out_times[i] = t0;
     tp.out_times[p.B + i] = t0;
 }
@@ -683,6 +667,35 @@ k_head_skipgram_neg(const SkipgramParams p)
     }
 }
 
+// ---- [host] what the batch builders' entry points share ---------------------------------------------------------------
+// the checks of the plain, weighted and biased entries on their filled parameters (the temporal entry words its own);
+// needs_edge_cdf: the entry draws its steps from the per-edge table
+static int unsup_check(const char *entry, const UnsupParams &u, bool needs_edge_cdf)
+{
+    GSAGE_REQUIRE(u.rowptr && u.col && u.seeds && u.cdf && u.ids && u.pair_w, "%s: null pointer", entry);
+    GSAGE_REQUIRE(!needs_edge_cdf || u.edge_cdf, "%s: the adjacency carries no edge weights (edge_cdf is NULL)", entry);
+    GSAGE_REQUIRE(u.n_rows > 0 && u.B > 0 && u.B < (1LL << 31) && u.Q > 0 && u.Q < (1LL << 31), "%s: bad sizes", entry);
+    GSAGE_REQUIRE(u.walk_len >= 1 && u.walk_len <= UNSUP_WALK_MAX, "%s: needs 1 <= walk_len <= %d", entry, UNSUP_WALK_MAX);
+    GSAGE_REQUIRE(u.cdf_total > 0.0 && u.cdf_total <= 1.7976931348623157e308,
+                  "%s: the negatives' weights sum to %g (every row has weight 0?)", entry, u.cdf_total);
+    return GSAGE_OK;
+}
+
+// per_block: walks a workgroup of the builder's kernel takes
+static void unsup_fill(UnsupParams &u, const int64_t *rowptr, const int32_t *col, const uint64_t *edge_cdf, int64_t n_rows,
+                       const int64_t *seeds, int64_t B, int per_block, int32_t walk_len, int64_t Q, const double *cdf,
+                       double cdf_total, uint64_t seed, const uint64_t *call_ctr, uint64_t call_base, uint64_t g0,
+                       int64_t *ids, float *pair_w, int32_t *err_flag)
+{
+    u.rowptr = rowptr; u.col = col; u.seeds = seeds; u.cdf = cdf; u.edge_cdf = edge_cdf; u.call_ctr = call_ctr;
+    u.ids = ids; u.pair_w = pair_w; u.err_flag = err_flag; u.n_rows = n_rows; u.B = B; u.Q = Q; u.call_base = call_base;
+    u.g0 = g0; u.cdf_total = cdf_total; u.seed_lo = (uint32_t)seed; u.seed_hi = (uint32_t)(seed >> 32);
+    u.walk_len = walk_len; u.walk_blocks = (int32_t)ceil_div(B, per_block);
+}
+
+// the walk workgroups, then a lane per negative
+static dim3 unsup_grid(const UnsupParams &u) { return dim3((unsigned)(u.walk_blocks + ceil_div(u.Q, 256))); }
+
 template <typename K>
 static int sg_raise_lds(K kernel, size_t lds, bool &done)
 {
@@ -707,17 +720,12 @@ int gsage_unsup_batch(const int64_t *rowptr, const int32_t *col, int64_t n_rows,
                       const uint64_t *call_ctr, uint64_t call_base, uint64_t g0, int64_t *ids, float *pair_w,
                       int32_t *err_flag, void *stream)
 {
-    GSAGE_REQUIRE(rowptr && col && seeds && cdf && ids && pair_w, "unsup_batch: null pointer");
-    GSAGE_REQUIRE(n_rows > 0 && B > 0 && B < (1LL << 31) && Q > 0 && Q < (1LL << 31), "unsup_batch: bad sizes");
-    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= UNSUP_WALK_MAX, "unsup_batch: needs 1 <= walk_len <= %d", UNSUP_WALK_MAX);
-    GSAGE_REQUIRE(cdf_total > 0.0 && cdf_total <= 1.7976931348623157e308,
-                  "unsup_batch: the negatives' weights sum to %g (every row has weight 0?)", cdf_total);
     UnsupParams p;
-    p.rowptr = rowptr; p.col = col; p.seeds = seeds; p.cdf = cdf; p.call_ctr = call_ctr; p.ids = ids; p.pair_w = pair_w;
-    p.err_flag = err_flag; p.n_rows = n_rows; p.B = B; p.Q = Q; p.call_base = call_base; p.g0 = g0;
-    p.cdf_total = cdf_total; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
-    p.walk_len = walk_len; p.walk_blocks = (int32_t)ceil_div(B, 256); p.edge_cdf = nullptr;
-    launch(k_unsup_batch, dim3((unsigned)(p.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream, p);
+    unsup_fill(p, rowptr, col, nullptr, n_rows, seeds, B, 256, walk_len, Q, cdf, cdf_total, seed, call_ctr, call_base, g0,
+               ids, pair_w, err_flag);                                            // a lane per walk
+    int rc = unsup_check("unsup_batch", p, false);
+    if (rc != GSAGE_OK) return rc;
+    launch(k_unsup_batch, unsup_grid(p), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("unsup_batch");
 }
 
@@ -726,20 +734,12 @@ int gsage_unsup_batch_weighted(const int64_t *rowptr, const int32_t *col, const 
                                double cdf_total, uint64_t seed, const uint64_t *call_ctr, uint64_t call_base, uint64_t g0,
                                int64_t *ids, float *pair_w, int32_t *err_flag, void *stream)
 {
-    GSAGE_REQUIRE(rowptr && col && seeds && cdf && ids && pair_w, "unsup_batch_weighted: null pointer");
-    GSAGE_REQUIRE(edge_cdf, "unsup_batch_weighted: the adjacency carries no edge weights (edge_cdf is NULL)");
-    GSAGE_REQUIRE(n_rows > 0 && B > 0 && B < (1LL << 31) && Q > 0 && Q < (1LL << 31), "unsup_batch_weighted: bad sizes");
-    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= UNSUP_WALK_MAX, "unsup_batch_weighted: needs 1 <= walk_len <= %d",
-                  UNSUP_WALK_MAX);
-    GSAGE_REQUIRE(cdf_total > 0.0 && cdf_total <= 1.7976931348623157e308,
-                  "unsup_batch_weighted: the negatives' weights sum to %g (every row has weight 0?)", cdf_total);
     UnsupParams p;
-    p.rowptr = rowptr; p.col = col; p.seeds = seeds; p.cdf = cdf; p.edge_cdf = edge_cdf; p.call_ctr = call_ctr;
-    p.ids = ids; p.pair_w = pair_w; p.err_flag = err_flag; p.n_rows = n_rows; p.B = B; p.Q = Q; p.call_base = call_base;
-    p.g0 = g0; p.cdf_total = cdf_total; p.seed_lo = (uint32_t)seed; p.seed_hi = (uint32_t)(seed >> 32);
-    p.walk_len = walk_len; p.walk_blocks = (int32_t)ceil_div(B, 4);              // a wave per walk, four to a workgroup
-    launch(k_unsup_batch_weighted, dim3((unsigned)(p.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream,
-           p);
+    unsup_fill(p, rowptr, col, edge_cdf, n_rows, seeds, B, 4, walk_len, Q, cdf, cdf_total, seed, call_ctr, call_base, g0,
+               ids, pair_w, err_flag);                                            // a wave per walk, four to a workgroup
+    int rc = unsup_check("unsup_batch_weighted", p, true);
+    if (rc != GSAGE_OK) return rc;
+    launch(k_unsup_batch_weighted, unsup_grid(p), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("unsup_batch_weighted");
 }
 
@@ -750,21 +750,13 @@ int gsage_unsup_batch_biased(const int64_t *rowptr, const int32_t *col, const ui
 {
     GSAGE_REQUIRE(p >= 0.125 && p <= 8.0, "unsup_batch_biased: p must be in [1/8, 8] (got %g)", p);
     GSAGE_REQUIRE(q >= 0.125 && q <= 8.0, "unsup_batch_biased: q must be in [1/8, 8] (got %g)", q);
-    GSAGE_REQUIRE(rowptr && col && seeds && cdf && ids && pair_w, "unsup_batch_biased: null pointer");
-    GSAGE_REQUIRE(n_rows > 0 && B > 0 && B < (1LL << 31) && Q > 0 && Q < (1LL << 31), "unsup_batch_biased: bad sizes");
-    GSAGE_REQUIRE(walk_len >= 1 && walk_len <= UNSUP_WALK_MAX, "unsup_batch_biased: needs 1 <= walk_len <= %d",
-                  UNSUP_WALK_MAX);
-    GSAGE_REQUIRE(cdf_total > 0.0 && cdf_total <= 1.7976931348623157e308,
-                  "unsup_batch_biased: the negatives' weights sum to %g (every row has weight 0?)", cdf_total);
     UnsupBiasedParams bp;
     (void)walk_bias_make(p, q, 0.0, bp.b);                                        // (the limits were checked above)
-    UnsupParams &u = bp.u;
-    u.rowptr = rowptr; u.col = col; u.seeds = seeds; u.cdf = cdf; u.edge_cdf = edge_cdf; u.call_ctr = call_ctr;
-    u.ids = ids; u.pair_w = pair_w; u.err_flag = err_flag; u.n_rows = n_rows; u.B = B; u.Q = Q; u.call_base = call_base;
-    u.g0 = g0; u.cdf_total = cdf_total; u.seed_lo = (uint32_t)seed; u.seed_hi = (uint32_t)(seed >> 32);
-    u.walk_len = walk_len; u.walk_blocks = (int32_t)ceil_div(B, 4);              // a wave per walk, four to a workgroup
-    launch(k_unsup_batch_biased, dim3((unsigned)(u.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream,
-           bp);
+    unsup_fill(bp.u, rowptr, col, edge_cdf, n_rows, seeds, B, 4, walk_len, Q, cdf, cdf_total, seed, call_ctr, call_base,
+               g0, ids, pair_w, err_flag);                                        // a wave per walk, four to a workgroup
+    int rc = unsup_check("unsup_batch_biased", bp.u, false);
+    if (rc != GSAGE_OK) return rc;
+    launch(k_unsup_batch_biased, unsup_grid(bp.u), dim3(256), 0, (hipStream_t)stream, bp);
     return check_launch("unsup_batch_biased");
 }
 
@@ -789,15 +781,12 @@ int gsage_unsup_batch_temporal(const int64_t *rowptr, const int32_t *col, const 
                   "unsup_batch_temporal: cdf_total, the sum of the negatives' weights, is %g (every row has weight 0?)",
                   cdf_total);
     UnsupTemporalParams tp;
-    UnsupParams &u = tp.u;
-    u.rowptr = rowptr; u.col = col; u.seeds = seeds; u.cdf = cdf; u.edge_cdf = nullptr; u.call_ctr = call_ctr;
-    u.ids = ids; u.pair_w = pair_w; u.err_flag = err_flag; u.n_rows = n_rows; u.B = B; u.Q = Q; u.call_base = call_base;
-    u.g0 = g0; u.cdf_total = cdf_total; u.seed_lo = (uint32_t)seed; u.seed_hi = (uint32_t)(seed >> 32);
-    u.walk_len = walk_len; u.walk_blocks = (int32_t)ceil_div(B, 256 / TEAM);     // a team per walk, sixteen to a workgroup
+    unsup_fill(tp.u, rowptr, col, nullptr, n_rows, seeds, B, 256 / TEAM, walk_len, Q, cdf, cdf_total, seed, call_ctr,
+               call_base, g0, ids, pair_w, err_flag);                             // a team per walk, sixteen to a workgroup
     tp.etime = etime; tp.times = times; tp.n_valid = n_valid; tp.out_times = out_times;
     auto kernel = inherit == GSAGE_TEMPORAL_INHERIT_EDGE ? k_unsup_batch_temporal<GSAGE_TEMPORAL_INHERIT_EDGE>
                                                          : k_unsup_batch_temporal<GSAGE_TEMPORAL_INHERIT_SEED>;
-    launch(kernel, dim3((unsigned)(u.walk_blocks + ceil_div(Q, 256))), dim3(256), 0, (hipStream_t)stream, tp);
+    launch(kernel, unsup_grid(tp.u), dim3(256), 0, (hipStream_t)stream, tp);
     return check_launch("unsup_batch_temporal");
 }
 

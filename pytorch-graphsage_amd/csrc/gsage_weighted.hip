@@ -16,7 +16,7 @@
 //                              [0, T) by a 64 x 64 -> high 64 multiplication, then the plain binary search for the
 //                              first entry of the row above it.  The n draws of a parent sit in consecutive lanes: the
 //                              first probes of their searches read the same words.
-//   gsage_sample_hops_weighted every hop of a frontier in ONE launch: the geometry of sample_hops_workgroup
+//   gsage_sample_hops_weighted every hop of a frontier in ONE launch: frontier_walk
 //                              (gsage_sample_dev.h: a workgroup per seed sub-tree, the previous hop in LDS), each
 //                              sample the draw above.  The search probes seven evenly spaced entries per round, issued
 //                              together (cdf_first_above_k8): three dependent rounds on a row of 420 edges where the
@@ -160,51 +160,24 @@ k_sample_weighted(const int64_t *__restrict__ rowptr, const int32_t *__restrict_
             out[t] = 0;
             continue;
         }
-        const uint64_t g = g0 + (uint64_t)t;
-        const uint64_t blk = g >> 1;
-        const philox4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)call, (uint32_t)(call >> 32),
-                                        seed_lo, seed_hi ^ WEIGHTED_TAG);
-        const uint64_t r64 = philox_r64(r, (g & 1ull) != 0);
-        const uint64_t x = __umul64hi(r64, T);            // < T
+        const uint64_t x = __umul64hi(philox_word64(g0 + (uint64_t)t, call, seed_lo, seed_hi ^ WEIGHTED_TAG), T);    // < T
         out[t] = (int64_t)col[cdf_first_above(cdf, beg, end, x)];
     }
 }
 
-// All hops of a weighted frontier: sample_hops_workgroup's walk (same seeds per workgroup, same ping-pong LDS buffers,
-// same ids layout, the LDS barrier between hops) with gsage_sample_csr_weighted's draw per sample.  The n children of a
-// parent sit in consecutive lanes: their loads of rowptr and of the row's total are the same words.
+// All hops of a weighted frontier: the frontier walk of gsage_sample_dev.h with gsage_sample_csr_weighted's draw per
+// sample, a lane each.  The n children of a parent sit in consecutive lanes: their loads of rowptr and of the row's
+// total are the same words.
 template <bool KARY>
 __global__ void __launch_bounds__(256)
 k_sample_hops_weighted(const HopsParams p, const uint64_t *__restrict__ cdf)
 {
     extern __shared__ int64_t frontier[];
-    const int seed0 = (int)blockIdx.x * p.spw;
-    const int nseed = min(p.spw, p.B - seed0);
-    if (nseed <= 0) return;
-    int width = 1, widest = 1;
-    for (int k = 1; k <= p.n_hops; ++k) { width *= p.fan[k]; widest = max(widest, width); }
-    int64_t *cur = frontier, *nxt = frontier + (int64_t)p.spw * widest;
-    if (p.seed_queue) {           // take the seeds from the queue (and publish them as hop 0)
-        const int64_t b = (int64_t)((uint64_t)(*p.batch_idx + p.batch_base) % (uint64_t)p.n_batches);
-        for (int t = threadIdx.x; t < nseed; t += 256) {
-            const int64_t v = p.seed_queue[b * p.B + seed0 + t];
-            cur[t] = v;
-            p.ids[p.off[0] + seed0 + t] = v;
-        }
-    } else {
-        for (int t = threadIdx.x; t < nseed; t += 256) cur[t] = p.ids[p.off[0] + seed0 + t];
-    }
-    lds_barrier();              // LDS only: the ids stored to HBM are not read back in this launch
-    const uint64_t ctr = p.call_ctr ? *p.call_ctr : 0ull;
-    int64_t per_seed = 1;                            // nodes of hop k per seed
-    for (int k = 1; k <= p.n_hops; ++k) {
-        const uint32_t n = (uint32_t)p.fan[k];
-        per_seed *= n;
-        const int64_t count = per_seed * nseed;      // <= spw * widest: fits the LDS buffer (fill_hops)
-        const uint64_t call = p.call_base + ctr + (uint64_t)(k - 1);
-        const int64_t local0 = (int64_t)seed0 * per_seed;             // first sample of this WG in hop k
-        for (int64_t t = threadIdx.x; t < count; t += 256) {
-            const int64_t id = cur[(uint32_t)t / n];
+    Frontier f;
+    if (!frontier_setup<256>(p, (int)blockIdx.x, frontier, f)) return;
+    frontier_walk(p, f, [&](const Hop &h) {
+        for (int64_t t = threadIdx.x; t < h.count; t += 256) {
+            const int64_t id = f.cur[(uint32_t)t / h.n];
             int64_t v = 0;                           // the dummy: no drawable edge, or an id outside the graph
             if ((uint64_t)id >= (uint64_t)p.n_rows) {
                 if (p.err_flag) *p.err_flag = 1;
@@ -212,20 +185,14 @@ k_sample_hops_weighted(const HopsParams p, const uint64_t *__restrict__ cdf)
                 const int64_t beg = p.rowptr[id], end = p.rowptr[id + 1];
                 const uint64_t T = end > beg ? cdf[end - 1] : 0ull;
                 if (T != 0) {
-                    const uint64_t g = p.g0[k] + (uint64_t)(local0 + t);
-                    const uint64_t blk = g >> 1;
-                    const philox4 r = philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), (uint32_t)call,
-                                                    (uint32_t)(call >> 32), p.seed_lo, p.seed_hi ^ WEIGHTED_TAG);
-                    const uint64_t x = __umul64hi(philox_r64(r, (g & 1ull) != 0), T);     // < T
+                    const uint64_t r64 = philox_word64(hop_sample(p, h, t), h.call, p.seed_lo, p.seed_hi ^ WEIGHTED_TAG);
+                    const uint64_t x = __umul64hi(r64, T);                                 // < T
                     v = (int64_t)p.col[KARY ? cdf_first_above_k8(cdf, beg, end, x) : cdf_first_above(cdf, beg, end, x)];
                 }
             }
-            nxt[t] = v;
-            p.ids[p.off[k] + local0 + t] = v;
+            hop_store(p, f, h, t, v);
         }
-        lds_barrier();
-        int64_t *tmp = cur; cur = nxt; nxt = tmp;
-    }
+    });
 }
 
 inline int weighted_grid(int64_t items, int per_block, int cap)

@@ -3,6 +3,7 @@ embedding table, the sharded L1 head; the data-parallel step as ONE list with a 
 (two ranks: tests/test_gpu_dist.py over gloo)."""
 import ctypes
 import os
+import re
 import subprocess
 import sys
 
@@ -472,3 +473,23 @@ def test_fused_sampler_with_several_seeds_per_workgroup(spw):
                         "-k", "fused_sampler_consumes or queue"], env=env, cwd=ROOT, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("spw", ["2", "4"])
+def test_variant_samplers_with_several_seeds_per_workgroup(spw):
+    """The weighted, distinct and temporal all-hops kernels stand on the same frontier walk as the uniform sampler
+    (seed0 / nseed / local0 of a workgroup's seeds), so their frontiers do not depend on GSAGE_HOPS_SPW either: their
+    frontier-level tests again, in a process that sets it.  Their shapes include batches that are no multiple of 4
+    (the last workgroup holds fewer seeds than the others) and batches smaller than 2 (one short workgroup)."""
+    env = dict(os.environ, GSAGE_HOPS_SPW=spw)
+    files = ["test_gpu_weighted_engine.py", "test_gpu_distinct.py", "test_gpu_temporal_hops.py"]
+    # one child for the three files (-k also matches a test's module): the temporal file whole, the others' frontier tests
+    pick = ("test_gpu_temporal_hops or (test_gpu_distinct and all_hops) or "
+            "(test_gpu_weighted_engine and (frontier_equals or seed_queue or rank_offsets))")
+    r = subprocess.run([sys.executable, "-m", "pytest"] + [os.path.join(ROOT, "tests", f) for f in files] +
+                       ["-q", "-x", "-p", "no:cacheprovider", "-m", "gpu", "-k", pick], env=env, cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    # 6 + 2 + 1 + 1 weighted, 7 + 4 distinct and the 36 temporal cases: a renamed file must not shrink the selection unseen
+    passed = re.search(r"(\d+) passed", r.stdout)
+    assert passed and int(passed.group(1)) >= 57 and " deselected" in r.stdout, r.stdout[-500:]
